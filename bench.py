@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the on-the-fly kernel matrix-vector product on MI355X: point-pair interactions per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|4shard|5|attn|softmax]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|4shard|5|attn|softmax] [--full] [--dump-outputs DIR]
+
+A plain run sets the workload up, warms it up, times exactly K steps, writes the last step's outputs if
+``--dump-outputs`` is given and prints the result line: nothing else.  ``--full`` adds what the headline figure does
+not need (see below): the error leg against the oracle, the other squared-distance forms, the CPU baselines, the
+mixed-precision solve of config 5 and the other configs.
+
+``--dump-outputs DIR`` writes what the timed path returned in its last step as ``DIR/<name>.npy`` (float64 or float32,
+at most 64 MB in all; a larger output is cut to a fixed seeded sample of its rows, whose indices go to
+``DIR/<name>_rows.npy``).  The inputs are seeded, so two builds can be compared output for output.
 
 ``--config`` names a BASELINE.json config (default 2, the one the headline metric is quoted on):
 
@@ -22,9 +31,9 @@
   softmax (not a BASELINE config) softmax attention exp(<x,y>) (README.md:51-59), row-normalised, x = y ~ N(0,1)^64,
           N = M = 65536, E = 64, bf16 MFMA tiles with the per-target online shift (kmvp_mfma.hpp).
 
-The default run (config 2, one GPU) also measures configs 2shard, 3, softmax, 4shard, 5 and the D = 3 attention shape in the same
-process AFTER the timed region of the headline line, a few steps each, and appends them as ``other_configs``
-(``--no-other-configs`` skips that).
+The default run with ``--full`` (config 2, one GPU) also measures configs 2shard, 3, softmax, 4shard, 5 and the D = 3
+attention shape in the same process AFTER the timed region of the headline line, a few steps each, and appends them as
+``other_configs`` (``--no-other-configs`` skips that).
 
 With N > 1 GPUs the M sources are sharded over the ranks (one process per GPU) and the (N, E) partial sums are
 summed by one RCCL all-reduce inside every step: total work is fixed -> "scaling": "strong".  Rank 0 prints ONE
@@ -38,7 +47,7 @@ own stream, include/kmvp.h ``kmvp_last_kernel_ms``): ``achieved`` = ALGORITHMIC 
 figure x pairs, no padding) / average kernel time; ``frac_basis`` says which unit's peak ``peak`` is and why;
 ``traffic`` is HBM-side bytes per launch from a rocprofv3 PMC run of the same workload (``traffic_source``
 names the committed file; it is NOT measured in this run, and null when no profile of this kernel exists).
-``cpu_baseline`` is test infrastructure timed on this box's host cores: ``port`` = the C/OpenMP restatement of
+``cpu_baseline`` (``--full``) is test infrastructure timed on this box's host cores: ``port`` = the C/OpenMP restatement of
 the reference's arithmetic (oracle/kmvp_oracle.c) on a bounded row sample of the SAME workload; ``dense`` = the
 numpy restatement of what the reference itself does (materialise K in fit(), then ``K @ b`` in query():
 bruteforce.py:113-153) at the sizes a dense matrix allows.
@@ -134,9 +143,14 @@ def parse(argv=None):
     p.add_argument("--precision", choices=["float32", "float64"], default=None, help="config 2 only")
     p.add_argument("--sqdists", choices=["auto", "difference", "expanded", "cells", "cells-valu"], default="auto",
                    help="squared-distance form (the reference's fast_sqdists flag)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also the error leg, the other squared-distance forms, the CPU baselines, config 5's refined solve and "
+                        "(default run) the other configs; a plain run only times the headline steps")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the timed path returned in its last step as DIR/<name>.npy (at most 64 MB in all)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full only: skip the CPU baselines")
     p.add_argument("--no-other-configs", action="store_true",
-                   help="default run only: do not measure configs 3 / 4shard / 5 / attn after the headline line's timed region")
+                   help="--full default run only: do not measure configs 3 / 4shard / 5 / attn after the headline line's timed region")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU time budget of the row-sample baseline")
     p.add_argument("--cpu-dense-sizes", default="10000", help="N = M of the dense numpy baseline (comma separated; "
                                                                "SURVEY 8d asks for 10000,20000,30000)")
@@ -537,6 +551,26 @@ def time_steps(W, steps, warmup, barrier):
     return time.perf_counter() - t0, kernel_ms, total_ms, allreduce_ms
 
 
+DUMP_BYTES = 60_000_000  # under the 64 MB budget of --dump-outputs with room for the .npy headers
+
+
+def dump_outputs(path, arrays, np):
+    """--dump-outputs: every (name, array) as path/<name>.npy, float64 (float32 kept as it is).  An array beyond the
+    budget is cut to a fixed seeded sample of its rows (sorted), whose indices are written as path/<name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        if arr.dtype not in (np.float32, np.float64):
+            arr = arr.astype(np.float64)
+        if arr.nbytes > DUMP_BYTES // len(arrays):
+            row_bytes = arr.nbytes // arr.shape[0]
+            keep = DUMP_BYTES // len(arrays) // (row_bytes + 8)
+            rows = np.sort(np.random.RandomState(0).choice(arr.shape[0], size=keep, replace=False))
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+            arr = arr[rows]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(arr))
+
+
 def error_leg(W, a, meta):
     """Against the float64 C restatement of the reference on 256 sampled rows (solver: the residual on those rows)."""
     import c_oracle
@@ -769,6 +803,8 @@ def main(argv=None):
     cfg = args.config
     steps = args.steps if args.steps is not None else {"2": 10, "2shard": 10, "3": 10, "4shard": 3, "4": 2, "5": 2, "attn": 10, "softmax": 10}[cfg]
     warmup = args.warmup if args.warmup is not None else {"2": 2, "2shard": 10, "3": 50, "attn": 50, "softmax": 50}.get(cfg, 1)
+    if steps < 1 or warmup < 0:
+        raise SystemExit(f"--steps {steps} --warmup {warmup}: at least one timed step, no negative warm-up")
 
     W = Workload(cfg, args, device, comm, np, n=args.n, sqdists=args.sqdists, kernel_arg=args.kernel,
                  precision_arg=args.precision)
@@ -790,10 +826,13 @@ def main(argv=None):
         rccl_ranks = int(seen[0])
         if rccl_ranks != world and cfg != "2shard":
             raise SystemExit(f"[rank {rank}] the communicator spans {rccl_ranks} rank(s), expected {world}")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"result": a}, np)  # (N, E) product / the solve's (N, E) solution
 
     # the other forms on the same resident data, for the record (config 2, one GPU, untimed region)
     others = {}
-    if cfg == "2" and args.sqdists == "auto" and world == 1 and kname in ("cellmm_kernel", "cellmm16_kernel", "cell_kernel", "fast_kernel"):
+    if (args.full and cfg == "2" and args.sqdists == "auto" and world == 1
+            and kname in ("cellmm_kernel", "cellmm16_kernel", "cell_kernel", "fast_kernel")):
         algo = W.algo
 
         def side_run(code):
@@ -815,8 +854,6 @@ def main(argv=None):
     out = None
     if rank == 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        # ---- error leg of the metric: against the float64 C restatement of the reference on sampled rows
-        max_err, rel_err, err = error_leg(W, a, meta)
         pairs_per_step = W.pairs * (meta["cg_iterations"] + 1) if solver else W.pairs  # + the true-residual product
 
         sec_per_step = elapsed / steps
@@ -838,7 +875,7 @@ def main(argv=None):
             "dtype": {"float32": "f32", "float64": "f64", "bfloat16": "bf16"}[precision],
             "data": "synthetic",
             "config": {
-                "workload": W.describe(args.gpus, err.get("iterations")),
+                "workload": W.describe(args.gpus, meta.get("cg_iterations")),
                 "sharding": (f"sources split over {args.gpus} GPUs, one "
                              f"{'RCCL all-reduce' if args.exchange == 'rccl' else 'HOST-STAGED gloo all-reduce (rehearsal)'} of "
                              f"the (N,E) f64 sums per step" if args.gpus > 1 else "single GPU"),
@@ -848,21 +885,26 @@ def main(argv=None):
             "exchange": ("host-staged rehearsal as rank 4 of 8 with nothing added: rccl_ranks is that communicator's size"
                          if cfg == "2shard" else (args.exchange if args.gpus > 1 else None)),
             "device_bytes": meta.get("device_bytes"),
-            "max_abs_err": max_err,
-            "max_rel_err": rel_err,
-            "error_reference": ("direct float64 numpy evaluation of exp(<x,y>) (oracle/kmvp_oracle.py exp_dot_product; PARITY "
-                                "UNPINNED: the kernel exists in the reference's README only), 256 sampled rows"
-                                if kernel == "exp-dot" else
-                                "float64 oracle/kmvp_oracle.c (C restatement of the reference's scipy/numpy bruteforce, pinned "
-                                "by tests/golden), 256 sampled rows; all rows: tests/test_gpu_parity.py::test_config2_*"),
             "roofline": r,
         }
         if solver:
-            out["solver"] = err
             out["config"]["operator_ms"] = W.operator_ms
-            out["solver"]["mixed_precision_refinement"] = W.refined_solve()
+        if args.full:
+            # ---- error leg of the metric: against the float64 C restatement of the reference on sampled rows
+            max_err, rel_err, err = error_leg(W, a, meta)
+            out["max_abs_err"] = max_err
+            out["max_rel_err"] = rel_err
+            out["error_reference"] = (
+                "direct float64 numpy evaluation of exp(<x,y>) (oracle/kmvp_oracle.py exp_dot_product; PARITY "
+                "UNPINNED: the kernel exists in the reference's README only), 256 sampled rows"
+                if kernel == "exp-dot" else
+                "float64 oracle/kmvp_oracle.c (C restatement of the reference's scipy/numpy bruteforce, pinned "
+                "by tests/golden), 256 sampled rows; all rows: tests/test_gpu_parity.py::test_config2_*")
+            if solver:
+                out["solver"] = err
+                out["solver"]["mixed_precision_refinement"] = W.refined_solve()
         out.update(others)
-        if not args.no_cpu_baseline and args.gpus == 1:
+        if args.full and not args.no_cpu_baseline and args.gpus == 1:
             if W.shard is not None:
                 lo, hi = W.shard
                 base = cpu_port(kernel, W.y[lo:hi], W.b[lo:hi], "float32", args.cpu_seconds, x64=W.y, shard=(lo, n))
@@ -882,7 +924,7 @@ def main(argv=None):
     default_shape = (cfg == "2" and world == 1 and n == FULL_SIZE["2"] and args.kernel is None and args.precision is None
                      and args.sqdists == "auto")
     if rank == 0:
-        if default_shape and not args.no_other_configs:
+        if default_shape and args.full and not args.no_other_configs:
             del W, a
             out["other_configs"] = measure_other_configs(args, device, np)
         print(json.dumps(out), flush=True)

@@ -107,3 +107,20 @@ def make_solver_inputs(case):
     y = rs.rand(case["n"], case["D"])
     b = rs.randn(case["n"], 1)
     return y, b
+
+
+# Pareto fronts (``golden/pareto.json``, written by ``make_pareto_golden.py`` and checked by test_abi_and_host.py)
+def pareto_point_set(seed, n, ties):
+    """(label, x, y) triples; ``ties`` quantises the values so that equal x / equal y occur."""
+    rs = np.random.RandomState(seed)
+    x = rs.lognormal(size=n)
+    y = rs.lognormal(size=n) * 1e-3
+    if ties:
+        x = np.round(x * ties) / ties
+        y = np.round(y * 1e3 * ties) / (1e3 * ties)
+    return [(f"p{i}", float(x[i]), float(y[i])) for i in range(n)]
+
+
+PARETO_CASES = [dict(seed=1, n=1, ties=0), dict(seed=2, n=7, ties=0), dict(seed=3, n=40, ties=0), dict(seed=4, n=40, ties=2),
+                dict(seed=5, n=60, ties=1), dict(seed=6, n=200, ties=4)]
+PARETO_AXES = [("total-time", "rmse-error"), ("query-time", "max-error"), ("memory-footprint", "median-error")]

@@ -13,29 +13,13 @@ import json
 import os
 import sys
 
-import numpy as np
+from golden_cases import PARETO_AXES as AXES, PARETO_CASES as CASES, pareto_point_set as point_set
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, "/root/reference")
 sys.dont_write_bytecode = True
 
 from kernel_matrix_benchmarks.plotting.utils import create_pointset  # noqa: E402  (the reference)
-
-
-def point_set(seed, n, ties):
-    """(label, x, y) triples; ``ties`` quantises the values so that equal x / equal y occur."""
-    rs = np.random.RandomState(seed)
-    x = rs.lognormal(size=n)
-    y = rs.lognormal(size=n) * 1e-3
-    if ties:
-        x = np.round(x * ties) / ties
-        y = np.round(y * 1e3 * ties) / (1e3 * ties)
-    return [(f"p{i}", float(x[i]), float(y[i])) for i in range(n)]
-
-
-CASES = [dict(seed=1, n=1, ties=0), dict(seed=2, n=7, ties=0), dict(seed=3, n=40, ties=0), dict(seed=4, n=40, ties=2),
-         dict(seed=5, n=60, ties=1), dict(seed=6, n=200, ties=4)]
-AXES = [("total-time", "rmse-error"), ("query-time", "max-error"), ("memory-footprint", "median-error")]
 
 
 def main():

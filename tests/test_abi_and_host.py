@@ -260,13 +260,11 @@ def test_pareto_front_matches_the_reference(expected):
     (plotting/utils.py:15-76, run by tests/make_pareto_golden.py) on seeded point sets with ties and duplicates."""
     import json
 
-    import make_pareto_golden
-
     with open(os.path.join(ROOT, "tests", "golden", "pareto.json")) as f:
         golden = json.load(f)
-    assert len(golden) == len(make_pareto_golden.CASES) * len(make_pareto_golden.AXES) == 18
+    assert len(golden) == len(golden_cases.PARETO_CASES) * len(golden_cases.PARETO_AXES) == 18
     for g in golden:
-        pts = make_pareto_golden.point_set(g["seed"], g["n"], g["ties"])
+        pts = golden_cases.pareto_point_set(g["seed"], g["n"], g["ties"])
         out = metrics.pareto_front(pts)
         assert out["all"]["labels"] == g["all"], g["seed"]
         assert out["front"]["labels"] == g["front"], g["seed"]
@@ -438,6 +436,38 @@ def test_bench_roofline_tables_and_committed_profiles():
         text = open(md).read()
         assert kname in text or (kname == "cellmm_kernel" and "cellmm16_kernel" in text), md
     assert bench.traffic_from_profile("no_such_kernel", "gaussian_1e6_f32") == (None, None)
+
+
+def test_bench_dump_outputs_writes_small_arrays_whole_and_a_seeded_row_sample_of_large_ones(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an array within the budget is written as it is; a larger one is cut to the same seeded,
+    sorted row sample on every run, written beside its row indices, both within the budget; --full is off by default."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)  # no GPU work at import
+    args = bench.parse(["--steps", "4"])
+    assert args.steps == 4 and not args.full and args.dump_outputs is None
+    args = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert args.full and args.dump_outputs == str(tmp_path)
+
+    a = np.random.RandomState(0).randn(1000, 3)
+    bench.dump_outputs(str(tmp_path / "whole"), {"result": a}, np)
+    got = np.load(tmp_path / "whole" / "result.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, a) and not (tmp_path / "whole" / "result_rows.npy").exists()
+    bench.dump_outputs(str(tmp_path / "f32"), {"result": a.astype(np.float32)}, np)
+    assert np.load(tmp_path / "f32" / "result.npy").dtype == np.float32
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8000)
+    samples = []
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), {"result": a}, np)
+        rows = np.load(tmp_path / run / "result_rows.npy")
+        got = np.load(tmp_path / run / "result.npy")
+        assert rows.dtype == np.float64 and got.nbytes + rows.nbytes <= 8000 and 0 < len(rows) == len(got) < len(a)
+        assert (np.diff(rows) > 0).all() and np.array_equal(got, a[rows.astype(np.int64)])
+        samples.append(rows)
+    assert np.array_equal(samples[0], samples[1])
 
 
 def test_tools_and_entry_points_parse():

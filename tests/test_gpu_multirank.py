@@ -57,7 +57,7 @@ def test_bench_starts_its_own_ranks_and_prints_one_line(config, points):
     relays rank 0's JSON line and exits 0.  Both ranks on GPU 0, host-staged exchange."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", config, "--points", str(points),
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--all-ranks-on-device", "0", "--exchange", "host"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--all-ranks-on-device", "0", "--exchange", "host"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -71,7 +71,8 @@ def test_bench_starts_its_own_ranks_and_prints_one_line(config, points):
 def test_bench_one_gpu_through_the_self_spawn_path_matches_the_in_process_line():
     """`bench.py --gpus 1 --spawn` (the launcher path with one rank, real RCCL communicator of world 1 is not formed:
     world == 1 attaches nothing) prints the same kind of line as the plain in-process run."""
-    common = ["--config", "2", "--points", "200000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs"]
+    common = ["--config", "2", "--points", "200000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+              "--no-other-configs"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     lines = []
     for extra in (["--spawn"], []):

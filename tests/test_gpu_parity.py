@@ -2264,7 +2264,7 @@ def test_bench_configs_at_reduced_size(config, points, tol):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", config, "--points", str(points), "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-other-configs"], capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-configs"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -2279,3 +2279,34 @@ def test_bench_configs_at_reduced_size(config, points, tol):
         assert d["max_rel_err"] <= tol, d["max_rel_err"]
     else:
         assert d["solver"]["converged"] and d["solver"]["residual_rows"] <= 2e-6, d["solver"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_the_last_result(tmp_path):
+    """A plain `bench.py` run (no --full): the contract's keys, exactly --steps timed steps, none of what --full adds;
+    --dump-outputs writes the last step's (N, E) result, which is the product on the benchmark's seeded inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 60000
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "2", "--points", str(n), "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    for key in ("max_rel_err", "cpu_baseline", "other_configs", "difference_form"):
+        assert key not in d, key
+    a = np.load(tmp_path / "out" / "result.npy")
+    assert a.shape == (n, 1) and a.dtype == np.float64
+    rs = np.random.RandomState(n + 3)  # the benchmark's uniform_cube recipe
+    y, b = rs.rand(n, 3), rs.randn(n, 1)
+    rows = np.arange(0, n, 331)
+    truth = c_oracle.product(kernel="gaussian", source_points=y, source_signal=b, rows=rows)
+    assert rel_err(a[rows], truth) <= 1e-5

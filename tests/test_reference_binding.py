@@ -20,8 +20,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE = "/root/reference"
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "kernel_matrix_benchmarks")),
-                                reason="the reference tree is not present on this machine")
+needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "kernel_matrix_benchmarks")),
+                                     reason="the reference tree is not present on this machine")
 
 
 def integration_blocks():
@@ -77,6 +77,7 @@ print("RESULT " + json.dumps(out))
 """
 
 
+@needs_reference
 def test_reference_loader_instantiates_the_plugin_from_the_integration_stub(tmp_path):
     stub, yaml_text = integration_blocks()
     assert "MI355XProduct" in stub and "mi355x-product" in yaml_text and "mi355x-solver" in yaml_text
@@ -110,3 +111,70 @@ def test_reference_loader_instantiates_the_plugin_from_the_integration_stub(tmp_
         assert inst["additional"] == {} and inst["memory"] == 0.0  # no GPU work before prepare_data (main.py:262-308)
     assert s64["cls"] == "MI355XSolver" and s64["is_ref_solver"] and not s64["is_ref_product"]
     assert s64["task"] == "solver" and s64["name"] == "MI355XSolver(float64, cg, rtol=1e-06)"
+
+
+# The same queries without the reference: the project's restatement of the loader (kernel_matrix_benchmarks_amd.definitions)
+# on the INTEGRATION.md blocks, the stub placed as kernel_matrix_benchmarks/algorithms/mi355x.py in a namespace-package overlay.
+CHILD_SELF_CONTAINED = r"""
+import json, os, sys
+overlay, root = sys.argv[1:3]
+sys.path[:0] = [overlay, root]
+from kernel_matrix_benchmarks_amd import definitions as D
+import kernel_matrix_benchmarks_amd.algorithms.base as our_base
+
+out = {}
+yaml_file = os.path.join(overlay, "algos.yaml")
+prod = D.get_definitions(definition_file=yaml_file, dimension=3, dataset="product-cube-D3-E1-M1000000-N1000000-gaussian",
+                         task="product", hardware="GPU", kernel="gaussian", normalize_rows=False)
+att = D.get_definitions(definition_file=yaml_file, dimension=3, dataset="product-cube-D3-E1-M1000-N1000-absolute-exponential",
+                        task="attention", hardware="GPU", kernel="absolute-exponential", normalize_rows=True)
+sol = D.get_definitions(definition_file=yaml_file, dimension=3, dataset="solver-cube-D3-E1-M100000-N100000-gaussian",
+                        task="solver", hardware="GPU", kernel="gaussian", normalize_rows=False)
+cpu = D.get_definitions(definition_file=yaml_file, dimension=3, dataset="product-cube-D3-E1-M1000-N1000-gaussian",
+                        task="product", hardware="CPU", kernel="gaussian", normalize_rows=False)
+out["counts"] = [len(prod), len(att), len(sol), len(cpu)]
+out["status"] = ["AVAILABLE" if D.algorithm_available(d) else "UNAVAILABLE" for d in prod + att + sol]
+out["modules"] = sorted({d.module for d in prod + att + sol})
+algos = [D.instantiate_algorithm(d) for d in prod + att + sol]
+out["using_reference_bases"] = bool(our_base.USING_REFERENCE_BASES)
+out["instances"] = [dict(cls=type(a).__name__, module=type(a).__module__, name=a.name, str=str(a), task=a.task,
+                         kernel=a.kernel, dimension=a.dimension, normalize_rows=bool(a.normalize_rows),
+                         precision=str(a.precision),
+                         is_ref_product=isinstance(a, our_base.BaseProduct), is_ref_solver=isinstance(a, our_base.BaseSolver),
+                         additional=a.get_additional(), memory=a.get_memory_usage())
+                    for a in algos]
+for a in algos:
+    a.done()
+bad = prod[0]._replace(arguments=dict(prod[0].arguments, kernel="laplacian"))
+try:
+    D.instantiate_algorithm(bad)
+    out["unknown_kernel"] = "accepted"
+except NotImplementedError:
+    out["unknown_kernel"] = "NotImplementedError"
+print("RESULT " + json.dumps(out))
+"""
+
+
+def test_integration_stub_gives_what_the_reference_loader_gave(tmp_path):
+    """Self-contained counterpart of the test above: the INTEGRATION.md blocks, expanded and instantiated by the project's
+    restatement of the reference's loader, give the definitions and plugin instances that the reference's own loader
+    gave on them (tests/golden/reference_loader.json, written by tests/make_reference_loader_golden.py).  Only which base
+    classes the plugin derives from differs: the reference's under the reference, the stand-ins without it."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_loader.json")) as f:
+        golden = json.load(f)
+    stub, yaml_text = integration_blocks()
+    assert "MI355XProduct" in stub and "mi355x-product" in yaml_text and "mi355x-solver" in yaml_text
+    overlay = tmp_path / "overlay"
+    (overlay / "kernel_matrix_benchmarks" / "algorithms").mkdir(parents=True)  # no __init__.py: namespace packages
+    (overlay / "kernel_matrix_benchmarks" / "algorithms" / "mi355x.py").write_text(stub)
+    (overlay / "algos.yaml").write_text(yaml_text)
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+    env.pop("PYTHONPATH", None)
+    run = subprocess.run([sys.executable, "-c", CHILD_SELF_CONTAINED, str(overlay), ROOT], capture_output=True, text=True,
+                         env=env, cwd=str(tmp_path), timeout=300)
+    assert run.returncode == 0, run.stdout + run.stderr
+    out = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+
+    assert golden["using_reference_bases"] and golden["same_class_objects"]  # recorded under the reference
+    assert not out.pop("using_reference_bases")
+    assert out == {k: v for k, v in golden.items() if k not in ("using_reference_bases", "same_class_objects")}
