@@ -347,15 +347,29 @@ cellmm_kernel(const CellmmArgs a) {
 //   lane l:  cc = l & 15,  kg = l >> 4 (k group 8 kg .. 8 kg + 7):  slot half h = kg & 1,  source group G = kg >> 1
 //   A operand (sources):  lane (cc, kg) holds the slots (h) of source row 16 G + cc of the tile       -- A[cc][8 kg + j]
 //   B operand (targets):  lane (cc, kg) holds the slots (h) of target cc of the half tile             -- B[8 kg + j][cc]
-//   accumulator (4 registers):  rows 4 (l >> 4) + reg, column cc; row sum = the 4 registers, then lanes l ^ 16 and l ^ 32
-//                               (v_permlane16_swap, v_permlane32_swap)
+//   accumulator (4 registers):  rows 4 (l >> 4) + reg, column cc; column sum = the 4 registers, then lanes l ^ 16 and l ^ 32
+//                               (v_permlane16_swap, v_permlane32_swap; cellmm16_fold4)
 // A wave owns the same TT tiles of 32 targets = 2 TT half tiles: 4 x 2 TT accumulator registers (64 at TT = 8, where
-// cellmm_kernel needs 128) and 4 x 2 TT operand registers (64 against 32).
-__device__ __forceinline__ float cellmm16_rows_sum(float v) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(a[0]) + __uint_as_float(a[1]);   // + lane ^ 16
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);  // + lane ^ 32
+// cellmm_kernel needs 128) and 4 x 2 TT operand registers (64 against 32).  At the fold each lane takes over TT / 2 of the
+// wave's targets (cellmm16_fold4) and keeps their offsets, U_i(S) and fp64 sums in registers: 200 VGPRs at TT = 8.
+
+// The fold, transposed: one target per lane.  Every lane holds the partial row sums of all 2 TT half tiles, but the column
+// sum of half tile u is wanted once, not in all 64 lanes.  A butterfly over four half tiles a, b, c, d (x = this lane's
+// (d0 + d1) + (d2 + d3) of each) leaves lane row k = l >> 4 with the column sums of the k-th of them:
+//   permlane16_swap(a, b): odd rows of a <-> even rows of b, so the pair's sum is a[l] + a[l ^ 16] in rows 0 and 2 and
+//                          b[l ^ 16] + b[l] in rows 1 and 3 (w0; (c, d) likewise: w1)
+//   permlane32_swap(w0, w1): upper half of w0 <-> lower half of w1, the pair's sum is the full column sum of a in row 0,
+//                          b in row 1, c in row 2, d in row 3
+// Each target's additions are those of one shared-operand swap per level, (x_cc + x_cc+16) + (x_cc+32 + x_cc+48): the
+// order the one-value-per-swap reduction used, so the sums are the same bit for bit.  12 swaps and 12 adds for 16 half
+// tiles, and U, vprev and the fp64 sums shrink from 2 TT to TT / 2 (at least 1) values per lane.
+__device__ __forceinline__ float cellmm16_fold4(float a, float b, float c, float d) {
+  const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  const float w0 = __uint_as_float(p[0]) + __uint_as_float(p[1]);
+  const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(c), __float_as_uint(d), false, false);
+  const float w1 = __uint_as_float(q[0]) + __uint_as_float(q[1]);
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(w0), __float_as_uint(w1), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 // sum over the wave's 32 distinct source rows (held by the lanes of rows 0 and 2 of 16; rows 1 and 3 duplicate them)
 __device__ __forceinline__ float cellmm16_sources_sum(float v) {
@@ -367,6 +381,10 @@ __device__ __forceinline__ float cellmm16_sources_sum(float v) {
          __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 47));
 }
 
+#ifndef CMM16_NOFOLD
+#define CMM16_NOFOLD 0  // 1: timing only, wrong sums -- the fold and U compiled out, their inputs kept live (what the fold costs)
+#endif
+
 template <int TT>
 __global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(TT >= 8 ? 2 : 1)))
 cellmm16_kernel(const CellmmArgs a) {
@@ -374,7 +392,8 @@ cellmm16_kernel(const CellmmArgs a) {
   constexpr int SB = CMM_STAGE_BYTES;
   constexpr int PIECES = SB / (16 * BLOCK_THREADS);
   constexpr float LOG2E = 1.4426950408889634f;
-  constexpr int HT = 2 * TT;  // half tiles of 16 targets
+  constexpr int HT = 2 * TT;          // half tiles of 16 targets
+  constexpr int NG = (HT + 3) / 4;    // fold groups of four half tiles (TT = 1: one, its rows 2 and 3 padded with zeros)
   __shared__ __attribute__((aligned(16))) unsigned char lds[2][SB];
 
   int tb, seg;
@@ -387,35 +406,37 @@ cellmm16_kernel(const CellmmArgs a) {
   const int rs = 16 * (kg >> 1) + cc;  // this lane's source row in a tile of 32
   const int64_t tile0 = a.tile_base + ((int64_t)tb * WAVES_PER_BLOCK + wave) * TT;
 
-  constexpr bool HOLD_D = TT < 8;
-  __shared__ __attribute__((aligned(16))) float dsh[HOLD_D ? 1 : WAVES_PER_BLOCK][HOLD_D ? 1 : HT][16][4];
-  float dl[HOLD_D ? HT : 1][3], cT[3], U[HT];
+  float cT[3];
   f16x8 xb[HT];
 #pragma unroll
   for (int u = 0; u < HT; ++u) {
-    const int64_t tile = tile0 + (u >> 1);
-    const f32x4 v = *reinterpret_cast<const f32x4*>(a.xd + (tile * CELL_TILE + 16 * (u & 1) + cc) * 4);
-    const f32x4 m = *reinterpret_cast<const f32x4*>(a.tmeta + tile * 4);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if constexpr (HOLD_D) dl[u][c] = v[c];
-      else if (kg == 0) dsh[wave][u][cc][c] = v[c];
-      if (u == 0) cT[c] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m[c])));  // one cell per wave
-    }
+    const f32x4 v = *reinterpret_cast<const f32x4*>(a.xd + ((tile0 + (u >> 1)) * CELL_TILE + 16 * (u & 1) + cc) * 4);
     xb[u] = cellmm_target_operand(v, h);
-    U[u] = 0.f;
+  }
+  {
+    const f32x4 m = *reinterpret_cast<const f32x4*>(a.tmeta + tile0 * 4);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) cT[c] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m[c])));  // one cell per wave
+  }
+  // this lane's own targets at the fold: column cc of half tile 4 g + kg (clamped where TT = 1 pads the group)
+  float dl[NG][3], U[NG], vprev[NG];
+  double outd[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int u = 4 * g + kg < HT ? 4 * g + kg : HT - 1;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(a.xd + ((tile0 + (u >> 1)) * CELL_TILE + 16 * (u & 1) + cc) * 4);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dl[g][c] = v[c];
+    U[g] = 0.f;
+    vprev[g] = 0.f;
+    outd[g] = 0.0;
   }
 
   f32x4 acc[HT];
-  double outd[HT];
-  float vprev[HT];
 #pragma unroll
-  for (int u = 0; u < HT; ++u) {
-    outd[u] = 0.0;
-    vprev[u] = 0.f;
+  for (int u = 0; u < HT; ++u)
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[u][k] = 0.f;
-  }
 
   const int64_t s_begin = (int64_t)seg * a.seg_stages;
   int64_t s_end = s_begin + a.seg_stages;
@@ -443,15 +464,21 @@ cellmm16_kernel(const CellmmArgs a) {
   float S0 = 0.f, S0c = 0.f;
   float D1[3] = {0.f, 0.f, 0.f};
 
-  auto fold = [&]() {  // as in cellmm_kernel
+  auto fold = [&]() {  // as in cellmm_kernel, transposed (cellmm16_fold4)
+#if CMM16_NOFOLD
+    asm volatile("" ::"v"(S0), "v"(S0c));
+#else
     const float s0 = cellmm16_sources_sum(S0) * CMM_TARGET_SCALE;
+    float x[4 * NG];
 #pragma unroll
-    for (int u = 0; u < HT; ++u) {
-      const f32x4 d = acc[u];
-      const float v = cellmm16_rows_sum((d[0] + d[1]) + (d[2] + d[3]));
-      outd[u] += (double)(U[u] * ((v - vprev[u]) + s0));
-      vprev[u] = v;
+    for (int u = 0; u < 4 * NG; ++u) x[u] = u < HT ? (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]) : 0.f;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const float v = cellmm16_fold4(x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]);
+      outd[g] += (double)(U[g] * ((v - vprev[g]) + s0));
+      vprev[g] = v;
     }
+#endif
     S0 = 0.f;
     S0c = 0.f;
   };
@@ -460,20 +487,18 @@ cellmm16_kernel(const CellmmArgs a) {
     key_s = ks;
 #pragma unroll
     for (int c = 0; c < 3; ++c) D1[c] = (cT[c] - cs[c]) * LOG2E;
+#if !CMM16_NOFOLD
 #pragma unroll
-    for (int u = 0; u < HT; ++u) {
-      f32x4 dv;
-      if constexpr (!HOLD_D) dv = *reinterpret_cast<const f32x4*>(&dsh[wave][u][cc][0]);
+    for (int g = 0; g < NG; ++g) {
       float s2 = 0.f;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        float df;
-        if constexpr (HOLD_D) df = dl[u][c] + (cT[c] - cs[c]);
-        else df = dv[c] + (cT[c] - cs[c]);
+        const float df = dl[g][c] + (cT[c] - cs[c]);
         s2 = fmaf(df, df, s2);
       }
-      U[u] = kexp2(s2 * -LOG2E);
+      U[g] = kexp2(s2 * -LOG2E);
     }
+#endif
   };
 
   for (int64_t s = s_begin; s < s_end; ++s) {
@@ -483,20 +508,26 @@ cellmm16_kernel(const CellmmArgs a) {
     const unsigned char* p_ef = base + CMM_E_OFF + rs * 16;
     const unsigned char* p_b = base + CMM_B_OFF + rs * 4;
     const f32x4* hdr = reinterpret_cast<const f32x4*>(base + CMM_HDR_OFF);
+    // the stage's cell keys, lane q holding tile q's: a tile's key is then one v_readlane, and the reads of its e and b
+    // no longer queue behind a header read and its wait
+    const int keys = lane < CMM_STAGE_TILES ? __float_as_int(hdr[lane < CMM_STAGE_TILES ? lane : 0][3]) : -1;
 #pragma unroll 1
     for (int q = 0; q < CMM_STAGE_TILES; ++q) {
-      const f32x4 cs = hdr[q];
-      const int ks = __builtin_amdgcn_readfirstlane(__float_as_int(cs[3]));
-      if (ks < 0) break;
-      if (ks != key_s) new_cell(cs, ks);
+      const int ks = __builtin_amdgcn_readlane(keys, q);
+      if (ks < 0) break;                         // pad tiles (key -1) only trail the last source tile (wave-uniform)
+      if (ks != key_s) new_cell(hdr[q], ks);     // wave-uniform, once per ~30 tiles
       // ---- A = psi_k(e_j) W_j(T) b_j for source row rs, slot half h (as cellmm_kernel)
       const f32x4 ef = *reinterpret_cast<const f32x4*>(p_ef);
       const float bq = *reinterpret_cast<const float*>(p_b);
       p_ef += CELL_TILE * 16;
       p_b += CELL_TILE * 4;
-      const f32x4 a14 = h ? f32x4{ef[2], ef[0] * ef[2], ef[2] * ef[2], ef[0] * ef[1]}
-                          : f32x4{ef[0], ef[1], ef[0] * ef[0], ef[1] * ef[1]};
-      const float a5 = h ? ef[1] * ef[2] : ef[1];
+      // the lane half's five monomial factors from three selects (v_cndmask) and four products, no exec-masked branch:
+      // h = 0: x, y, x x, y y | y;  h = 1: z, x z, z z, x y | y z  (the products with 1 are exact)
+      const float m0 = h ? ef[2] : ef[0];
+      const float m1 = h ? ef[0] : ef[1];
+      const float m2 = h ? ef[2] : 1.f;
+      const f32x4 a14 = f32x4{m0, m1 * m2, m0 * m0, m1 * ef[1]};
+      const float a5 = ef[1] * m2;
       const float arg = fmaf(ef[0], D1[0], fmaf(ef[1], D1[1], fmaf(ef[2], D1[2], ef[3])));
       const float wb = kexp2(arg) * bq;
       {
@@ -524,12 +555,17 @@ cellmm16_kernel(const CellmmArgs a) {
     __syncthreads();
   }
   if (key_s >= 0) fold();
+#if CMM16_NOFOLD
+#pragma unroll
+  for (int u = 0; u < HT; ++u) asm volatile("" ::"v"(acc[u][0]), "v"(acc[u][1]), "v"(acc[u][2]), "v"(acc[u][3]));
+#endif
 
+  // lanes 0-31 store tile 2 g's 32 slots, lanes 32-63 tile 2 g + 1's
   const double inv = (double)a.scale[1];
 #pragma unroll
-  for (int u = 0; u < HT; ++u)
-    if (kg == 0)
-      a.part[(int64_t)seg * a.n_slots + (tile0 + (u >> 1) - a.tile_base) * CELL_TILE + 16 * (u & 1) + cc] = outd[u] * inv;
+  for (int g = 0; g < NG; ++g)
+    if (4 * g + kg < HT)
+      a.part[(int64_t)seg * a.n_slots + (tile0 + 2 * g + (kg >> 1) - a.tile_base) * CELL_TILE + 16 * h + cc] = outd[g] * inv;
 }
 
 // shape: 0 = cellmm_kernel (32x32x16), 1 = cellmm16_kernel (16x16x32)
