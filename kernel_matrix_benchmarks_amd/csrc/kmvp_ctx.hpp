@@ -1,7 +1,7 @@
 // Shared host-side state of libkmvp.so: the per-GPU context, small helpers and the
 // functions the translation units call across each other.
 //   kmvp_api.hip      the extern "C" surface of include/kmvp.h
-//   kmvp_product.hip  layouts, launch geometry and the three pair-loop paths
+//   kmvp_product.hip  layouts, launch geometry, the pair-loop paths and the policy that picks one
 //   kmvp_solvers.hip  conjugate gradients and MINRES on the product
 #pragma once
 #include <dlfcn.h>

@@ -1,5 +1,6 @@
-// The product a = K b [/ K 1]: kernel layouts, launch geometry, the three pair-loop paths
-// (lowd_kernel / fast_kernel / mfma_kernel) and their common epilogue
+// The product a = K b [/ K 1]: kernel layouts, launch geometry, the host side of the pair-loop paths
+// (difference form, split-bf16 / centred / cell forms, the matrix-core column products, bf16 MFMA),
+// the policy that picks one of them, and their common epilogue
 //   segment reduction -> [RCCL all-reduce over the source shards] -> normalise.
 // Reference call this serves: BruteForceProductBLAS.query (bruteforce.py:130-153).
 #include "kmvp_ctx.hpp"
@@ -243,6 +244,43 @@ __global__ void fill_kernel(double* p, int64_t n, double v) {
 // stream capture) records nothing.
 inline hipError_t mark(kmvp_ctx* c, int i) { return c->async_product ? hipSuccess : hipEventRecord(c->ev[i], c->stream); }
 
+// Last step of every product, once the (N, E) result is queued into c->out: an asynchronous product leaves it on the
+// stream (the caller keeps working there); a synchronous one waits for it and reads the elapsed times of its marks.
+int complete(kmvp_ctx* c, int64_t N, int E) {
+  c->out_n = N;
+  c->out_e = E;
+  if (c->async_product) return KMVP_OK;
+  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_kernel_ms, c->ev[0], c->ev[1]));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
+  c->last_allreduce_ms = 0.f;
+  if (c->exchanges()) HIP_TRY(c, hipEventElapsedTime(&c->last_allreduce_ms, c->ev[3], c->ev[4]));
+  return KMVP_OK;
+}
+
+// What the shared xs / rec buffers hold: the layout of one path for one kernel and T (targets per lane or tiles per
+// wavefront, and whatever else the layout depends on), packed from one version of the points, and -- the signal image --
+// from one version of the signal for one product kind `sig` (-1: an image that is not reusable as it is).
+struct PackKey {
+  int layout, kernel, T;
+};
+bool points_stale(const kmvp_ctx* c, PackKey k) {
+  return c->packed_points_ver != c->points_ver || c->packed_kernel != k.kernel || c->packed_layout != k.layout ||
+         c->packed_T != k.T;
+}
+bool signal_stale(const kmvp_ctx* c, PackKey k, int sig) {
+  return points_stale(c, k) || sig < 0 || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
+}
+void record_packed(kmvp_ctx* c, PackKey k, int sig) {
+  c->packed_points_ver = c->points_ver;
+  c->packed_signal_ver = c->signal_ver;
+  c->packed_layout = k.layout;
+  c->packed_kernel = k.kernel;
+  c->packed_T = k.T;
+  c->packed_sig = sig;
+}
+
 // In-place all-reduce of `count` doubles on the device over the ranks of the attached exchange: ncclAllReduce on the
 // context's stream, or -- rehearsal transport (kmvp_comm_init_host) -- device -> host, the caller's callback (e.g. gloo),
 // host -> device: same buffer, same place in the stream, only the wire differs.
@@ -289,16 +327,7 @@ int finish_product(kmvp_ctx* c, int64_t count, int64_t N, int64_t n_pad, int E, 
   hipLaunchKernelGGL(finish_kernel, dim3(blocks_for(std::max<int64_t>(N, 1))), dim3(256), 0, c->stream,
                      sums, (double*)c->out.p, N, n_pad, E, sig == SIG_NORM ? 1 : 0, kshift);
   HIP_TRY(c, hipGetLastError());
-  c->out_n = N;
-  c->out_e = E;
-  if (c->async_product) return KMVP_OK;  // the caller keeps working on the stream
-  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipEventElapsedTime(&c->last_kernel_ms, c->ev[0], c->ev[1]));
-  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
-  c->last_allreduce_ms = 0.f;
-  if (c->exchanges()) HIP_TRY(c, hipEventElapsedTime(&c->last_allreduce_ms, c->ev[3], c->ev[4]));
-  return KMVP_OK;
+  return complete(c, N, E);
 }
 
 
@@ -339,15 +368,7 @@ int reduce_and_finish(kmvp_ctx* c, int segments, int NE, int64_t N, int64_t n_pa
   hipLaunchKernelGGL(reduce_finish_kernel, dim3(blocks_for(std::max<int64_t>(N, 1) * (split ? SEG_SPLIT : 1))), dim3(256), 0, c->stream,
                      (const double*)c->part.p, (double*)c->out.p, N, n_pad, E, NE, segments, sig == SIG_NORM ? 1 : 0, split);
   HIP_TRY(c, hipGetLastError());
-  c->out_n = N;
-  c->out_e = E;
-  if (c->async_product) return KMVP_OK;  // the caller keeps working on the stream
-  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipEventElapsedTime(&c->last_kernel_ms, c->ev[0], c->ev[1]));
-  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
-  c->last_allreduce_ms = 0.f;
-  return KMVP_OK;
+  return complete(c, N, E);
 }
 
 // Number of source segments of a launch (specialised kernels).  Three pulls:
@@ -390,6 +411,28 @@ int settle_segments(int64_t units, int seg) {
   return (int)settled(seg);
 }
 
+// Geometry of the specialised difference-form kernels (kmvp_lowd.hpp): tiles of 64 T targets per wave, source records of
+// R reals in batches, segments of whole batches, `cols` columns of partial sums per segment.  Everything but the buffers.
+constexpr int64_t LOWD_BATCH = 8;  // two ping-pong batches of 4 records
+template <typename real>
+LowdArgs<real> lowd_geometry(const kmvp_ctx* c, int T, int R, int cols) {
+  const int64_t tile = 64 * (int64_t)T * WAVES_PER_BLOCK;
+  LowdArgs<real> a;
+  a.n = c->N;
+  a.n_pad = round_up(std::max<int64_t>(c->N, 1), tile);
+  a.tile_blocks = (int)(a.n_pad / tile);
+  a.m_pad = round_up(std::max<int64_t>(c->M, 1), LOWD_BATCH);
+  // few targets: short segments, so that the launch still covers the chip (n = 2000, fp64: 121 -> 9 us)
+  const bool small = c->N < SMALL_PROBLEM_TARGETS;
+  const int segments = choose_segments(c, a.n_pad / tile, a.m_pad, cols, a.n_pad, (int64_t)R * sizeof(real), small ? 32 : 1024, small);
+  a.seg_len = round_up((a.m_pad + segments - 1) / segments, LOWD_BATCH);
+  a.segments = (int)((a.m_pad + a.seg_len - 1) / a.seg_len);
+  a.chunk = (int)round_up(std::max(c->opt_chunk, 8), LOWD_BATCH);
+  a.j_offset = c->j_offset;
+  a.m_total = c->m_total;
+  return a;
+}
+
 // The whole product: everything query() times.  `sig` as in kmvp_lowd.hpp.
 template <typename real>
 int run_product_t(kmvp_ctx* c, int kernel, int sig) {
@@ -404,7 +447,6 @@ int run_product_t(kmvp_ctx* c, int kernel, int sig) {
 
   int64_t n_pad;
   int segments;
-  int64_t seg_len;
   HIP_TRY(c, mark(c, 0));
   if (specialised) {
     LowdTuning tune;
@@ -420,59 +462,34 @@ int run_product_t(kmvp_ctx* c, int kernel, int sig) {
         tune.feed = DEFAULT_FEED;
       }
     }
-    const int T = tune.targets_per_lane;
     const int EB = sig == SIG_DENSITY ? 0 : E;
     const int R = (D + EB + 3) / 4 * 4;
-    const int64_t tile = 64 * (int64_t)T * WAVES_PER_BLOCK;
-    n_pad = round_up(std::max<int64_t>(N, 1), tile);
-    const int64_t tile_blocks = n_pad / tile;
-    const int64_t batch = 8;  // two ping-pong batches of 4 records
-    const int64_t m_pad = round_up(std::max<int64_t>(M, 1), batch);
-    // few targets: short segments, so that the launch still covers the chip (n = 2000, fp64: 121 -> 9 us)
-    const bool small = N < SMALL_PROBLEM_TARGETS;
-    segments = choose_segments(c, tile_blocks, m_pad, NE, n_pad, (int64_t)R * sizeof(real), small ? 32 : 1024, small);
-    seg_len = round_up((m_pad + segments - 1) / segments, batch);
-    segments = (int)((m_pad + seg_len - 1) / seg_len);
+    LowdArgs<real> a = lowd_geometry<real>(c, tune.targets_per_lane, R, NE);
+    n_pad = a.n_pad;
+    segments = a.segments;
 
     // (re)pack the kernel layouts when the points, the signal, the kernel or T changed
-    const bool pts_stale = c->packed_points_ver != c->points_ver || c->packed_kernel != kernel ||
-                           c->packed_layout != LAYOUT_LOWD || c->packed_T != T;
-    const bool sig_stale = pts_stale || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
-    if (pts_stale) {
+    const PackKey key = {LAYOUT_LOWD, kernel, tune.targets_per_lane};
+    if (points_stale(c, key)) {
       if ((rc = ensure(c, c->xs, (size_t)D * n_pad * sizeof(real)))) return rc;
       hipLaunchKernelGGL((pack_targets_kernel<real>), dim3(blocks_for(n_pad)), dim3(256), 0,
                          c->stream, x_raw, (real*)c->xs.p, N, n_pad, D, scale);
     }
-    if (sig_stale) {
+    if (signal_stale(c, key, sig)) {
       // one spare batch behind the last record keeps the prefetch in bounds
-      if ((rc = ensure(c, c->rec, (size_t)(m_pad + batch) * R * sizeof(real)))) return rc;
-      hipLaunchKernelGGL((pack_sources_kernel<real>), dim3(blocks_for(m_pad + batch)), dim3(256), 0,
+      if ((rc = ensure(c, c->rec, (size_t)(a.m_pad + LOWD_BATCH) * R * sizeof(real)))) return rc;
+      hipLaunchKernelGGL((pack_sources_kernel<real>), dim3(blocks_for(a.m_pad + LOWD_BATCH)), dim3(256), 0,
                          c->stream, (const real*)c->y_raw.p, (const real*)c->b_raw.p,
-                         (real*)c->rec.p, M, m_pad + batch, D, EB, R, scale);
+                         (real*)c->rec.p, M, a.m_pad + LOWD_BATCH, D, EB, R, scale);
     }
     HIP_TRY(c, hipGetLastError());
-    c->packed_points_ver = c->points_ver;
-    c->packed_signal_ver = c->signal_ver;
-    c->packed_kernel = kernel;
-    c->packed_sig = sig;
-    c->packed_layout = LAYOUT_LOWD;
-    c->packed_T = T;
+    record_packed(c, key, sig);
 
     if ((rc = ensure(c, c->part, (size_t)segments * NE * n_pad * sizeof(double)))) return rc;
-    LowdArgs<real> a;
     a.xs = (const real*)c->xs.p;
     a.rec = (const real*)c->rec.p;
     a.part = (double*)c->part.p;
-    a.n = N;
-    a.n_pad = n_pad;
-    a.m_pad = m_pad;
-    a.seg_len = seg_len;
-    a.segments = segments;
-    a.tile_blocks = (int)tile_blocks;
-    a.chunk = (int)round_up(std::max(c->opt_chunk, 8), batch);
-    a.j_offset = c->j_offset;
-    a.m_total = c->m_total;
-    const int64_t nblocks = tile_blocks * segments;
+    const int64_t nblocks = (int64_t)a.tile_blocks * segments;
     if (nblocks > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
     HIP_TRY(c, mark(c, 0));
     hipError_t le = launch_lowd<real>(kernel, D, E, sig, tune, a, dim3((unsigned)nblocks), c->stream,
@@ -501,7 +518,7 @@ int run_product_t(kmvp_ctx* c, int kernel, int sig) {
     }
     const int64_t tile_blocks = n_pad / BLOCK_THREADS;
     segments = choose_segments(c, tile_blocks, M, NE, n_pad, (int64_t)D * sizeof(real), 256);
-    seg_len = (M + segments - 1) / segments;
+    const int64_t seg_len = (M + segments - 1) / segments;
     segments = (int)((M + seg_len - 1) / seg_len);
     if ((rc = ensure(c, c->part, (size_t)segments * NE * n_pad * sizeof(double)))) return rc;
     const real* xg = (const real*)(c->same_points ? c->y_scaled.p : c->x_scaled.p);
@@ -541,37 +558,27 @@ int run_product_blocked(kmvp_ctx* c, int kernel, int sig) {
   LowdTuning tune;
   tune.feed = DEFAULT_FEED;
   tune.targets_per_lane = DEFAULT_TARGETS_PER_LANE;
-  const int T = tune.targets_per_lane;
   const int R = (D + LOWD_MAX_E + 3) / 4 * 4;
-  const int64_t tile = 64 * (int64_t)T * WAVES_PER_BLOCK;
-  const int64_t n_pad = round_up(std::max<int64_t>(N, 1), tile);
-  const int64_t tile_blocks = n_pad / tile;
-  const int64_t batch = 8;
-  const int64_t m_pad = round_up(std::max<int64_t>(M, 1), batch);
-  const bool small = N < SMALL_PROBLEM_TARGETS;
-  int segments = choose_segments(c, tile_blocks, m_pad, LOWD_MAX_E + 1, n_pad, (int64_t)R * sizeof(real),
-                                 small ? 32 : 1024, small);
-  const int64_t seg_len = round_up((m_pad + segments - 1) / segments, batch);
-  segments = (int)((m_pad + seg_len - 1) / seg_len);
+  LowdArgs<real> a = lowd_geometry<real>(c, tune.targets_per_lane, R, LOWD_MAX_E + 1);
+  const int64_t n_pad = a.n_pad, m_pad = a.m_pad;
+  const int segments = a.segments;
 
   HIP_TRY(c, mark(c, 0));
-  const bool pts_stale = c->packed_points_ver != c->points_ver || c->packed_kernel != kernel ||
-                         c->packed_layout != LAYOUT_LOWD || c->packed_T != T;
-  if (pts_stale) {
+  const PackKey key = {LAYOUT_LOWD, kernel, tune.targets_per_lane};
+  if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)D * n_pad * sizeof(real)))) return rc;
     hipLaunchKernelGGL((pack_targets_kernel<real>), dim3(blocks_for(n_pad)), dim3(256), 0, c->stream, x_raw,
                        (real*)c->xs.p, N, n_pad, D, (real)1);
   }
-  c->packed_points_ver = c->points_ver;
-  c->packed_kernel = kernel;
-  c->packed_layout = LAYOUT_LOWD;
-  c->packed_T = T;
-  c->packed_sig = -1;  // the source records below hold one column block: never reusable as they are
-  if ((rc = ensure(c, c->rec, (size_t)(m_pad + batch) * R * sizeof(real)))) return rc;
+  record_packed(c, key, -1);  // the source records below hold one column block: never reusable as they are
+  if ((rc = ensure(c, c->rec, (size_t)(m_pad + LOWD_BATCH) * R * sizeof(real)))) return rc;
   if ((rc = ensure(c, c->part, (size_t)segments * (LOWD_MAX_E + 1) * n_pad * sizeof(double)))) return rc;
   if ((rc = ensure(c, c->sums, (size_t)NE * n_pad * sizeof(double)))) return rc;
+  a.xs = (const real*)c->xs.p;
+  a.rec = (const real*)c->rec.p;
+  a.part = (double*)c->part.p;
 
-  const int64_t nblocks = tile_blocks * segments;
+  const int64_t nblocks = (int64_t)a.tile_blocks * segments;
   if (nblocks > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
   HIP_TRY(c, mark(c, 0));
   for (int e0 = 0; e0 < E; e0 += LOWD_MAX_E) {
@@ -579,22 +586,9 @@ int run_product_blocked(kmvp_ctx* c, int kernel, int sig) {
     const int sigk = (sig == SIG_NORM && e0 == 0) ? SIG_NORM : SIG_PRODUCT;
     const int NEk = sigk == SIG_NORM ? Ek + 1 : Ek;
     const int Rk = (D + Ek + 3) / 4 * 4;
-    hipLaunchKernelGGL((pack_sources_kernel<real>), dim3(blocks_for(m_pad + batch)), dim3(256), 0, c->stream,
-                       (const real*)c->y_raw.p, (const real*)c->b_raw.p, (real*)c->rec.p, M, m_pad + batch, D, Ek,
+    hipLaunchKernelGGL((pack_sources_kernel<real>), dim3(blocks_for(m_pad + LOWD_BATCH)), dim3(256), 0, c->stream,
+                       (const real*)c->y_raw.p, (const real*)c->b_raw.p, (real*)c->rec.p, M, m_pad + LOWD_BATCH, D, Ek,
                        Rk, (real)1, E, e0);
-    LowdArgs<real> a;
-    a.xs = (const real*)c->xs.p;
-    a.rec = (const real*)c->rec.p;
-    a.part = (double*)c->part.p;
-    a.n = N;
-    a.n_pad = n_pad;
-    a.m_pad = m_pad;
-    a.seg_len = seg_len;
-    a.segments = segments;
-    a.tile_blocks = (int)tile_blocks;
-    a.chunk = (int)round_up(std::max(c->opt_chunk, 8), batch);
-    a.j_offset = c->j_offset;
-    a.m_total = c->m_total;
     hipError_t le = launch_lowd<real>(kernel, D, Ek, sigk, tune, a, dim3((unsigned)nblocks), c->stream,
                                       &c->last_kernel_name);
     if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "no kernel instantiated for this column block");
@@ -636,29 +630,22 @@ int run_product_fast(kmvp_ctx* c, int kernel, int sig) {
   segments = settle_segments(m_stages, segments);
   const int64_t seg_stages = (m_stages + segments - 1) / segments;
 
-  const bool pts_stale = c->packed_points_ver != c->points_ver || c->packed_kernel != kernel ||
-                         c->packed_layout != LAYOUT_FAST || c->packed_T != TT;
-  const bool sig_stale = pts_stale || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
+  const PackKey key = {LAYOUT_FAST, kernel, TT};
   float* centre = (float*)c->aux.p;  // written by kmvp_set_points
-  if (pts_stale) {
+  if (points_stale(c, key)) {
     const int RD = fast_target_row(D);
     if ((rc = ensure(c, c->xs, (size_t)n_pad * RD * sizeof(float)))) return rc;
     hipLaunchKernelGGL(pack_fast_targets_kernel, dim3(blocks_for(n_pad)), dim3(256), 0, c->stream, x_raw,
                        centre, (float*)c->xs.p, N, n_pad, D, RD, scale);
   }
-  if (sig_stale) {
+  if (signal_stale(c, key, sig)) {
     if ((rc = ensure(c, c->rec, (size_t)m_stages * SB))) return rc;
     hipLaunchKernelGGL(pack_fast_sources_kernel, dim3(blocks_for(m_stages * ST * FAST_TILE)),
                        dim3(256), 0, c->stream, (const float*)c->y_raw.p, (const float*)c->b_raw.p, centre,
                        (unsigned char*)c->rec.p, M, m_stages, D, EB, KS, scale);
   }
   HIP_TRY(c, hipGetLastError());
-  c->packed_points_ver = c->points_ver;
-  c->packed_signal_ver = c->signal_ver;
-  c->packed_kernel = kernel;
-  c->packed_sig = sig;
-  c->packed_layout = LAYOUT_FAST;
-  c->packed_T = TT;
+  record_packed(c, key, sig);
 
   if ((rc = ensure(c, c->part, (size_t)segments * NE * n_pad * sizeof(double)))) return rc;
   FastArgs a;
@@ -717,7 +704,6 @@ int run_product_fastmm(kmvp_ctx* c, int kernel, int sig, bool dot = false) {
   // the fixed shift 2^15 assumes every target has a source at distance ~0, i.e. targets == sources (also when the
   // sources are sharded: the all-reduced row then contains the self term); otherwise the per-target running shift
   const int online = (dot || !(c->same_points || c->opt_same_global)) ? 1 : 0;
-  const int layout_kernel = dot ? K_EXPDOT : kernel;
   int rc;
 
   // (the kernel's time does not depend on the segment count between 8 and 48 at 1e5 points, the fp64 partial sums --
@@ -727,16 +713,15 @@ int run_product_fastmm(kmvp_ctx* c, int kernel, int sig, bool dot = false) {
   const int64_t seg_stages = (m_stages + segments - 1) / segments;
   if (tile_blocks * segments > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
 
-  const int layout_T = TT + 16 * MODE;
-  const bool pts_stale = c->packed_points_ver != c->points_ver || c->packed_kernel != layout_kernel ||
-                         c->packed_layout != LAYOUT_FASTMM || c->packed_T != layout_T;
+  const PackKey key = {LAYOUT_FASTMM, dot ? K_EXPDOT : kernel, TT + 16 * MODE};
   const bool one_block = NE <= FMM_MAX_COLS;
-  const bool sig_stale = pts_stale || !one_block || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
+  const int image_sig = one_block ? sig : -1;  // several column blocks: the signal image holds the last one
+  const bool sig_stale = signal_stale(c, key, image_sig);
   float* centre = (float*)c->aux.p;  // written by kmvp_set_points
   if ((rc = ensure(c, c->cell_scale, 1024))) return rc;
   float* sigma = (float*)((char*)c->cell_scale.p + 256);
   double* unscale = (double*)((char*)c->cell_scale.p + 512);
-  if (pts_stale) {
+  if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)n_pad * KS * 32))) return rc;
     if ((rc = ensure(c, c->rec, (size_t)m_stages * SB))) return rc;
     hipLaunchKernelGGL(pack_fastmm_targets_kernel, dim3(blocks_for(n_pad * KS * 2)), dim3(256), 0, c->stream, x_raw,
@@ -747,12 +732,7 @@ int run_product_fastmm(kmvp_ctx* c, int kernel, int sig, bool dot = false) {
                        scale, dot ? 1 : 0);
     HIP_TRY(c, hipGetLastError());
   }
-  c->packed_points_ver = c->points_ver;
-  c->packed_kernel = layout_kernel;
-  c->packed_layout = LAYOUT_FASTMM;
-  c->packed_T = layout_T;
-  c->packed_signal_ver = c->signal_ver;
-  c->packed_sig = one_block ? sig : -1;
+  record_packed(c, key, image_sig);
 
   if ((rc = ensure(c, c->part, (size_t)segments * nb_max * n_pad * sizeof(double)))) return rc;
   if ((!one_block || dot) && (rc = ensure(c, c->sums, (size_t)NE * n_pad * sizeof(double)))) return rc;
@@ -874,27 +854,20 @@ int run_product_cfast(kmvp_ctx* c, int kernel, int sig) {
   const int64_t seg_stages = (m_stages + segments - 1) / segments;
 
   if ((rc = morton_order(c, m_alloc))) return rc;
-  const bool pts_stale = c->packed_points_ver != c->points_ver || c->packed_kernel != kernel ||
-                         c->packed_layout != LAYOUT_CFAST || c->packed_T != TT;
-  const bool sig_stale = pts_stale || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
-  if (pts_stale) {
+  const PackKey key = {LAYOUT_CFAST, kernel, TT};
+  if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)n_pad * 4 * sizeof(float)))) return rc;
     hipLaunchKernelGGL(pack_cfast_targets_kernel, dim3(blocks_for(n_pad)), dim3(256), 0, c->stream, x_raw,
                        (float*)c->xs.p, N, n_pad, D);
   }
-  if (sig_stale) {
+  if (signal_stale(c, key, sig)) {
     if ((rc = ensure(c, c->rec, (size_t)m_stages * CF_STAGE_BYTES))) return rc;
     hipLaunchKernelGGL(pack_cfast_sources_kernel, dim3((unsigned)(m_alloc / CF_GROUP)), dim3(CF_GROUP), 0,
                        c->stream, (const float*)c->y_raw.p, (const float*)c->b_raw.p, (const int*)c->perm.p,
                        (unsigned char*)c->rec.p, M, D, EB, scale, c->j_offset);
   }
   HIP_TRY(c, hipGetLastError());
-  c->packed_points_ver = c->points_ver;
-  c->packed_signal_ver = c->signal_ver;
-  c->packed_kernel = kernel;
-  c->packed_sig = sig;
-  c->packed_layout = LAYOUT_CFAST;
-  c->packed_T = TT;
+  record_packed(c, key, sig);
 
   if ((rc = ensure(c, c->part, (size_t)segments * NE * n_pad * sizeof(double)))) return rc;
   CfastArgs a;
@@ -956,15 +929,14 @@ int run_product_cfastmm(kmvp_ctx* c, int kernel, int sig) {
   if (tile_blocks * segments > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
 
   if ((rc = morton_order(c, m_alloc))) return rc;
-  const int layout_T = TT + 16 * MODE;
-  const bool pts_stale = c->packed_points_ver != c->points_ver || c->packed_kernel != kernel ||
-                         c->packed_layout != LAYOUT_CFASTMM || c->packed_T != layout_T;
+  const PackKey key = {LAYOUT_CFASTMM, kernel, TT + 16 * MODE};
   const bool one_block = NE <= FMM_MAX_COLS;
-  const bool sig_stale = pts_stale || !one_block || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
+  const int image_sig = one_block ? sig : -1;  // as in run_product_fastmm
+  const bool sig_stale = signal_stale(c, key, image_sig);
   if ((rc = ensure(c, c->cell_scale, 1024))) return rc;
   float* sigma = (float*)((char*)c->cell_scale.p + 256);
   double* unscale = (double*)((char*)c->cell_scale.p + 512);
-  if (pts_stale) {
+  if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)n_pad * 4 * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->rec, (size_t)m_stages * SB))) return rc;
     hipLaunchKernelGGL(pack_cfast_targets_kernel, dim3(blocks_for(n_pad)), dim3(256), 0, c->stream, x_raw,
@@ -973,12 +945,7 @@ int run_product_cfastmm(kmvp_ctx* c, int kernel, int sig) {
                        (const float*)c->y_raw.p, (const int*)c->perm.p, (unsigned char*)c->rec.p, M, D, MODE, scale, c->j_offset);
     HIP_TRY(c, hipGetLastError());
   }
-  c->packed_points_ver = c->points_ver;
-  c->packed_kernel = kernel;
-  c->packed_layout = LAYOUT_CFASTMM;
-  c->packed_T = layout_T;
-  c->packed_signal_ver = c->signal_ver;
-  c->packed_sig = one_block ? sig : -1;
+  record_packed(c, key, image_sig);
 
   if ((rc = ensure(c, c->part, (size_t)segments * nb_max * n_pad * sizeof(double)))) return rc;
   if (!one_block && (rc = ensure(c, c->sums, (size_t)NE * n_pad * sizeof(double)))) return rc;
@@ -1283,40 +1250,72 @@ double cell_padding(const kmvp_ctx* c) {  // (empty tiles included)
   return std::max(t, s);
 }
 
+// The two launches of the float32 cell kernels over the target lists of cell_tiles_split(): r = 0 the MAIN list (groups
+// of cell_tt tiles per wavefront), r = 1 the REST list (the cells' leftover tiles, two per wavefront -- few workgroups,
+// latency-bound each, so its own, finer split of the sources).  Each launch has its own segments and its own region
+// [segment][cols][slots] of the partial sums in c->part.
+struct CellSplit {
+  int64_t m_stages, n_slots;  // source stages; target slots of both lists
+  int64_t blocks[2], slots[2], seg_stages[2];
+  int segments[2];
+  int tt(const kmvp_ctx* c, int r) const { return r ? 2 : c->cell_tt; }
+  dim3 grid(int r) const { return dim3((unsigned)(blocks[r] * segments[r])); }
+  size_t part_doubles(int cols) const { return ((size_t)segments[0] * slots[0] + (size_t)segments[1] * slots[1]) * cols; }
+  double* region(const kmvp_ctx* c, int cols, int r) const { return (double*)c->part.p + (r ? (size_t)segments[0] * cols * slots[0] : 0); }
+  template <class Args>
+  void args(const kmvp_ctx* c, int cols, int r, Args& a) const {
+    a.part = region(c, cols, r);
+    a.n_slots = slots[r];
+    a.tile_base = r ? c->cell_n_main : 0;
+    a.seg_stages = seg_stages[r];
+    a.segments = segments[r];
+    a.tile_blocks = (int)blocks[r];
+  }
+};
+
+// Per path: the stage of its source image, and for the main launch the shortest segment on big problems, the L2 budget
+// of a segment and the target number of workgroups (choose_segments)
+CellSplit cell_split(const kmvp_ctx* c, int cols, int stage_tiles, int64_t stage_bytes, int min_seg, int64_t l2_seg_bytes,
+                     int64_t target_blocks) {
+  const bool small = c->N < SMALL_PROBLEM_TARGETS;
+  CellSplit s;
+  s.m_stages = (c->cell_m_tiles + stage_tiles - 1) / stage_tiles;
+  s.n_slots = c->cell_n_tiles * CELL_TILE;
+  s.blocks[0] = c->cell_n_main / (c->cell_tt * WAVES_PER_BLOCK);
+  s.blocks[1] = c->cell_n_rest / (2 * WAVES_PER_BLOCK);
+  s.slots[0] = c->cell_n_main * CELL_TILE;
+  s.slots[1] = c->cell_n_rest * CELL_TILE;
+  s.segments[0] = settle_segments(s.m_stages, choose_segments(c, std::max<int64_t>(1, s.blocks[0]), s.m_stages, cols, s.n_slots,
+                                                              stage_bytes, small ? 1 : min_seg, small, l2_seg_bytes, target_blocks));
+  s.seg_stages[0] = (s.m_stages + s.segments[0] - 1) / s.segments[0];
+  s.segments[1] = 0;
+  s.seg_stages[1] = 1;
+  if (s.blocks[1] > 0) {
+    const int seg = choose_segments(c, s.blocks[1], s.m_stages, cols, s.n_slots, stage_bytes, 1, small, l2_seg_bytes, 1536);
+    s.seg_stages[1] = (s.m_stages + seg - 1) / seg;
+    s.segments[1] = (int)((s.m_stages + s.seg_stages[1] - 1) / s.seg_stages[1]);
+  }
+  return s;
+}
+
 int run_product_cell(kmvp_ctx* c, int sig) {
   const int D = c->D;
   const int E = 1;
   const int NE = sig == SIG_NORM ? 2 : 1;
   const int64_t N = c->N;
-  const bool small = N < SMALL_PROBLEM_TARGETS;
-  const int TT = c->cell_tt;  // the target tile lists were built for it (cell_prepare)
-  const int64_t n_tiles = c->cell_n_tiles;  // whole groups of TT, then leftover tiles in groups of 2 (cell_tiles_split)
-  const int64_t n_slots = n_tiles * CELL_TILE;
-  const int64_t tile_blocks = c->cell_n_main / (TT * WAVES_PER_BLOCK);
-  const int64_t rest_blocks = c->cell_n_rest / (2 * WAVES_PER_BLOCK);
-  const int64_t m_stages = (c->cell_m_tiles + CELL_STAGE_TILES - 1) / CELL_STAGE_TILES;
+  const int64_t n_tiles = c->cell_n_tiles;  // whole groups of cell_tt, then leftover tiles in groups of 2 (cell_tiles_split)
+  const CellSplit s = cell_split(c, NE, CELL_STAGE_TILES, CELL_STAGE_BYTES, 4, 2 << 20, 16384);
+  const int64_t m_stages = s.m_stages, n_slots = s.n_slots;
   int rc;
   CellGrid grid;
   cell_load_grid(c, grid);
 
-  int segments = choose_segments(c, std::max<int64_t>(1, tile_blocks), m_stages, NE, n_slots, CELL_STAGE_BYTES,
-                                 small ? 1 : 4, small);
-  segments = settle_segments(m_stages, segments);
-  const int64_t seg_stages = (m_stages + segments - 1) / segments;
-  // the launch over the leftover tiles: its own, finer split of the sources and its own region of partial sums
-  int rest_segments = rest_blocks > 0 ? choose_segments(c, rest_blocks, m_stages, NE, n_slots, CELL_STAGE_BYTES, 1, small, 2 << 20, 1536) : 0;
-  const int64_t rest_seg_stages = rest_blocks > 0 ? (m_stages + rest_segments - 1) / rest_segments : 1;
-  if (rest_blocks > 0) rest_segments = (int)((m_stages + rest_seg_stages - 1) / rest_seg_stages);
-  const int64_t main_slots = c->cell_n_main * CELL_TILE, rest_slots = c->cell_n_rest * CELL_TILE;
-
-  const bool pts_stale = c->packed_points_ver != c->points_ver || c->packed_kernel != K_GAUSSIAN ||
-                         c->packed_layout != LAYOUT_CELL || c->packed_T != TT;
-  const bool sig_stale = pts_stale || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
+  const PackKey key = {LAYOUT_CELL, K_GAUSSIAN, c->cell_tt};
   const float* x_raw = (const float*)(c->same_points ? c->y_raw.p : c->x_raw.p);
   const int* tperm = (const int*)(c->same_points ? c->cell_sperm.p : c->cell_tperm.p);
   const int* tgrp = (const int*)c->cell_tgrp.p;
   const int* sgrp = (const int*)c->cell_sgrp.p;
-  if (pts_stale) {
+  if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)n_slots * 4 * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->cell_tmeta, (size_t)n_tiles * 4 * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->cell_slot, (size_t)N * sizeof(int)))) return rc;
@@ -1324,7 +1323,7 @@ int run_product_cell(kmvp_ctx* c, int sig) {
                        tgrp, tgrp + c->cell_n_tiles, (const unsigned*)(tgrp + 2 * c->cell_n_tiles), c->cell_n_tiles, D,
                        grid, (float*)c->xs.p, (float*)c->cell_tmeta.p, (int*)c->cell_slot.p);
   }
-  if (sig_stale) {
+  if (signal_stale(c, key, sig)) {
     if ((rc = ensure(c, c->rec, (size_t)m_stages * CELL_STAGE_BYTES))) return rc;
     hipLaunchKernelGGL(pack_cell_sources_kernel, dim3((unsigned)(m_stages * CELL_STAGE_TILES)), dim3(CELL_TILE), 0,
                        c->stream, (const float*)c->y_raw.p,
@@ -1334,16 +1333,9 @@ int run_product_cell(kmvp_ctx* c, int sig) {
                        (unsigned char*)c->rec.p);
   }
   HIP_TRY(c, hipGetLastError());
-  c->packed_points_ver = c->points_ver;
-  c->packed_signal_ver = c->signal_ver;
-  c->packed_kernel = K_GAUSSIAN;
-  c->packed_sig = sig;
-  c->packed_layout = LAYOUT_CELL;
-  c->packed_T = TT;
+  record_packed(c, key, sig);
 
-  if ((rc = ensure(c, c->part, ((size_t)segments * main_slots + (size_t)rest_segments * rest_slots) * NE * sizeof(double)))) return rc;
-  double* part_main = (double*)c->part.p;
-  double* part_rest = part_main + (size_t)segments * NE * main_slots;
+  if ((rc = ensure(c, c->part, s.part_doubles(NE) * sizeof(double)))) return rc;
   CellArgs a;
   a.xd = (const float*)c->xs.p;
   a.tmeta = (const float*)c->cell_tmeta.p;
@@ -1352,24 +1344,11 @@ int run_product_cell(kmvp_ctx* c, int sig) {
   a.chunk_stages = std::max(1, c->opt_chunk / (CELL_TILE * CELL_STAGE_TILES));
   HIP_TRY(c, mark(c, 0));
   hipError_t le = hipSuccess;
-  if (tile_blocks > 0) {
-    a.part = part_main;
-    a.n_slots = main_slots;
-    a.tile_base = 0;
-    a.seg_stages = seg_stages;
-    a.segments = segments;
-    a.tile_blocks = (int)tile_blocks;
-    le = launch_cell_gaussian(sig, TT, a, dim3((unsigned)(tile_blocks * segments)), c->stream, &c->last_kernel_name);
-  }
-  if (le == hipSuccess && rest_blocks > 0) {  // the cells' leftover tiles, two per wavefront
-    a.part = part_rest;
-    a.n_slots = rest_slots;
-    a.tile_base = c->cell_n_main;
-    a.seg_stages = rest_seg_stages;
-    a.segments = rest_segments;
-    a.tile_blocks = (int)rest_blocks;
-    le = launch_cell_gaussian(sig, 2, a, dim3((unsigned)(rest_blocks * rest_segments)), c->stream, &c->last_kernel_name);
-  }
+  for (int r = 0; r < 2 && le == hipSuccess; ++r)
+    if (s.blocks[r] > 0) {
+      s.args(c, NE, r, a);
+      le = launch_cell_gaussian(sig, s.tt(c, r), a, s.grid(r), c->stream, &c->last_kernel_name);
+    }
   if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "fast_tiles must be 1, 2, 4 or 8");
   HIP_TRY(c, le);
   HIP_TRY(c, mark(c, 1));
@@ -1377,12 +1356,11 @@ int run_product_cell(kmvp_ctx* c, int sig) {
   // ---- epilogue: segments -> sums in the caller's order, [all-reduce over the source shards], normalise
   if ((rc = ensure(c, c->sums, (size_t)NE * N * sizeof(double)))) return rc;
   if ((rc = ensure(c, c->cell_sums, (size_t)NE * n_slots * sizeof(double)))) return rc;
-  if (tile_blocks > 0)
-    hipLaunchKernelGGL(reduce_region_kernel, dim3(blocks_for((int64_t)NE * main_slots)), dim3(256), 0, c->stream,
-                       (const double*)part_main, (double*)c->cell_sums.p, main_slots, NE, segments, n_slots, (int64_t)0);
-  if (rest_blocks > 0)
-    hipLaunchKernelGGL(reduce_region_kernel, dim3(blocks_for((int64_t)NE * rest_slots)), dim3(256), 0, c->stream,
-                       (const double*)part_rest, (double*)c->cell_sums.p, rest_slots, NE, rest_segments, n_slots, main_slots);
+  for (int r = 0; r < 2; ++r)
+    if (s.blocks[r] > 0)
+      hipLaunchKernelGGL(reduce_region_kernel, dim3(blocks_for((int64_t)NE * s.slots[r])), dim3(256), 0, c->stream,
+                         (const double*)s.region(c, NE, r), (double*)c->cell_sums.p, s.slots[r], NE, s.segments[r], n_slots,
+                         r ? s.slots[0] : (int64_t)0);
   hipLaunchKernelGGL(gather_cells_kernel, dim3(blocks_for((int64_t)NE * N)), dim3(256), 0, c->stream,
                      (const double*)c->cell_sums.p, (const int*)c->cell_slot.p, (double*)c->sums.p, N, n_slots, NE);
   HIP_TRY(c, hipGetLastError());
@@ -1407,36 +1385,22 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
   const int E = sig == SIG_DENSITY ? 1 : c->E;
   const int NE = sig == SIG_NORM ? E + 1 : E;
   const int64_t N = c->N;
-  const bool small = N < SMALL_PROBLEM_TARGETS;
   const int TT = c->cell_tt;  // the target tile lists were built for it (cell_prepare)
   const int64_t n_tiles = c->cell_n_tiles;  // whole groups of TT, then leftover tiles in groups of 2 (cell_tiles_split)
-  const int64_t n_slots = n_tiles * CELL_TILE;
-  const int64_t tile_blocks = c->cell_n_main / (TT * WAVES_PER_BLOCK);
-  const int64_t rest_blocks = c->cell_n_rest / (2 * WAVES_PER_BLOCK);
-  const int64_t m_stages = (c->cell_m_tiles + CMM_STAGE_TILES - 1) / CMM_STAGE_TILES;
-  int rc;
-  CellGrid grid;
-  cell_load_grid(c, grid);
-
   // segments of <= 3 MiB of source image (one per XCD at a time in its 4 MiB L2) and ~14 rounds of resident
   // workgroups: 8 at the headline shape.  tools/cellmm_segments.py: 8 ... 32 segments run alike (28.3-28.5 ms),
   // 4 is slower (29.0); every segment costs n_slots x 8 bytes of partial sums written and read back and one more
   // pass over the targets, so the fewest that keep the chip full are taken (HBM-side traffic 0.44 -> 0.25 GB).
-  int segments = choose_segments(c, std::max<int64_t>(1, tile_blocks), m_stages, 1, n_slots, CMM_STAGE_BYTES,
-                                 small ? 1 : 2, small, 3 << 20, 7168);
-  segments = settle_segments(m_stages, segments);
-  const int64_t seg_stages = (m_stages + segments - 1) / segments;
-  // the launch over the leftover tiles (two per wavefront, few workgroups) gets its own, finer split of the sources --
-  // it is latency-bound per workgroup, so it needs many of them -- and its own region of partial sums
-  int rest_segments = rest_blocks > 0 ? choose_segments(c, rest_blocks, m_stages, 1, n_slots, CMM_STAGE_BYTES, 1, small, 3 << 20, 1536) : 0;
-  const int64_t rest_seg_stages = rest_blocks > 0 ? (m_stages + rest_segments - 1) / rest_segments : 1;
-  if (rest_blocks > 0) rest_segments = (int)((m_stages + rest_seg_stages - 1) / rest_seg_stages);
-  const int64_t main_slots = c->cell_n_main * CELL_TILE, rest_slots = c->cell_n_rest * CELL_TILE;
+  const CellSplit s = cell_split(c, 1, CMM_STAGE_TILES, CMM_STAGE_BYTES, 2, 3 << 20, 7168);
+  const int64_t m_stages = s.m_stages, n_slots = s.n_slots;
+  int rc;
+  CellGrid grid;
+  cell_load_grid(c, grid);
 
-  const bool pts_stale = c->packed_points_ver != c->points_ver || c->packed_kernel != K_GAUSSIAN ||
-                         c->packed_layout != LAYOUT_CELLMM || c->packed_T != TT;
+  const PackKey key = {LAYOUT_CELLMM, K_GAUSSIAN, TT};
   // the image holds ONE column's signal: it can be reused only by single-column products
-  const bool sig_stale = pts_stale || NE > 1 || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
+  const int image_sig = NE > 1 ? -1 : sig;
+  const bool sig_stale = signal_stale(c, key, image_sig);
   const float* x_raw = (const float*)(c->same_points ? c->y_raw.p : c->x_raw.p);
   const int* tperm = (const int*)(c->same_points ? c->cell_sperm.p : c->cell_tperm.p);
   const int* tgrp = (const int*)c->cell_tgrp.p;
@@ -1445,7 +1409,7 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
   float* scale = (float*)c->cell_scale.p;
   unsigned* bmax = (unsigned*)c->cell_scale.p + 4;
   HIP_TRY(c, mark(c, 0));
-  if (pts_stale) {
+  if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)n_slots * 4 * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->cell_tmeta, (size_t)n_tiles * 4 * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->cell_slot, (size_t)N * sizeof(int)))) return rc;
@@ -1458,18 +1422,11 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
                        (const unsigned*)(sgrp + 2 * c->cell_m_tiles), c->cell_m_tiles, D, grid, (unsigned char*)c->rec.p);
     HIP_TRY(c, hipGetLastError());
   }
-  c->packed_points_ver = c->points_ver;
-  c->packed_signal_ver = c->signal_ver;
-  c->packed_kernel = K_GAUSSIAN;
-  c->packed_sig = NE > 1 ? -1 : sig;
-  c->packed_layout = LAYOUT_CELLMM;
-  c->packed_T = TT;
+  record_packed(c, key, image_sig);
 
-  if ((rc = ensure(c, c->part, ((size_t)segments * main_slots + (size_t)rest_segments * rest_slots) * sizeof(double)))) return rc;
+  if ((rc = ensure(c, c->part, s.part_doubles(1) * sizeof(double)))) return rc;
   if ((rc = ensure(c, c->sums, (size_t)NE * N * sizeof(double)))) return rc;
   if ((rc = ensure(c, c->cell_sums, (size_t)NE * n_slots * sizeof(double)))) return rc;
-  double* part_main = (double*)c->part.p;
-  double* part_rest = part_main + (size_t)segments * main_slots;
   // MFMA shape: 16x16x32 (cellmm16_kernel) sustains more under the power limit, but issues twice the MFMAs per flop:
   // 1e6 points 27.7 -> 26.6 ms, 5e5 equal, 2e5 (smaller cells' tile groups) 1.73 -> 1.96 ms (tools/cellmm_shapes.py).  What
   // counts is how full the TARGET cells are, not the pair count: one of eight ranks' share of config 2 (1e6 targets x 125 000
@@ -1498,35 +1455,20 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
       if (NE == 1) HIP_TRY(c, mark(c, 0));
     }
     hipError_t le = hipSuccess;
-    if (tile_blocks > 0) {
-      a.tile_base = 0;
-      a.tile_blocks = (int)tile_blocks;
-      a.part = part_main;
-      a.n_slots = main_slots;
-      a.seg_stages = seg_stages;
-      a.segments = segments;
-      le = launch_cellmm_gaussian(TT, shape, a, dim3((unsigned)(tile_blocks * segments)), c->stream, &c->last_kernel_name);
-    }
-    if (le == hipSuccess && rest_blocks > 0) {  // the cells' leftover tiles, two per wavefront
-      a.tile_base = c->cell_n_main;
-      a.tile_blocks = (int)rest_blocks;
-      a.part = part_rest;
-      a.n_slots = rest_slots;
-      a.seg_stages = rest_seg_stages;
-      a.segments = rest_segments;
-      le = launch_cellmm_gaussian(2, shape, a, dim3((unsigned)(rest_blocks * rest_segments)), c->stream, &c->last_kernel_name);
-    }
+    for (int r = 0; r < 2 && le == hipSuccess; ++r)
+      if (s.blocks[r] > 0) {
+        s.args(c, 1, r, a);
+        le = launch_cellmm_gaussian(s.tt(c, r), shape, a, s.grid(r), c->stream, &c->last_kernel_name);
+      }
     if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "fast_tiles must be 1, 2, 4 or 8");
     HIP_TRY(c, le);
     if (NE == 1) HIP_TRY(c, mark(c, 1));
     // segments -> this column's sums in cell order (each launch's region with its own number of segments)
     double* col_sums = (double*)c->cell_sums.p + (size_t)col * n_slots;
-    if (tile_blocks > 0)
-      hipLaunchKernelGGL(reduce_segments_kernel, dim3(blocks_for(main_slots)), dim3(256), 0, c->stream,
-                         (const double*)part_main, col_sums, main_slots, segments, 0);
-    if (rest_blocks > 0)
-      hipLaunchKernelGGL(reduce_segments_kernel, dim3(blocks_for(rest_slots)), dim3(256), 0, c->stream,
-                         (const double*)part_rest, col_sums + main_slots, rest_slots, rest_segments, 0);
+    for (int r = 0; r < 2; ++r)
+      if (s.blocks[r] > 0)
+        hipLaunchKernelGGL(reduce_segments_kernel, dim3(blocks_for(s.slots[r])), dim3(256), 0, c->stream,
+                           (const double*)s.region(c, 1, r), col_sums + (r ? s.slots[0] : 0), s.slots[r], s.segments[r], 0);
     HIP_TRY(c, hipGetLastError());
   }
   if (NE > 1) HIP_TRY(c, mark(c, 1));  // several columns: the "kernel" time covers every column's pack + pair loop
@@ -1599,13 +1541,11 @@ int run_product_cell64(kmvp_ctx* c, int sig) {
   const int seg_cells = (int)((n_scells + seg - 1) / seg);
   const int segments = (n_scells + seg_cells - 1) / seg_cells;
 
-  const bool pts_stale = c->packed_points_ver != c->points_ver || c->packed_kernel != K_GAUSSIAN ||
-                         c->packed_layout != LAYOUT_CELL64;
-  const bool sig_stale = pts_stale || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
+  const PackKey key = {LAYOUT_CELL64, K_GAUSSIAN, 1};  // (no tile count: T = 1)
   const double* x_raw = (const double*)(c->same_points ? c->y_raw.p : c->x_raw.p);
   const int* tperm = (const int*)(c->same_points ? c->cell_sperm.p : c->cell_tperm.p);
   const int* tgrp = (const int*)c->cell_tgrp.p;
-  if (pts_stale) {
+  if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)n_slots * 4 * sizeof(double)))) return rc;
     if ((rc = ensure(c, c->cell_tmeta, (size_t)n_tiles * 4 * sizeof(double)))) return rc;
     if ((rc = ensure(c, c->cell_slot, (size_t)N * sizeof(int)))) return rc;
@@ -1613,7 +1553,7 @@ int run_product_cell64(kmvp_ctx* c, int sig) {
                        tgrp, tgrp + c->cell_n_tiles, (const unsigned*)(tgrp + 2 * c->cell_n_tiles), c->cell_n_tiles, D,
                        grid, (double*)c->xs.p, (double*)c->cell_tmeta.p, (int*)c->cell_slot.p);
   }
-  if (sig_stale) {
+  if (signal_stale(c, key, sig)) {
     const int64_t m_alloc = M + 64;  // zero records behind the last cell: the W pass reads whole groups of 64
     if ((rc = ensure(c, c->rec, (size_t)m_alloc * 4 * sizeof(double)))) return rc;
     hipLaunchKernelGGL(pack_cell64_sources_kernel, dim3(blocks_for(m_alloc)), dim3(256), 0, c->stream,
@@ -1621,12 +1561,7 @@ int run_product_cell64(kmvp_ctx* c, int sig) {
                        (const int*)c->cell_sperm.p, (const unsigned*)c->cell_skey.p, M, m_alloc, D, grid, (double*)c->rec.p);
   }
   HIP_TRY(c, hipGetLastError());
-  c->packed_points_ver = c->points_ver;
-  c->packed_signal_ver = c->signal_ver;
-  c->packed_kernel = K_GAUSSIAN;
-  c->packed_sig = sig;
-  c->packed_layout = LAYOUT_CELL64;
-  c->packed_T = 1;
+  record_packed(c, key, sig);
 
   if ((rc = ensure(c, c->part, (size_t)segments * NE * n_slots * sizeof(double)))) return rc;
   Cell64Args a;
@@ -1656,6 +1591,79 @@ int run_product_cell64(kmvp_ctx* c, int sig) {
   return finish_product(c, (int64_t)NE * N, N, N, 1, sig);
 }
 
+// ---- the rules of the dispatch (run_product, prepare_points), each stated once
+
+// The radius rule: the squared half-diagonal of the clouds' bounding box in the kernel's scaled coordinates is within
+// FAST_AUTO_RADIUS2 -- where the expanded forms of the squared distance are as accurate as the difference form
+float scaled_radius2(const kmvp_ctx* c, int kernel) {
+  const float sc = scale_for<float>(kernel);
+  return c->cloud_radius2 * sc * sc;
+}
+bool radius_ok(const kmvp_ctx* c, int kernel) { return scaled_radius2(c, kernel) <= FAST_AUTO_RADIUS2; }
+
+bool big_clouds(const kmvp_ctx* c) { return c->N >= SMALL_PROBLEM_TARGETS && c->M >= SMALL_PROBLEM_TARGETS; }
+
+// Target tiles per wavefront of the float32 cell lists: as requested ("fast_tiles"), else 1 for few targets, else 0
+// (cell_prepare takes the cheapest grouping)
+int cell_tiles_request(const kmvp_ctx* c) {
+  return c->opt_fast_tiles > 0 ? c->opt_fast_tiles : (c->N < SMALL_PROBLEM_TARGETS ? 1 : 0);
+}
+
+// cellmm_kernel's f16 operands have the range: clouds inside the radius rule, weights W_j <= 2^CMM_MAX_WLOG2 on the grid
+bool cellmm_in_range(const kmvp_ctx* c) { return radius_ok(c, K_GAUSSIAN) && cellmm_wlog2(c) <= CMM_MAX_WLOG2; }
+
+// Whether the float32 cell form (Gaussian, D <= 3) is worth building: forced (fast_sqdists >= 3), or in auto for big
+// clouds inside the radius rule.  Several signal columns have cellmm_kernel alone (no cell_kernel to fall back on): they
+// need the radius rule even when forced, and fast_sqdists = 4 (cell_kernel) rules them out.
+bool cells_considered(const kmvp_ctx* c, bool several) {
+  if (several && (c->opt_fast == 4 || !radius_ok(c, K_GAUSSIAN))) return false;
+  return c->opt_fast >= 3 || (c->opt_fast < 0 && radius_ok(c, K_GAUSSIAN) && big_clouds(c));
+}
+
+// ok: the float32 cell form serves this product -- it is considered, the cell lists of the current points apply
+// (cell_prepare) and, unless forced, pad the tiles by at most CELL_AUTO_MAX_PAD; several columns also need cellmm_kernel's
+// operand range.  A refusal leaves its reason in the dispatch note (kmvp_last_dispatch_note): the fastest paths are
+// narrow, and a caller who gets 5e12 instead of 3.7e13 pairs/s should be told which condition failed.
+int cells_usable(kmvp_ctx* c, bool several, bool& ok) {
+  const bool forced = c->opt_fast >= 3;
+  ok = false;
+  if (cells_considered(c, several)) {
+    const int rc = cell_prepare(c, cell_tiles_request(c));
+    if (rc) return rc;
+    ok = c->cell_state == 1 && (forced || cell_padding(c) <= CELL_AUTO_MAX_PAD) && (!several || cellmm_in_range(c));
+    if (ok) return KMVP_OK;
+  }
+  char buf[256];
+  if (c->opt_fast >= 0 && !forced) {
+    snprintf(buf, sizeof buf, "cell form not considered: fast_sqdists = %d was requested", c->opt_fast);
+  } else if (!radius_ok(c, K_GAUSSIAN)) {
+    snprintf(buf, sizeof buf, "cell form not taken: squared half-diagonal of the clouds' bounding box %.3g > %.3g (radius rule)",
+             (double)scaled_radius2(c, K_GAUSSIAN), (double)FAST_AUTO_RADIUS2);
+  } else if (!big_clouds(c)) {
+    snprintf(buf, sizeof buf, "cell form not taken: fewer than %lld points in a cloud (N = %lld, M = %lld)",
+             (long long)SMALL_PROBLEM_TARGETS, (long long)c->N, (long long)c->M);
+  } else if (c->cell_state != 1) {
+    snprintf(buf, sizeof buf, "cell form not taken: the grid does not apply (non-finite box or more than %d cells along an axis)",
+             CELL_MAX_GRID);
+  } else {
+    snprintf(buf, sizeof buf, "cell form not taken: padding the cells' tiles would use %.0f %% of the slots (limit %.0f %%): too few "
+             "points per grid cell", 100.0 * cell_padding(c), 100.0 * CELL_AUTO_MAX_PAD);
+  }
+  c->note = buf;
+  return KMVP_OK;
+}
+
+// Whether the float64 cell form (kmvp_cell64.hpp) is worth building: forced (fast_sqdists = 3), or in auto for big clouds
+bool cells64_considered(const kmvp_ctx* c) { return c->opt_fast == 3 || (c->opt_fast < 0 && big_clouds(c)); }
+
+// Whether the product ends in finish_product_shifted (per-target exponents: all-reduce MIN, then SUM): exp(<x,y>), and the
+// bf16 Gaussian with targets != sources (K_GAUSSIAN_SHIFTED; an explicit "mfma_variant" asks for the plain kernel).  Every
+// rank must agree, one with an empty source slice included.
+bool takes_shifted_tail(const kmvp_ctx* c, int kernel) {
+  return kernel == K_EXPDOT || (c->dtype == KMVP_BF16 && kernel == K_GAUSSIAN && !(c->same_points || c->opt_same_global) &&
+                                c->opt_mfma_variant < 0 && mfma_ksteps_shifted(c->D) <= MFMA_MAX_KS);
+}
+
 // bf16 MFMA path (kmvp_mfma.hpp): host arrays are float32, points and signal are packed
 // to augmented bf16 rows / LDS tile images, sums come back as fp32 partials.
 int run_product_mfma(kmvp_ctx* c, int kernel, int sig) {
@@ -1669,10 +1677,9 @@ int run_product_mfma(kmvp_ctx* c, int kernel, int sig) {
   // lengths from every source would otherwise have its whole row under the float32 range (0, or 0/0 when normalised) -- the
   // bf16 counterpart of what fastmm_kernel / cfastmm_kernel do for float32.  Targets == sources keep the plain kernel (every
   // row contains k = 1); exp(-r) would need r > 87 and stays plain.
-  const bool shifted = kernel == K_GAUSSIAN && !(c->same_points || c->opt_same_global) && c->opt_mfma_variant < 0 &&
-                       mfma_ksteps_shifted(D) <= MFMA_MAX_KS;  // (an explicit "mfma_variant" asks for the plain kernel)
+  const bool dot = takes_shifted_tail(c, kernel);  // (mantissa, exponent) partial sums and the shifted tail
+  const bool shifted = dot && kernel == K_GAUSSIAN;
   if (shifted) kernel = K_GAUSSIAN_SHIFTED;
-  const bool dot = kernel == K_EXPDOT || shifted;  // (mantissa, exponent) partial sums and the shifted tail
   const int KS = kernel == K_EXPDOT ? mfma_ksteps_dot(D) : (shifted ? mfma_ksteps_shifted(D) : mfma_ksteps(D));
   const int NT = (E + 31) / 32;
   if (KS > MFMA_MAX_KS || NT > MFMA_MAX_NT)
@@ -1706,16 +1713,14 @@ int run_product_mfma(kmvp_ctx* c, int kernel, int sig) {
   const int64_t seg_tiles = (m_tiles + seg - 1) / seg;
   const int segments = (int)((m_tiles + seg_tiles - 1) / seg_tiles);
 
-  const bool pts_stale = c->packed_points_ver != c->points_ver || c->packed_kernel != kernel ||
-                         c->packed_layout != LAYOUT_MFMA || c->packed_T != TW;
-  const bool sig_stale = pts_stale || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
+  const PackKey key = {LAYOUT_MFMA, kernel, TW};
   HIP_TRY(c, mark(c, 0));
-  if (pts_stale) {
+  if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)n_pad * KD * 2))) return rc;
     hipLaunchKernelGGL(pack_mfma_targets_kernel, dim3(blocks_for(n_pad)), dim3(256), 0, c->stream,
                        x_raw, (__bf16*)c->xs.p, N, n_pad, D, KD, scale, pack_mode);
   }
-  if (sig_stale) {
+  if (signal_stale(c, key, sig)) {
     if ((rc = ensure(c, c->rec, (size_t)m_tiles * IMG))) return rc;
     hipLaunchKernelGGL(pack_mfma_sources_kernel, dim3(blocks_for(m_tiles * MFMA_TILE)), dim3(256), 0,
                        c->stream, (const float*)c->y_raw.p,
@@ -1723,12 +1728,7 @@ int run_product_mfma(kmvp_ctx* c, int kernel, int sig) {
                        (unsigned char*)c->rec.p, M, m_tiles, D, E, KS, NT, scale, pack_mode);
   }
   HIP_TRY(c, hipGetLastError());
-  c->packed_points_ver = c->points_ver;
-  c->packed_signal_ver = c->signal_ver;
-  c->packed_kernel = kernel;
-  c->packed_sig = sig;
-  c->packed_layout = LAYOUT_MFMA;
-  c->packed_T = TW;
+  record_packed(c, key, sig);
 
   if ((rc = ensure(c, c->part, (size_t)segments * n_pad * NEP * sizeof(float)))) return rc;
   if ((rc = ensure(c, c->partd, (size_t)segments * n_pad * sizeof(float)))) return rc;
@@ -1813,44 +1813,12 @@ int measure_clouds(kmvp_ctx* c, int dtype, int64_t M, int64_t N, int D) {
 }
 
 // kmvp_fit: the cell structures of the Gaussian paths depend on the points only, so they can be built
-// before any signal exists (the conditions are those of run_product() with E = 1 assumed).
+// before any signal exists (the rules are those of run_product() with E = 1 assumed).
 int prepare_points(kmvp_ctx* c, int kernel) {
-  if (kernel != K_GAUSSIAN || c->D > CELL_MAX_D || c->N == 0 || c->M == 0 || c->centre_ver != c->points_ver ||
-      c->opt_fast == 0 || c->opt_fast == 1 || c->opt_fast == 2)
-    return KMVP_OK;
-  const bool big = c->N >= SMALL_PROBLEM_TARGETS && c->M >= SMALL_PROBLEM_TARGETS;
-  if (c->dtype == KMVP_F32) {
-    const float sc = scale_for<float>(kernel);
-    const bool global_ok = c->cloud_radius2 * sc * sc <= FAST_AUTO_RADIUS2;
-    if (c->opt_fast >= 3 || (global_ok && big))
-      return cell_prepare(c, c->opt_fast_tiles > 0 ? c->opt_fast_tiles : (c->N < SMALL_PROBLEM_TARGETS ? 1 : 0));
-  } else if (c->dtype == KMVP_F64) {
-    if (c->opt_fast == 3 || big) return cell64_prepare(c);
-  }
+  if (kernel != K_GAUSSIAN || c->D > CELL_MAX_D || c->N == 0 || c->M == 0 || c->centre_ver != c->points_ver) return KMVP_OK;
+  if (c->dtype == KMVP_F32 && cells_considered(c, false)) return cell_prepare(c, cell_tiles_request(c));
+  if (c->dtype == KMVP_F64 && cells64_considered(c)) return cell64_prepare(c);
   return KMVP_OK;
-}
-
-// Why a float32 Gaussian product at D <= 3 did not take the cell form (kmvp_last_dispatch_note): the fastest paths
-// are narrow, and a caller who gets 5e12 instead of 3.7e13 pairs/s should be told which condition failed.
-static void note_no_cells(kmvp_ctx* c) {
-  char buf[256];
-  const float sc = scale_for<float>(K_GAUSSIAN);
-  if (c->opt_fast >= 0 && c->opt_fast < 3) {
-    snprintf(buf, sizeof buf, "cell form not considered: fast_sqdists = %d was requested", c->opt_fast);
-  } else if (!(c->cloud_radius2 * sc * sc <= FAST_AUTO_RADIUS2)) {
-    snprintf(buf, sizeof buf, "cell form not taken: squared half-diagonal of the clouds' bounding box %.3g > %.3g (radius rule)",
-             (double)(c->cloud_radius2 * sc * sc), (double)FAST_AUTO_RADIUS2);
-  } else if (c->N < SMALL_PROBLEM_TARGETS || c->M < SMALL_PROBLEM_TARGETS) {
-    snprintf(buf, sizeof buf, "cell form not taken: fewer than %lld points in a cloud (N = %lld, M = %lld)",
-             (long long)SMALL_PROBLEM_TARGETS, (long long)c->N, (long long)c->M);
-  } else if (c->cell_state != 1) {
-    snprintf(buf, sizeof buf, "cell form not taken: the grid does not apply (non-finite box or more than %d cells along an axis)",
-             CELL_MAX_GRID);
-  } else {
-    snprintf(buf, sizeof buf, "cell form not taken: padding the cells' tiles would use %.0f %% of the slots (limit %.0f %%): too few "
-             "points per grid cell", 100.0 * cell_padding(c), 100.0 * CELL_AUTO_MAX_PAD);
-  }
-  c->note = buf;
 }
 
 int run_product(kmvp_ctx* c, int kernel, bool normalise) {
@@ -1865,11 +1833,11 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
     return fail(c, KMVP_E_INVALID,
                 "the sources are a shard (M < M_total) but no multi-rank communicator is attached: call kmvp_comm_init, "
                 "or set option partial_shard = 1 to get this shard's partial sums on purpose");
+  const int sig = c->density ? SIG_DENSITY : (normalise ? SIG_NORM : SIG_PRODUCT);
   if (c->M == 0 && c->N > 0 && c->exchanges() && c->world > 1) {
-    // a rank whose source slice is empty still owes the other ranks its (zero) share of the sums
-    const int sig0 = c->density ? SIG_DENSITY : (normalise ? SIG_NORM : SIG_PRODUCT);
+    // a rank whose source slice is empty still owes the other ranks its (zero) share of the sums, through the same tail
     const int E = c->density ? 1 : c->E;
-    const int64_t NE = sig0 == SIG_NORM ? E + 1 : E;
+    const int64_t NE = sig == SIG_NORM ? E + 1 : E;
     int rc = ensure(c, c->sums, (size_t)NE * c->N * sizeof(double));
     if (rc) return rc;
     HIP_TRY(c, mark(c, 0));
@@ -1877,14 +1845,14 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
     HIP_TRY(c, mark(c, 1));
     c->last_kernel_name = "none";
     if (c->density && normalise) {  // every rank takes the all-ones shortcut below: no exchange
-    } else if (kernel == K_EXPDOT) {  // ... and its (absent) exponents: +inf loses every all-reduce(min)
+    } else if (takes_shifted_tail(c, kernel)) {  // ... and its (absent) exponents: +inf loses every all-reduce(min)
       if ((rc = ensure(c, c->kshift, (size_t)c->N * sizeof(double)))) return rc;
       hipLaunchKernelGGL(fill_kernel, dim3(blocks_for(c->N)), dim3(256), 0, c->stream, (double*)c->kshift.p, c->N,
                          (double)INFINITY);
       HIP_TRY(c, hipGetLastError());
-      return finish_product_shifted(c, c->N, c->N, E, sig0);
+      return finish_product_shifted(c, c->N, c->N, E, sig);
     } else {
-      return finish_product(c, NE * c->N, c->N, c->N, E, sig0);
+      return finish_product(c, NE * c->N, c->N, c->N, E, sig);
     }
   }
   if (c->N == 0 || c->M == 0) {
@@ -1916,7 +1884,6 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
     c->last_kernel_name = "fill_kernel";
     return KMVP_OK;
   }
-  const int sig = c->density ? SIG_DENSITY : (normalise ? SIG_NORM : SIG_PRODUCT);
   if (kernel == K_EXPDOT) {
     // k = exp(<x,y>) (include/kmvp.h kmvp_expdot): float32 on fastmm_kernel's matrix-core path only
     if (c->density) return fail(c, KMVP_E_UNSUPPORTED, "exp(<x,y>): pass a signal of ones for density estimation");
@@ -1927,31 +1894,27 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
     return run_product_fastmm(c, K_GAUSSIAN, sig, true);
   }
   if (c->dtype == KMVP_BF16) return run_product_mfma(c, kernel, sig);
-  if (c->dtype == KMVP_F32 && kernel == K_GAUSSIAN && !c->density && (c->E > 1 || c->D > FAST_MAX_D) &&
-      c->centre_ver == c->points_ver && (c->opt_fast < 0 || c->opt_fast == 1 || c->opt_fast == 3)) {
+  const bool f32 = c->dtype == KMVP_F32 && c->centre_ver == c->points_ver;  // float32, clouds measured (measure_clouds)
+  bool cells = false;  // the float32 Gaussian's cell form serves this product (cells_usable)
+  if (f32 && kernel == K_GAUSSIAN && c->D <= CELL_MAX_D) {
+    const int rc = cells_usable(c, !c->density && c->E > 1, cells);
+    if (rc) return rc;
+  }
+  if (f32 && kernel == K_GAUSSIAN && !c->density && (c->E > 1 || c->D > FAST_MAX_D) &&
+      (c->opt_fast < 0 || c->opt_fast == 1 || c->opt_fast == 3)) {
     // Several signal columns (low-D attention with E value channels) -- and single columns beyond fast_kernel's D = 39,
     // which fastmm_kernel serves up to D = 64.  Two forms on the matrix cores:
     //   fastmm_kernel  the tile of kernel values goes back to the matrix pipe for the product with the signal: up to 32
     //                  columns per pass at a cost per pair that does not depend on the column count (D <= 64);
-    //   cellmm_kernel  one launch per column where the cell form applies (same rule as for E = 1 below; D <= 3) --
-    //                  a seventh of fastmm's cost per pair and column where the cells are well filled.
+    //   cellmm_kernel  one launch per column where the cell form applies (D <= 3) -- a seventh of fastmm's cost per
+    //                  pair and column where the cells are well filled.
     // auto takes the cheaper one by the tile counts (picoseconds per 32 x 32 tile on the whole chip, measured at
     // 1e5 .. 1e6 points: tools/fmm_probe.py); fast_sqdists 1 / 3 force one of them.
-    const float sc = scale_for<float>(kernel);
-    const bool global_ok = c->cloud_radius2 * sc * sc <= FAST_AUTO_RADIUS2;
     const int cols = c->E + (normalise ? 1 : 0);
-    const bool fmm_ok = c->D <= FMM_MAX_D && (c->opt_fast == 1 || (c->opt_fast < 0 && global_ok));
-    double t_cell = INFINITY;
-    if (c->D <= CELL_MAX_D && global_ok && c->opt_fast != 1 &&
-        (c->opt_fast == 3 || (c->N >= SMALL_PROBLEM_TARGETS && c->M >= SMALL_PROBLEM_TARGETS))) {
-      const int TT = c->opt_fast_tiles > 0 ? c->opt_fast_tiles : (c->N < SMALL_PROBLEM_TARGETS ? 1 : 0);
-      int rc = cell_prepare(c, TT);
-      if (rc) return rc;
-      if (c->cell_state == 1 && (c->opt_fast == 3 || cell_padding(c) <= CELL_AUTO_MAX_PAD) &&
-          cellmm_wlog2(c) <= CMM_MAX_WLOG2)
-        t_cell = (double)cols * (double)c->cell_m_tiles *
-                 (cell_ps_per_tile(c->cell_tt) * (double)c->cell_n_main + cell_ps_per_tile(2) * (double)c->cell_n_rest);
-    }
+    const bool fmm_ok = c->D <= FMM_MAX_D && (c->opt_fast == 1 || (c->opt_fast < 0 && radius_ok(c, kernel)));
+    const double t_cell = cells ? (double)cols * (double)c->cell_m_tiles *
+                                      (cell_ps_per_tile(c->cell_tt) * (double)c->cell_n_main + cell_ps_per_tile(2) * (double)c->cell_n_rest)
+                                : INFINITY;
     // (the inputs of the choice go into the dispatch note: the constants were measured on one power-limited box)
     char cost[224];
     double t_fmm = INFINITY;
@@ -1967,22 +1930,20 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
       if (c->opt_fast < 0) c->note += cost;
       return rc;
     }
-    if (t_cell < INFINITY) {
+    if (cells) {
       c->note.clear();
       const int rc = run_product_cellmm(c, sig);
       if (c->opt_fast < 0) c->note += cost;
       return rc;
     }
   }
-  if (c->dtype == KMVP_F32 && kernel == K_ABSEXP && !c->density && c->D > CFAST_MAX_D && c->D <= FMM_MAX_D &&
-      c->centre_ver == c->points_ver && (c->opt_fast < 0 || c->opt_fast == 1)) {
+  if (f32 && kernel == K_ABSEXP && !c->density && c->D > CFAST_MAX_D && c->D <= FMM_MAX_D && (c->opt_fast < 0 || c->opt_fast == 1)) {
     // exp(-r) beyond the centred forms' D = 4: fastmm_kernel's expansion around one centre with the closest pairs
     // recomputed exactly (any number of signal columns, one included), on clouds inside the radius rule
     // (auto: beyond the specialised difference form's D = 8, or where that form would go column by column -- at
     // D = 5 with up to four columns the two are equally fast)
-    const float sc = scale_for<float>(kernel);
     const bool pays = c->D > LOWD_MAX_D || c->E + (normalise ? 1 : 0) > LOWD_MAX_E;
-    if (c->cloud_radius2 * sc * sc <= FAST_AUTO_RADIUS2 && (c->opt_fast == 1 || pays)) {
+    if (radius_ok(c, kernel) && (c->opt_fast == 1 || pays)) {
       c->note.clear();
       return run_product_fastmm(c, K_ABSEXP, sig);
     }
@@ -1990,16 +1951,14 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
   // (1/r: cfast_kernel's zero rule drops the pair with the target's own index among the COINCIDENT pairs, so the targets
   // must be the sources -- all of them, also when the sources are sharded)
   const bool invdist_square = kernel == K_INVDIST && (c->same_points || c->opt_same_global) && c->N == c->m_total;
-  if (c->dtype == KMVP_F32 && (kernel == K_GAUSSIAN || kernel == K_ABSEXP || invdist_square) && !c->density && c->E > 1 &&
-      c->D <= CFAST_MAX_D && c->centre_ver == c->points_ver &&
+  if (f32 && (kernel == K_GAUSSIAN || kernel == K_ABSEXP || invdist_square) && !c->density && c->E > 1 && c->D <= CFAST_MAX_D &&
       (c->opt_fast == 2 || (c->opt_fast < 0 && c->E + (normalise ? 1 : 0) >= CFMM_AUTO_MIN_COLS))) {
     // several signal columns where fastmm_kernel does not apply: exp(-r) and 1/r, which need relative accuracy in s, and
     // the Gaussian on clouds outside the radius rule -- cfast_kernel's distances, the same second product
     c->note.clear();
     return run_product_cfastmm(c, kernel, sig);
   }
-  if (c->dtype == KMVP_F32 && kernel == K_GAUSSIAN && c->D <= CELL_MAX_D && c->centre_ver == c->points_ver) note_no_cells(c);
-  if (c->dtype == KMVP_F32 && c->D <= FAST_MAX_D && (c->density || c->E == 1) && c->centre_ver == c->points_ver) {
+  if (f32 && c->D <= FAST_MAX_D && (c->density || c->E == 1)) {
     // "fast_sqdists": squared distances in the expanded form on the matrix cores.
     //   fast_kernel  one centre for the whole cloud: absolute error eps32 (|x'|^2 + |y'|^2) in s
     //                -> as accurate as the difference form only for the Gaussian (smooth in s)
@@ -2009,36 +1968,27 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
     //                inverse-distance zero rule is applied there to coincident pairs only, so
     //                it needs targets == sources.
     // auto (-1) picks the cheapest form that is as accurate as the difference form.
-    const float sc = scale_for<float>(kernel);
-    const bool global_ok = kernel == K_GAUSSIAN && c->cloud_radius2 * sc * sc <= FAST_AUTO_RADIUS2;
-    const bool same = c->same_points || c->opt_same_global;
-    const bool centred_ok = c->D <= CFAST_MAX_D && (kernel != K_INVDIST || (same && c->N == c->m_total));
+    const bool global_ok = kernel == K_GAUSSIAN && radius_ok(c, kernel);
+    const bool centred_ok = c->D <= CFAST_MAX_D && (kernel != K_INVDIST || invdist_square);
     // cell_kernel: exp() range-reduced by grid cells, the polynomial remainder on the matrix cores
     // (Gaussian, D <= 3).  auto: when the clouds fill the cells well enough that padding stays small.
     // (also inside a solver iteration: grid, cell order and tile lists belong to the points and were built by
     // kmvp_fit or by the first product -- long before a burst of iterations is captured into a hipGraph -- and the
     // launches of the cell paths themselves are asynchronous)
-    if (kernel == K_GAUSSIAN && c->D <= CELL_MAX_D &&
-        (c->opt_fast >= 3 || (c->opt_fast < 0 && global_ok && c->N >= SMALL_PROBLEM_TARGETS && c->M >= SMALL_PROBLEM_TARGETS))) {
-      const int TT = c->opt_fast_tiles > 0 ? c->opt_fast_tiles : (c->N < SMALL_PROBLEM_TARGETS ? 1 : 0);  // 0: by the padding
-      int rc = cell_prepare(c, TT);
-      if (rc) return rc;
-      if (c->cell_state == 1 && (c->opt_fast >= 3 || cell_padding(c) <= CELL_AUTO_MAX_PAD)) {
-        // cellmm_kernel (weights in the operand, sum in the accumulator) where its f16 operands have the range:
-        // clouds inside the radius rule; cell_kernel otherwise (wide clouds) or on request (fast_sqdists = 4)
-        c->note.clear();
-        if (c->opt_fast != 4 && global_ok && cellmm_wlog2(c) <= CMM_MAX_WLOG2)
-          return run_product_cellmm(c, sig);  // normalised rows: a second launch with b = 1 for the denominator
-        if (c->opt_fast != 4) c->note = "cell_kernel instead of cellmm_kernel: the clouds are outside the radius rule (f16 operand range)";
-        return run_product_cell(c, sig);
-      }
+    if (cells) {
+      // cellmm_kernel (weights in the operand, sum in the accumulator) where its f16 operands have the range:
+      // clouds inside the radius rule; cell_kernel otherwise (wide clouds) or on request (fast_sqdists = 4)
+      c->note.clear();
+      if (c->opt_fast != 4 && cellmm_in_range(c))
+        return run_product_cellmm(c, sig);  // normalised rows: a second launch with b = 1 for the denominator
+      if (c->opt_fast != 4) c->note = "cell_kernel instead of cellmm_kernel: the clouds are outside the radius rule (f16 operand range)";
+      return run_product_cell(c, sig);
     }
     if (c->opt_fast == 1 || (c->opt_fast < 0 && global_ok)) return run_product_fast(c, kernel, sig);
     if (centred_ok && (c->opt_fast == 2 || c->opt_fast < 0)) return run_product_cfast(c, kernel, sig);
   }
   if (c->dtype == KMVP_F64 && kernel == K_GAUSSIAN && c->D <= CELL_MAX_D && (c->density || c->E == 1) &&
-      c->centre_ver == c->points_ver &&
-      (c->opt_fast == 3 || (c->opt_fast < 0 && c->N >= SMALL_PROBLEM_TARGETS && c->M >= SMALL_PROBLEM_TARGETS))) {
+      c->centre_ver == c->points_ver && cells64_considered(c)) {
     // float64 cell form (kmvp_cell64.hpp): 12 fp64 instructions per pair instead of ~23
     int rc = cell64_prepare(c);
     if (rc) return rc;
@@ -2046,10 +1996,10 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
         (c->opt_fast == 3 || (double)c->cell_n_tiles * CELL64_TILE <= CELL_AUTO_MAX_PAD * (double)c->N))
       return run_product_cell64(c, sig);
   }
-  if (c->D <= LOWD_MAX_D && !c->density && c->E > LOWD_MAX_E && c->note.empty())
-    c->note = "E > 4 signal columns: the difference form runs once per block of four columns";
-  if (c->D <= LOWD_MAX_D && !c->density && c->E > LOWD_MAX_E)  // low D, many signal columns
+  if (c->D <= LOWD_MAX_D && !c->density && c->E > LOWD_MAX_E) {  // low D, many signal columns
+    if (c->note.empty()) c->note = "E > 4 signal columns: the difference form runs once per block of four columns";
     return c->dtype == KMVP_F64 ? run_product_blocked<double>(c, kernel, sig) : run_product_blocked<float>(c, kernel, sig);
+  }
   if (c->dtype == KMVP_F64) return run_product_t<double>(c, kernel, sig);
   return run_product_t<float>(c, kernel, sig);
 }

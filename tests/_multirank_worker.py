@@ -43,6 +43,7 @@ def main():
         ("absolute-exponential", True, np.float64, 3000, 5, 3, True, 1e-11),
         ("absolute-exponential", True, "bfloat16", 4096, 64, 64, False, 1e-2),
         ("gaussian", False, "float32", world - 1, 3, 1, False, 1e-5),     # fewer sources than ranks: an EMPTY shard
+        ("gaussian", False, "bfloat16", world - 1, 16, 1, True, 2e-2),    # ... bf16, x != y: the shifted tail on every rank
     ]
     for kernel, normalize, precision, n, D, E, other, tol in products:
         rs = np.random.RandomState(n + D)
