@@ -47,29 +47,6 @@ __global__ void cg_dot_kernel(const double* __restrict__ u, const double* __rest
   }
 }
 
-// out[i][e] = u[i][e] + coef[e] * v[i][e]
-__global__ void cg_axpy_kernel(double* __restrict__ out, const double* __restrict__ u,
-                               const double* __restrict__ v, const double* __restrict__ coef,
-                               int64_t m, int E) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= m * E) return;
-  out[q] = u[q] + coef[q % E] * v[q];
-}
-
-// Coefficients of a vector update passed BY VALUE in the kernel argument block (E <= 8): no
-// host-to-device copy and no stream synchronisation per update (a small solve is otherwise
-// dominated by them: seven synchronisations per CG iteration instead of three).
-constexpr int COEF_INLINE_E = 8;
-struct Coef8 { double v[COEF_INLINE_E]; };
-struct Coef24 { double v[3 * COEF_INLINE_E]; };
-
-__global__ void cg_axpy_inline_kernel(double* __restrict__ out, const double* __restrict__ u,
-                                      const double* __restrict__ v, const Coef8 coef, int64_t m, int E) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= m * E) return;
-  out[q] = u[q] + coef.v[q % E] * v[q];
-}
-
 template <typename real>
 __global__ void cg_cast_kernel(const double* __restrict__ in, real* __restrict__ out, int64_t n) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -79,6 +56,13 @@ template <typename real>
 __global__ void cg_widen_kernel(const real* __restrict__ in, double* __restrict__ out, int64_t n) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q < n) out[q] = (double)in[q];
+}
+// out = a - K x: the right-hand side as uploaded (working precision), widened, minus the product
+template <typename real>
+__global__ void residual_kernel(const real* __restrict__ a, const double* __restrict__ Kx, double* __restrict__ out,
+                                int64_t n) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < n) out[q] = (double)a[q] - Kx[q];
 }
 
 // Sum of the CG_BLOCKS partials of column e by the whole block (fixed tree order: deterministic).
@@ -153,16 +137,54 @@ __global__ void cg_update_p_kernel(double* __restrict__ p, const double* __restr
   p[q] = r[q] + scal[2 * E + q % E] * p[q];
 }
 
-struct CgWork {
-  double *x, *r, *p, *partial, *coef;
+// ------------------------------------------------------------------------------------
+// host side shared by both solvers
+
+// One solve's scratch block: `nvec` Krylov vectors of N x E doubles, the dot products' partial sums, then
+// the device-resident iteration's state, with its stop word at `stop` and the iteration count after it.
+struct Krylov {
+  int64_t m = 0;  // length of the Krylov vectors: all points
+  int E = 0;
+  size_t n = 0;  // m * E
+  size_t stop = 0;
+  double *vecs = nullptr, *partial = nullptr, *state = nullptr;
+  double* vec(int i) const { return vecs + (size_t)i * n; }
 };
 
-int cg_dots(kmvp_ctx* c, const double* u, const double* v, int64_t m, int E, const CgWork& w,
-            std::vector<double>& host_partial, std::vector<double>& out) {
-  hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, u, v, m, E, w.partial);
+// The checks both solvers make, the device, and the scratch layout.
+static int solver_begin(kmvp_ctx* c, const void* a_host, int E, double rtol, int maxit, const double* out_b, int nvec,
+                        size_t stop, Krylov& k) {
+  if (!c) return KMVP_E_INVALID;
+  if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
+  if (int rc = solver_shape(c)) return rc;
+  if (!a_host || !out_b || E < 1 || maxit < 0 || !(rtol > 0)) return fail(c, KMVP_E_INVALID, "bad solver arguments");
+  HIP_TRY(c, hipSetDevice(c->device));
+  k.m = c->N;
+  k.E = E;
+  k.n = (size_t)k.m * E;
+  k.stop = stop;
+  if (int rc = ensure(c, c->scratch, sizeof(double) * (nvec * k.n + (size_t)CG_BLOCKS * E + stop + 2))) return rc;
+  k.vecs = (double*)c->scratch.p;
+  k.partial = k.vec(nvec);
+  k.state = k.partial + (size_t)CG_BLOCKS * E;
+  return KMVP_OK;
+}
+
+// However a solve ends, the product is synchronous again and no signal is left behind: b_raw held the
+// right-hand side and the Krylov vectors, not what kmvp_set_signal uploaded.
+struct SolveGuard {
+  kmvp_ctx* c;
+  ~SolveGuard() { c->async_product = false; c->have_signal = false; }
+};
+
+// out = sum over the CG_BLOCKS partials of u . v per column
+static int cg_dots(kmvp_ctx* c, const double* u, const double* v, const Krylov& k, std::vector<double>& out) {
+  const int E = k.E;
+  std::vector<double> host_partial((size_t)CG_BLOCKS * E);
+  hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, u, v, k.m, E, k.partial);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(host_partial.data(), w.partial, sizeof(double) * CG_BLOCKS * E,
-                            hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(host_partial.data(), k.partial, sizeof(double) * CG_BLOCKS * E, hipMemcpyDeviceToHost,
+                            c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   out.assign(E, 0.0);
   for (int b = 0; b < CG_BLOCKS; ++b)
@@ -170,85 +192,170 @@ int cg_dots(kmvp_ctx* c, const double* u, const double* v, int64_t m, int E, con
   return KMVP_OK;
 }
 
-int cg_axpy(kmvp_ctx* c, double* out, const double* u, const double* v,
-            const std::vector<double>& coef, int64_t m, int E, const CgWork& w) {
-  if (E <= COEF_INLINE_E) {
-    Coef8 k;
-    for (int e = 0; e < COEF_INLINE_E; ++e) k.v[e] = e < E ? coef[e] : 0.0;
-    hipLaunchKernelGGL(cg_axpy_inline_kernel, dim3(blocks_for(m * E)), dim3(256), 0, c->stream, out, u, v, k, m, E);
-    HIP_TRY(c, hipGetLastError());
-    return KMVP_OK;
-  }
-  HIP_TRY(c, hipMemcpyAsync(w.coef, coef.data(), sizeof(double) * E, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // coef is a host temporary
-  hipLaunchKernelGGL(cg_axpy_kernel, dim3(blocks_for(m * E)), dim3(256), 0, c->stream, out, u, v,
-                     w.coef, m, E);
-  HIP_TRY(c, hipGetLastError());
-  return KMVP_OK;
-}
-
-// K applied to the device vector v (n,E) double, n = all points; the result lands in c->out
-// (n,E) double.  With source sharding the Krylov vectors are replicated on every
+// K applied to the device vector v (N,E) double, N = all points; the result lands in c->out
+// (N,E) double.  With source sharding the Krylov vectors are replicated on every
 // rank, the operator is sharded: this rank's signal is its own slice v[j_offset .. j_offset+M)
-// and run_product() ends with the all-reduce of the (n,E) sums, so every rank continues with
+// and run_product() ends with the all-reduce of the (N,E) sums, so every rank continues with
 // bitwise the same vectors.
-int cg_apply(kmvp_ctx* c, int kernel, const double* v, int64_t n, int E) {
-  const int64_t m = c->M;  // sources of this rank
-  (void)n;
-  v += (size_t)c->j_offset * E;
-  int rc = ensure(c, c->b_raw, (size_t)n * E * elem_size(c->dtype));  // also holds the right-hand side
+static int cg_apply(kmvp_ctx* c, int kernel, const double* v, const Krylov& k) {
+  const int64_t n = c->M * k.E;  // this rank's sources
+  v += (size_t)c->j_offset * k.E;
+  int rc = ensure(c, c->b_raw, k.n * elem_size(c->dtype));  // also holds the right-hand side
   if (rc) return rc;
   if (c->dtype == KMVP_F64)
-    hipLaunchKernelGGL((cg_cast_kernel<double>), dim3(blocks_for(m * E)), dim3(256), 0, c->stream, v,
-                       (double*)c->b_raw.p, m * E);
+    hipLaunchKernelGGL((cg_cast_kernel<double>), dim3(blocks_for(n)), dim3(256), 0, c->stream, v, (double*)c->b_raw.p, n);
   else
-    hipLaunchKernelGGL((cg_cast_kernel<float>), dim3(blocks_for(m * E)), dim3(256), 0, c->stream, v,
-                       (float*)c->b_raw.p, m * E);
+    hipLaunchKernelGGL((cg_cast_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, c->stream, v, (float*)c->b_raw.p, n);
   HIP_TRY(c, hipGetLastError());
   c->density = false;
-  c->E = E;
+  c->E = k.E;
   c->have_signal = true;
   ++c->signal_ver;
   return run_product(c, kernel, false);
 }
 
+// b_raw = the right-hand side as the caller passed it (N x E values in the working precision)
+static int upload_rhs(kmvp_ctx* c, const void* a_host, const Krylov& k) {
+  const size_t bytes = k.n * elem_size(c->dtype);
+  if (int rc = ensure(c, c->b_raw, bytes)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->b_raw.p, a_host, bytes, hipMemcpyHostToDevice, c->stream));
+  return KMVP_OK;
+}
+
+// out = the right-hand side widened to double
+static int load_rhs(kmvp_ctx* c, const void* a_host, double* out, const Krylov& k) {
+  if (int rc = upload_rhs(c, a_host, k)) return rc;
+  const int64_t n = (int64_t)k.n;
+  if (c->dtype == KMVP_F64)
+    hipLaunchKernelGGL((cg_widen_kernel<double>), dim3(blocks_for(n)), dim3(256), 0, c->stream, (const double*)c->b_raw.p, out, n);
+  else
+    hipLaunchKernelGGL((cg_widen_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, c->stream, (const float*)c->b_raw.p, out, n);
+  HIP_TRY(c, hipGetLastError());
+  return KMVP_OK;
+}
+
+// r = a - K x with one more product, and r2 = |r|^2 per column
+static int true_residual(kmvp_ctx* c, int kernel, const void* a_host, const double* x, double* r, const Krylov& k,
+                         std::vector<double>& r2) {
+  int rc = cg_apply(c, kernel, x, k);
+  if (!rc) rc = upload_rhs(c, a_host, k);  // after the product: b_raw held x
+  if (rc) return rc;
+  const int64_t n = (int64_t)k.n;
+  const double* Kx = (const double*)c->out.p;
+  if (c->dtype == KMVP_F64)
+    hipLaunchKernelGGL((residual_kernel<double>), dim3(blocks_for(n)), dim3(256), 0, c->stream, (const double*)c->b_raw.p, Kx, r, n);
+  else
+    hipLaunchKernelGGL((residual_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, c->stream, (const float*)c->b_raw.p, Kx, r, n);
+  HIP_TRY(c, hipGetLastError());
+  return cg_dots(c, r, r, k, r2);
+}
+
+// One burst = CG_CHECK iterations of ~10 launches each.  A solve that is still running after
+// CG_GRAPH_AFTER full bursts replays the burst as a hipGraph from then on (instantiating the 80-node
+// graph costs ~70 ms on this stack, so short solves never pay for it; single GPU only: with a
+// communicator the all-reduce stays out of graphs).  KMVP_NO_GRAPH=1 disables it; a refused capture
+// falls back to plain launches for the rest of the solve.  One per solve, across its restarts.
+struct BurstGraph {
+  hipGraphExec_t exec = nullptr;
+  int full_bursts = 0;
+  bool try_graph;
+  explicit BurstGraph(const kmvp_ctx* c) : try_graph(!c->exchanges() && getenv("KMVP_NO_GRAPH") == nullptr) {}
+  BurstGraph(const BurstGraph&) = delete;
+  BurstGraph& operator=(const BurstGraph&) = delete;
+  ~BurstGraph() { if (exec) (void)hipGraphExecDestroy(exec); }
+  int launch(kmvp_ctx* c) {
+    return hipGraphLaunch(exec, c->stream) == hipSuccess ? KMVP_OK : fail(c, KMVP_E_DEVICE, "hipGraphLaunch failed");
+  }
+  template <typename Body>
+  int run(kmvp_ctx* c, int burst, const Body& body) {
+    if (burst != CG_CHECK) return body(burst);
+    const bool capture = !exec && try_graph && full_bursts >= CG_GRAPH_AFTER;
+    ++full_bursts;
+    if (exec) return launch(c);
+    if (!capture) return body(burst);
+    // every buffer exists and every layout decision has been taken by the first burst: capture
+    if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+      (void)hipGetLastError();
+      try_graph = false;
+      return body(burst);
+    }
+    const int rc = body(burst);
+    hipGraph_t graph = nullptr;
+    const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
+    if (rc == KMVP_OK && ee == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess)
+      exec = nullptr;
+    if (graph) (void)hipGraphDestroy(graph);
+    if (rc) return rc;
+    if (exec) return launch(c);
+    (void)hipGetLastError();  // capture refused: nothing ran, go on launch by launch
+    try_graph = false;
+    return body(burst);
+  }
+};
+
+// The host's part of a device-resident iteration: while it < maxit and rel > rtol, one burst of
+// iterations (`body`, through `graph` when there is one), then a look at the device state (k.stop + 2
+// doubles, read into `state`): the iteration count, `rel` as `rel_of` computes it from the state, and
+// the stop word, set by the device once the tolerance was met inside the burst.
+template <typename Body, typename Rel>
+static int run_bursts(kmvp_ctx* c, const Krylov& k, int maxit, double rtol, int& it, double& rel,
+                      std::vector<double>& state, const Body& body, const Rel& rel_of, BurstGraph* graph) {
+  c->async_product = true;
+  while (it < maxit && rel > rtol) {
+    const int burst = std::min(CG_CHECK, maxit - it);
+    if (int rc = graph ? graph->run(c, burst, body) : body(burst)) return rc;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(state.data(), k.state, sizeof(double) * (k.stop + 2), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    it = (int)state[k.stop + 1];  // iterations that changed the iterate
+    rel = rel_of();
+    if (state[k.stop] != 0.0) break;
+  }
+  c->async_product = false;
+  return KMVP_OK;
+}
+
+// Copies the solution out.  The verdict is on the TRUE residual (include/kmvp.h), with 1.5x slack for
+// the rounding between it and the recurrence the iteration stops on; a non-finite residual
+// (non-finite operator or right-hand side) is never a success.
+static int solver_end(kmvp_ctx* c, const char* method, const double* x, const Krylov& k, double* out_b, int it,
+                      double true_rel, double rtol, int* iters, double* resid) {
+  HIP_TRY(c, hipMemcpyAsync(out_b, x, sizeof(double) * k.n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (iters) *iters = it;
+  if (resid) *resid = true_rel;
+  if (!(std::isfinite(true_rel) && true_rel <= rtol * 1.5)) {
+    c->err = std::string(method) + (std::isfinite(true_rel)
+                                         ? " stopped before the true residual reached the requested tolerance"
+                                         : ": the residual is not finite (non-finite operator or right-hand side)");
+    return KMVP_E_NOT_CONVERGED;
+  }
+  return KMVP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// conjugate gradients
+
 int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit,
              double* out_b, int* iters, double* resid) {
-  if (!c) return KMVP_E_INVALID;
-  if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
-  if (int rc0 = solver_shape(c)) return rc0;
-  if (!a_host || !out_b || E < 1 || maxit < 0 || !(rtol > 0)) return fail(c, KMVP_E_INVALID, "bad solver arguments");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const int64_t m = c->N;  // length of the Krylov vectors: all points
-  const size_t vec = (size_t)m * E * sizeof(double);
-  int rc = ensure(c, c->scratch, 3 * vec + sizeof(double) * ((CG_BLOCKS + 1 + 4) * (size_t)E + 2));
-  if (rc) return rc;
-  CgWork w;
-  w.x = (double*)c->scratch.p;
-  w.r = w.x + (size_t)m * E;
-  w.p = w.r + (size_t)m * E;
-  w.partial = w.p + (size_t)m * E;
-  w.coef = w.partial + (size_t)CG_BLOCKS * E;
-  std::vector<double> hp((size_t)CG_BLOCKS * E), rs, rs_new, pap, anorm2, coef(E);
+  Krylov k;  // x, r, p; state: scal = [rs_old | alpha | beta | |a|^2] x E, stop, iterations
+  if (int rc = solver_begin(c, a_host, E, rtol, maxit, out_b, 3, 4 * (size_t)E, k)) return rc;
+  SolveGuard guard{c};
+  BurstGraph graph(c);
+  const int64_t m = k.m;
+  const size_t vec = k.n * sizeof(double);
+  double *x = k.vec(0), *r = k.vec(1), *p = k.vec(2), *scal = k.state;
 
   // r = p = a (widened to double), x = 0
-  rc = ensure(c, c->b_raw, (size_t)m * E * elem_size(c->dtype));
+  int rc = load_rhs(c, a_host, r, k);
   if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->b_raw.p, a_host, (size_t)m * E * elem_size(c->dtype), hipMemcpyHostToDevice, c->stream));
-  if (c->dtype == KMVP_F64)
-    hipLaunchKernelGGL((cg_widen_kernel<double>), dim3(blocks_for(m * E)), dim3(256), 0, c->stream,
-                       (const double*)c->b_raw.p, w.r, m * E);
-  else
-    hipLaunchKernelGGL((cg_widen_kernel<float>), dim3(blocks_for(m * E)), dim3(256), 0, c->stream,
-                       (const float*)c->b_raw.p, w.r, m * E);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(w.p, w.r, vec, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(c, hipMemsetAsync(w.x, 0, vec, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(p, r, vec, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(x, 0, vec, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if ((rc = cg_dots(c, w.r, w.r, m, E, w, hp, rs))) return rc;
-  anorm2 = rs;
+  std::vector<double> anorm2, rs_new;
+  if ((rc = cg_dots(c, r, r, k, anorm2))) return rc;
 
-  auto worst = [&](const std::vector<double>& r2) {
+  auto worst = [&](const double* r2) {
     double wv = 0.0;
     for (int e = 0; e < E; ++e) {
       const double v = anorm2[e] > 0 ? std::sqrt(r2[e] / anorm2[e]) : (anorm2[e] == 0 ? 0.0 : NAN);
@@ -261,42 +368,30 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
   // the dot products' partial sums (same additions in the same order as the host would do) and the
   // vector updates read them from device memory, so an iteration is a sequence of launches with no
   // host synchronisation; the host looks at the residual every CG_CHECK iterations only.
-  double* scal = w.partial + (size_t)CG_BLOCKS * E + E;  // [rs_old | alpha | beta | |a|^2] x E, stop, iterations
-  {
-    std::vector<double> init((size_t)4 * E + 2, 0.0);
-    for (int e = 0; e < E; ++e) {
-      init[e] = rs[e];
-      init[3 * E + e] = anorm2[e];
-    }
-    HIP_TRY(c, hipMemcpyAsync(scal, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::vector<double> state(k.stop + 2, 0.0);
+  for (int e = 0; e < E; ++e) {
+    state[e] = anorm2[e];
+    state[3 * E + e] = anorm2[e];
   }
+  HIP_TRY(c, hipMemcpyAsync(scal, state.data(), sizeof(double) * state.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   const unsigned vblocks = blocks_for(m * E);
-  std::vector<double> state((size_t)4 * E + 2);
-  int it = 0;
-  double rel = worst(rs);
-  c->async_product = true;
-  // one burst = CG_CHECK iterations of ~10 launches each.  A solve that is still running after
-  // CG_GRAPH_AFTER bursts replays the burst as a hipGraph from then on (instantiating the 80-node
-  // graph costs ~70 ms on this stack, so short solves never pay for it; single GPU only: with a
-  // communicator the all-reduce stays out of graphs).  KMVP_NO_GRAPH=1 disables it.
-  auto run_burst = [&](int burst) -> int {
-    for (int k = 0; k < burst; ++k) {
-      int rcb = cg_apply(c, kernel, w.p, m, E);
-      if (rcb) return rcb;
+  auto body = [&](int burst) -> int {
+    for (int i = 0; i < burst; ++i) {
+      if (int rcb = cg_apply(c, kernel, p, k)) return rcb;
       const double* Ap = (const double*)c->out.p;
-      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, w.p, Ap, m, E, w.partial);
-      hipLaunchKernelGGL(cg_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, w.partial, scal, E, 1, rtol);
-      hipLaunchKernelGGL(cg_update_xr_kernel, dim3(vblocks), dim3(256), 0, c->stream, w.x, w.r, w.p, Ap, scal, m, E);
-      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, w.r, w.r, m, E, w.partial);
-      hipLaunchKernelGGL(cg_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, w.partial, scal, E, 2, rtol);
-      hipLaunchKernelGGL(cg_update_p_kernel, dim3(vblocks), dim3(256), 0, c->stream, w.p, w.r, scal, m, E);
+      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, p, Ap, m, E, k.partial);
+      hipLaunchKernelGGL(cg_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, scal, E, 1, rtol);
+      hipLaunchKernelGGL(cg_update_xr_kernel, dim3(vblocks), dim3(256), 0, c->stream, x, r, p, Ap, scal, m, E);
+      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, r, r, m, E, k.partial);
+      hipLaunchKernelGGL(cg_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, scal, E, 2, rtol);
+      hipLaunchKernelGGL(cg_update_p_kernel, dim3(vblocks), dim3(256), 0, c->stream, p, r, scal, m, E);
     }
     return KMVP_OK;
   };
-  hipGraphExec_t gexec = nullptr;
-  bool try_graph = !c->exchanges() && getenv("KMVP_NO_GRAPH") == nullptr;
-  int full_bursts = 0;
+  auto rel_of = [&] { return worst(state.data()); };  // rs_old heads the state
+  int it = 0;
+  double rel = worst(anorm2.data());
   double true_rel = NAN, prev_true = INFINITY;
   // The iteration stops on the RECURRENCE residual; the verdict is on the TRUE one, a - K x, from one more
   // product.  Where the two have drifted apart (float32 operator, ill-conditioned Gaussian matrices) the
@@ -304,146 +399,27 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
   // CG_MAX_RESTARTS times and only while that still halves the true residual.
   constexpr int CG_MAX_RESTARTS = 3;
   for (int pass = 0;; ++pass) {
-    while (it < maxit && rel > rtol) {
-      const int burst = std::min(CG_CHECK, maxit - it);
-      if (gexec && burst == CG_CHECK) {
-        if (hipGraphLaunch(gexec, c->stream) != hipSuccess) rc = fail(c, KMVP_E_DEVICE, "hipGraphLaunch failed");
-      } else if (try_graph && full_bursts >= CG_GRAPH_AFTER && burst == CG_CHECK) {
-        // every buffer exists and every layout decision has been taken by the first burst: capture
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-          rc = run_burst(burst);
-          hipGraph_t graph = nullptr;
-          const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
-          if (rc == KMVP_OK && ee == hipSuccess && graph &&
-              hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess)
-            gexec = nullptr;
-          if (graph) (void)hipGraphDestroy(graph);
-          if (rc == KMVP_OK) {
-            if (gexec) {
-              if (hipGraphLaunch(gexec, c->stream) != hipSuccess) rc = fail(c, KMVP_E_DEVICE, "hipGraphLaunch failed");
-            } else {
-              (void)hipGetLastError();  // capture refused: nothing ran, go on launch by launch
-              try_graph = false;
-              rc = run_burst(burst);
-            }
-          }
-        } else {
-          (void)hipGetLastError();
-          try_graph = false;
-          rc = run_burst(burst);
-        }
-      } else {
-        rc = run_burst(burst);
-      }
-      if (burst == CG_CHECK) ++full_bursts;
-      if (rc) {
-        c->async_product = false;
-        if (gexec) (void)hipGraphExecDestroy(gexec);
-        return rc;
-      }
-      hipError_t le = hipGetLastError();
-      if (le == hipSuccess)
-        le = hipMemcpyAsync(state.data(), scal, sizeof(double) * state.size(), hipMemcpyDeviceToHost, c->stream);
-      if (le == hipSuccess) le = hipStreamSynchronize(c->stream);
-      if (le != hipSuccess) {
-        c->async_product = false;
-        if (gexec) (void)hipGraphExecDestroy(gexec);
-        HIP_TRY(c, le);
-      }
-      for (int e = 0; e < E; ++e) rs[e] = state[e];
-      it = (int)state[(size_t)4 * E + 1];  // iterations that changed the iterate
-      rel = worst(rs);
-      if (state[(size_t)4 * E] != 0.0) break;  // the device met the tolerance inside the burst
-    }
-    c->async_product = false;
-
-    // true residual ||a - K x|| / ||a|| with one more product: w.p = a (widened again) - K x
-    rc = cg_apply(c, kernel, w.x, m, E);
-    hipError_t he = hipSuccess;
-    if (!rc) he = hipMemcpyAsync(c->b_raw.p, a_host, (size_t)m * E * elem_size(c->dtype), hipMemcpyHostToDevice, c->stream);
-    if (!rc && he == hipSuccess) {
-      if (c->dtype == KMVP_F64)
-        hipLaunchKernelGGL((cg_widen_kernel<double>), dim3(blocks_for(m * E)), dim3(256), 0, c->stream,
-                           (const double*)c->b_raw.p, w.p, m * E);
-      else
-        hipLaunchKernelGGL((cg_widen_kernel<float>), dim3(blocks_for(m * E)), dim3(256), 0, c->stream,
-                           (const float*)c->b_raw.p, w.p, m * E);
-      he = hipGetLastError();
-    }
-    if (!rc && he == hipSuccess) {
-      for (int e = 0; e < E; ++e) coef[e] = -1.0;
-      rc = cg_axpy(c, w.p, w.p, (const double*)c->out.p, coef, m, E, w);
-      if (!rc) rc = cg_dots(c, w.p, w.p, m, E, w, hp, rs_new);
-    }
-    if (rc || he != hipSuccess) {
-      if (gexec) (void)hipGraphExecDestroy(gexec);
-      if (rc) return rc;
-      HIP_TRY(c, he);
-    }
-    true_rel = worst(rs_new);
+    if ((rc = run_bursts(c, k, maxit, rtol, it, rel, state, body, rel_of, &graph))) return rc;
+    if ((rc = true_residual(c, kernel, a_host, x, p, k, rs_new))) return rc;  // p = a - K x
+    true_rel = worst(rs_new.data());
     const bool met = std::isfinite(true_rel) && true_rel <= rtol * 1.5;
     if (met || !std::isfinite(true_rel) || it >= maxit || pass >= CG_MAX_RESTARTS || !(true_rel <= 0.5 * prev_true)) break;
     // restart from the true residual: r = p = a - K x, rs_old = |r|^2, stop flag cleared (the count goes on)
     prev_true = true_rel;
-    HIP_TRY(c, hipMemcpyAsync(w.r, w.p, vec, hipMemcpyDeviceToDevice, c->stream));
-    rs = rs_new;
-    {
-      std::vector<double> head((size_t)E);
-      for (int e = 0; e < E; ++e) head[e] = rs[e];
-      const double zero = 0.0;
-      HIP_TRY(c, hipMemcpyAsync(scal, head.data(), sizeof(double) * E, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(scal + 4 * (size_t)E, &zero, sizeof(double), hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    const double zero = 0.0;
+    HIP_TRY(c, hipMemcpyAsync(r, p, vec, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(scal, rs_new.data(), sizeof(double) * E, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(scal + 4 * (size_t)E, &zero, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     rel = true_rel;
-    c->async_product = true;
   }
-  if (gexec) (void)hipGraphExecDestroy(gexec);
-
-  HIP_TRY(c, hipMemcpyAsync(out_b, w.x, vec, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->have_signal = false;  // b_raw was used as scratch
-  if (iters) *iters = it;
-  if (resid) *resid = true_rel;
-  // the verdict is on the TRUE residual (include/kmvp.h), with 1.5x slack for the rounding between it and the
-  // recurrence; a non-finite residual (non-finite operator or right-hand side) is never a success
-  if (!(std::isfinite(true_rel) && true_rel <= rtol * 1.5)) {
-    c->err = std::isfinite(true_rel) ? "conjugate gradients stopped before the true residual reached the requested tolerance"
-                                     : "conjugate gradients: the residual is not finite (non-finite operator or right-hand side)";
-    return KMVP_E_NOT_CONVERGED;
-  }
-  return KMVP_OK;
+  return solver_end(c, "conjugate gradients", x, k, out_b, it, true_rel, rtol, iters, resid);
 }
 
 
 // ------------------------------------------------------------------------------------
 // MINRES (Paige & Saunders) for the symmetric INDEFINITE inverse-distance systems (zero
 // diagonal), where conjugate gradients does not apply.  One product per iteration.
-
-// out[i][e] = ca[e] * a[i][e] + cb[e] * b[i][e] + cc[e] * c[i][e]   (coefficients: [3][E])
-__global__ void vec_lin3_kernel(double* __restrict__ out, const double* __restrict__ a,
-                                const double* __restrict__ b, const double* __restrict__ c,
-                                const double* __restrict__ coef, int64_t m, int E) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= m * E) return;
-  const int e = (int)(q % E);
-  double v = coef[e] * a[q];
-  if (b) v += coef[E + e] * b[q];
-  if (c) v += coef[2 * E + e] * c[q];
-  out[q] = v;
-}
-
-__global__ void vec_lin3_inline_kernel(double* __restrict__ out, const double* __restrict__ a,
-                                       const double* __restrict__ b, const double* __restrict__ c,
-                                       const Coef24 coef, int64_t m, int E) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= m * E) return;
-  const int e = (int)(q % E);
-  double v = coef.v[e] * a[q];
-  if (b) v += coef.v[E + e] * b[q];
-  if (c) v += coef.v[2 * E + e] * c[q];
-  out[q] = v;
-}
 
 // ---- MINRES on the device.  State per column e (doubles): see MS_* below; five coefficient
 // triples [3E] feed vec_lin3_dev_kernel.  Same scalar arithmetic, in the same order, as the
@@ -564,66 +540,29 @@ __global__ void __launch_bounds__(CG_BLOCKS) minres_scalars_kernel(const double*
 
 int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit,
                  double* out_b, int* iters, double* resid) {
-  if (!c) return KMVP_E_INVALID;
-  if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
-  if (int rc0 = solver_shape(c)) return rc0;
-  if (!a_host || !out_b || E < 1 || maxit < 0 || !(rtol > 0)) return fail(c, KMVP_E_INVALID, "bad solver arguments");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const int64_t m = c->N;  // length of the Krylov vectors: all points
-  const size_t n = (size_t)m * E;
-  const size_t vec = n * sizeof(double);
-  int rc = ensure(c, c->scratch, 8 * vec + sizeof(double) * ((CG_BLOCKS + 3) * (size_t)E + ms_stop(E) + 2));
-  if (rc) return rc;
-  double* base = (double*)c->scratch.p;
-  double *x = base, *r1 = base + n, *r2 = base + 2 * n, *y = base + 3 * n, *v = base + 4 * n;
-  double *w = base + 5 * n, *w1 = base + 6 * n, *w2 = base + 7 * n;
-  CgWork wk;
-  wk.x = wk.r = wk.p = nullptr;
-  wk.partial = base + 8 * n;
-  wk.coef = wk.partial + (size_t)CG_BLOCKS * E;  // 3*E coefficients
-  std::vector<double> hp((size_t)CG_BLOCKS * E), dots, coef(3 * (size_t)E);
-  auto lin3 = [&](double* out, const double* pa, const double* pb, const double* pc) -> int {
-    if (E <= COEF_INLINE_E) {
-      Coef24 k;
-      for (int q = 0; q < 3 * COEF_INLINE_E; ++q) k.v[q] = q < 3 * E ? coef[q] : 0.0;
-      hipLaunchKernelGGL(vec_lin3_inline_kernel, dim3(blocks_for((int64_t)n)), dim3(256), 0, c->stream, out, pa, pb,
-                         pc, k, m, E);
-      HIP_TRY(c, hipGetLastError());
-      return KMVP_OK;
-    }
-    HIP_TRY(c, hipMemcpyAsync(wk.coef, coef.data(), sizeof(double) * 3 * E, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    hipLaunchKernelGGL(vec_lin3_kernel, dim3(blocks_for((int64_t)n)), dim3(256), 0, c->stream, out, pa, pb, pc,
-                       wk.coef, m, E);
-    HIP_TRY(c, hipGetLastError());
-    return KMVP_OK;
-  };
+  Krylov k;  // x, r1, r2, y, v, w, w1, w2; state: see MS_* above
+  if (int rc = solver_begin(c, a_host, E, rtol, maxit, out_b, 8, ms_stop(E), k)) return rc;
+  SolveGuard guard{c};
+  const int64_t m = k.m;
+  const size_t vec = k.n * sizeof(double);
+  double *x = k.vec(0), *r1 = k.vec(1), *r2 = k.vec(2), *y = k.vec(3), *v = k.vec(4);
+  double *w = k.vec(5), *w1 = k.vec(6), *w2 = k.vec(7), *st = k.state;
 
   // r1 = r2 = y = a (widened), x = w = w2 = 0
-  rc = ensure(c, c->b_raw, n * elem_size(c->dtype));
+  int rc = load_rhs(c, a_host, y, k);
   if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->b_raw.p, a_host, n * elem_size(c->dtype), hipMemcpyHostToDevice, c->stream));
-  if (c->dtype == KMVP_F64)
-    hipLaunchKernelGGL((cg_widen_kernel<double>), dim3(blocks_for((int64_t)n)), dim3(256), 0, c->stream,
-                       (const double*)c->b_raw.p, y, (int64_t)n);
-  else
-    hipLaunchKernelGGL((cg_widen_kernel<float>), dim3(blocks_for((int64_t)n)), dim3(256), 0, c->stream,
-                       (const float*)c->b_raw.p, y, (int64_t)n);
-  HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(r1, y, vec, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(r2, y, vec, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipMemsetAsync(x, 0, vec, c->stream));
   HIP_TRY(c, hipMemsetAsync(w, 0, vec, c->stream));
   HIP_TRY(c, hipMemsetAsync(w2, 0, vec, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if ((rc = cg_dots(c, y, y, m, E, wk, hp, dots))) return rc;
+  std::vector<double> dots;
+  if ((rc = cg_dots(c, y, y, k, dots))) return rc;
 
   // ---- device-resident recurrence (see minres_scalars_kernel); the host rotates buffer pointers and
   // looks at the residual every CG_CHECK iterations
-  std::vector<double> beta1(E);
-  double* st = wk.coef + 3 * (size_t)E;
-  const size_t st_len = ms_stop(E) + 2;
-  std::vector<double> state(st_len, 0.0);
+  std::vector<double> beta1(E), state(k.stop + 2, 0.0);
   for (int e = 0; e < E; ++e) {
     beta1[e] = std::sqrt(dots[e]);
     state[(size_t)MS_BETA1 * E + e] = beta1[e];
@@ -635,10 +574,10 @@ int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol
     state[ms_triple(E, 0) + e] = (!zero_rhs) ? 1.0 / beta1[e] : 0.0;  // T0 = (1/beta, 0, 0)
     state[ms_triple(E, 1) + e] = 1.0;                                   // T1 = (1, 0, 0): no r1 term in iteration 1
   }
-  HIP_TRY(c, hipMemcpyAsync(st, state.data(), sizeof(double) * st_len, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(st, state.data(), sizeof(double) * state.size(), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const double* stop = st + ms_stop(E);
-  const unsigned vb = blocks_for((int64_t)n);
+  const double* stop = st + k.stop;
+  const unsigned vb = blocks_for((int64_t)k.n);
   auto worst = [&]() {
     double wv = 0.0;
     for (int e = 0; e < E; ++e) {
@@ -652,28 +591,19 @@ int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol
     hipLaunchKernelGGL(vec_lin3_dev_kernel, dim3(vb), dim3(256), 0, c->stream, out, pa, pb, pc,
                        st + ms_triple(E, triple), stop, m, E, (double*)nullptr);
   };
-
-  int it = 0;
-  double rel = worst();
-  c->async_product = true;
-  dlin3(v, y, nullptr, nullptr, 0);  // v = y / beta of the first iteration
-  while (it < maxit && rel > rtol) {
-    const int burst = std::min(CG_CHECK, maxit - it);
-    for (int k = 0; k < burst; ++k) {
-      // (v = y / beta was written by the previous iteration's tail, or before the loop)
-      if ((rc = cg_apply(c, kernel, v, m, E))) {
-        c->async_product = false;
-        return rc;
-      }
+  auto body = [&](int burst) -> int {
+    for (int i = 0; i < burst; ++i) {
+      // (v = y / beta was written by the previous iteration's tail, or before the first burst)
+      if (int rcb = cg_apply(c, kernel, v, k)) return rcb;
       dlin3(y, (const double*)c->out.p, r1, nullptr, 1);  // y = K v - (beta / oldb) r1
-      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, v, y, m, E, wk.partial);
-      hipLaunchKernelGGL(minres_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, wk.partial, st, E, 1, rtol);
+      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, v, y, m, E, k.partial);
+      hipLaunchKernelGGL(minres_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, st, E, 1, rtol);
       // y - (alfa / beta) r2, written into the old r1 buffer AND back into y
       hipLaunchKernelGGL(vec_lin3_dev_kernel, dim3(vb), dim3(256), 0, c->stream, r1, (const double*)y, (const double*)r2,
                          (const double*)nullptr, st + ms_triple(E, 2), stop, m, E, y);
       std::swap(r1, r2);             // r1 <- r2, r2 <- the new vector
-      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, r2, r2, m, E, wk.partial);
-      hipLaunchKernelGGL(minres_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, wk.partial, st, E, 2, rtol);
+      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, r2, r2, m, E, k.partial);
+      hipLaunchKernelGGL(minres_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, st, E, 2, rtol);
       {  // w_new = (v - oldeps w1 - delta w2) / gamma with w1 <- w2, w2 <- w
         double* t = w1;
         w1 = w2;
@@ -684,55 +614,23 @@ int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol
       hipLaunchKernelGGL(minres_tail_kernel, dim3(vb), dim3(256), 0, c->stream, w, v, (const double*)w1, (const double*)w2, x,
                          (const double*)y, st + ms_triple(E, 3), st + ms_triple(E, 4), st + ms_triple(E, 0), stop, m, E);
     }
-    hipError_t le = hipGetLastError();
-    if (le == hipSuccess) le = hipMemcpyAsync(state.data(), st, sizeof(double) * st_len, hipMemcpyDeviceToHost, c->stream);
-    if (le == hipSuccess) le = hipStreamSynchronize(c->stream);
-    if (le != hipSuccess) {
-      c->async_product = false;
-      HIP_TRY(c, le);
-    }
-    it = (int)state[ms_stop(E) + 1];
-    rel = worst();
-    if (state[ms_stop(E)] != 0.0) break;
-  }
-  c->async_product = false;
+    return KMVP_OK;
+  };
+
+  int it = 0;
+  double rel = worst();
+  dlin3(v, y, nullptr, nullptr, 0);  // v = y / beta of the first iteration
+  if ((rc = run_bursts(c, k, maxit, rtol, it, rel, state, body, worst, nullptr))) return rc;
 
   // true residual ||a - K x|| / ||a||
-  if ((rc = cg_apply(c, kernel, x, m, E))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->b_raw.p, a_host, n * elem_size(c->dtype), hipMemcpyHostToDevice, c->stream));
-  if (c->dtype == KMVP_F64)
-    hipLaunchKernelGGL((cg_widen_kernel<double>), dim3(blocks_for((int64_t)n)), dim3(256), 0, c->stream,
-                       (const double*)c->b_raw.p, v, (int64_t)n);
-  else
-    hipLaunchKernelGGL((cg_widen_kernel<float>), dim3(blocks_for((int64_t)n)), dim3(256), 0, c->stream,
-                       (const float*)c->b_raw.p, v, (int64_t)n);
-  HIP_TRY(c, hipGetLastError());
-  for (int e = 0; e < E; ++e) {
-    coef[e] = 1.0;
-    coef[E + e] = -1.0;
-  }
-  if ((rc = lin3(v, v, (const double*)c->out.p, nullptr))) return rc;
-  if ((rc = cg_dots(c, v, v, m, E, wk, hp, dots))) return rc;
+  if ((rc = true_residual(c, kernel, a_host, x, v, k, dots))) return rc;
   double true_rel = 0.0;
   for (int e = 0; e < E; ++e) {
     if (beta1[e] == 0.0) continue;
     const double v = std::sqrt(dots[e]) / beta1[e];
     if (!(v <= true_rel)) true_rel = v;  // NaN propagates
   }
-
-  HIP_TRY(c, hipMemcpyAsync(out_b, x, vec, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->have_signal = false;
-  if (iters) *iters = it;
-  if (resid) *resid = true_rel;
-  // the verdict is on the TRUE residual ||a - K x|| / ||a|| (include/kmvp.h), with 1.5x slack for the rounding
-  // between it and the recurrence the iteration stops on; a non-finite residual is never a success
-  if (!(std::isfinite(true_rel) && true_rel <= rtol * 1.5)) {
-    c->err = std::isfinite(true_rel) ? "MINRES stopped before the true residual reached the requested tolerance"
-                                     : "MINRES: the residual is not finite (non-finite operator or right-hand side)";
-    return KMVP_E_NOT_CONVERGED;
-  }
-  return KMVP_OK;
+  return solver_end(c, "MINRES", x, k, out_b, it, true_rel, rtol, iters, resid);
 }
 
 }  // namespace kmvp

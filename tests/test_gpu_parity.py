@@ -1987,9 +1987,9 @@ def test_cg_solver_reaches_the_residual(expected):
 
 def test_minres_solver_on_the_references_sphere_datasets():
     """solver-sphere-*-inverse-distance (datasets.py:393-399): symmetric indefinite matrix -> MINRES."""
-    for n in (500, 2000):
+    for n, E in ((500, 2), (2000, 2), (500, 12)):
         y = kmvp_oracle.uniform_sphere_points(n)
-        b_true = np.random.RandomState(n).randn(n, 2)
+        b_true = np.random.RandomState(n).randn(n, E)
         a = kmvp_oracle.product(kernel="inverse-distance", source_points=y, source_signal=b_true)
         algo = MI355XSolver(kernel="inverse-distance", dimension=3, precision=np.float64, rtol=1e-8, maxit=20000)
         try:
@@ -2002,10 +2002,35 @@ def test_minres_solver_on_the_references_sphere_datasets():
         finally:
             algo.done()
         res = kmvp_oracle.relative_residual(kernel="inverse-distance", source_points=y, solution=sol, target_signal=a)
-        assert info["cg_converged"] and res <= 2e-8, (n, res, info)
+        assert info["cg_converged"] and res <= 2e-8, (n, E, res, info)
         # this matrix is well conditioned enough for the iterate to match the dense lstsq answer
         ref = kmvp_oracle.solve(kernel="inverse-distance", source_points=y, target_signal=a)
         assert np.max(np.abs(sol - ref)) <= 1e-5 * np.max(np.abs(ref)), np.max(np.abs(sol - ref))
+
+
+def test_cg_solver_with_twelve_right_hand_sides():
+    """More than eight columns in one CG solve (Gaussian, float64).  The 64-point case: the recurrence residual of a
+    larger Gaussian system is far from monotonic, and twelve columns seldom meet 1e-8 at the same iteration."""
+    case = golden_cases.solver_cases()[0]
+    y, _ = golden_cases.make_solver_inputs(case)
+    a = kmvp_oracle.product(kernel="gaussian", source_points=y, source_signal=np.random.RandomState(12).randn(case["n"], 12))
+    algo = MI355XSolver(kernel="gaussian", dimension=3, precision=np.float64, rtol=1e-8, maxit=5000)
+    try:
+        algo.prepare_data(source_points=y)
+        algo.fit()
+        algo.prepare_query(target_signal=a)
+        algo.query()
+        sol = algo.get_result()
+        info = algo.get_additional()
+    finally:
+        algo.done()
+    assert sol.shape == a.shape and sol.dtype == np.float64
+    # the solver reports its worst column
+    res = max(kmvp_oracle.relative_residual(kernel="gaussian", source_points=y, solution=sol[:, [e]], target_signal=a[:, [e]])
+              for e in range(12))
+    assert info["cg_converged"], info
+    assert res <= 2e-8, (res, info)
+    assert abs(res - info["cg_relative_residual"]) <= 1e-9
 
 
 def test_cg_solver_config5_shape_small():
