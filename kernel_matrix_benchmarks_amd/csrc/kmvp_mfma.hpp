@@ -344,6 +344,11 @@ __global__ void __launch_bounds__(BLOCK_THREADS) mfma_kernel(const MfmaArgs a) {
 
       // ---- 2. kernel values on the VALU; target on the lane, 16 sources in registers
       if constexpr (DOT) {  // (kmvp_mfma.hpp "the per-target running shift")
+        // mfma_tile_max reads s in inline asm, which the compiler does not check against the MFMA that is still writing
+        // s: without a compiler-visible read first, v_min3 / v_max3 took stale registers right behind the MFMA and the
+        // shift missed tiles (targets far from every source came back 0 or NaN).  The canonicalize (one v_max_f32, an
+        // identity here) is that read: the XDL-write-to-VALU-read wait states are inserted ahead of it.
+        s[0] = __builtin_canonicalizef(s[0]);
         if (unset[w] || __any(mfma_tile_max<mfma_sgn<KERNEL>()>(s) > MFMA_DOT_LIMIT_LOG2)) {  // wave-uniform, rare after the first tile
           mfma_dot_event<NT, mfma_sgn<KERNEL>()>(unset[w], s, o[w], den[w], msh[w], xb[w][KS - 1], &dscr[wave][0], r, h);
           unset[w] = false;

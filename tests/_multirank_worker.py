@@ -16,6 +16,8 @@ for p in (HERE, os.path.join(HERE, "..", "oracle"), os.path.join(HERE, "..")):
 
 import numpy as np  # noqa: E402
 
+C_BF16 = 1.2011224087864498  # sqrt(log2 e): the bf16 Gaussian's / exp(<x,y>)'s coordinate scale
+
 
 def main():
     from kernel_matrix_benchmarks_amd import _lib, sharding
@@ -24,6 +26,7 @@ def main():
     import torch.distributed as dist
 
     import kmvp_oracle
+    from kmvp_bf16_model import bf16_round
     from kernel_matrix_benchmarks_amd.algorithms.mi355x import MI355XProduct, MI355XSolver
 
     dist.init_process_group("gloo")
@@ -88,13 +91,7 @@ def main():
             algo.done()
         ys, xs = y, x
         if precision == "bfloat16":  # the truth on the operands the kernel multiplies (points x sqrt(log2 e), rounded to bf16)
-            c = 1.2011224087864498
-
-            def bf16(a):  # ONE float32 product, as the packing kernel forms it, rounded to bf16, divided by c again
-                u = (np.ascontiguousarray(a, dtype=np.float32) * np.float32(c)).view(np.uint32)
-                return ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32).astype(np.float64) / c
-
-            ys, xs = bf16(y), bf16(x)
+            ys, xs = bf16_round(y, C_BF16), bf16_round(x, C_BF16)
         want = kmvp_oracle.exp_dot_product(source_points=ys, target_points=xs, source_signal=b, normalize_rows=normalize)
         mass = want if normalize else kmvp_oracle.exp_dot_product(source_points=ys, target_points=xs, source_signal=np.abs(b))
         scale = np.max(np.abs(mass), axis=1, keepdims=True)
@@ -108,11 +105,6 @@ def main():
     # the bf16 Gaussian with targets far from every source, sharded: the ranks' shifts differ (sources sorted by distance), the
     # exponents are merged by all-reduce(min) exactly as for exp(<x,y>)
     rs = np.random.RandomState(6)
-    c = 1.2011224087864498
-
-    def bf16r(a):
-        u = (np.ascontiguousarray(a, dtype=np.float32) * np.float32(c)).view(np.uint32)  # ONE float32 product, as the kernel forms it
-        return ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32).astype(np.float64) / c
 
     y = rs.rand(3001, 32) / np.sqrt(32 / 3.0)
     x = rs.rand(400, 32) / np.sqrt(32 / 3.0) + 14.0 / np.sqrt(32)
@@ -129,8 +121,8 @@ def main():
             meta = algo.get_additional()
         finally:
             algo.done()
-        want = kmvp_oracle.product(kernel="gaussian", source_points=bf16r(y), target_points=bf16r(x), source_signal=b, normalize_rows=normalize)
-        mass = kmvp_oracle.product(kernel="gaussian", source_points=bf16r(y), target_points=bf16r(x), source_signal=np.abs(b),
+        want = kmvp_oracle.product(kernel="gaussian", source_points=bf16_round(y, C_BF16), target_points=bf16_round(x, C_BF16), source_signal=b, normalize_rows=normalize)
+        mass = kmvp_oracle.product(kernel="gaussian", source_points=bf16_round(y, C_BF16), target_points=bf16_round(x, C_BF16), source_signal=np.abs(b),
                                    normalize_rows=normalize)
         e = float(np.max(np.abs(got - want) / mass))
         assert "online shift" in meta["dispatch_note"] and meta["rccl_ranks"] == world, meta

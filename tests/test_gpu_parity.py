@@ -17,6 +17,7 @@ import c_oracle
 import golden_cases
 import kmvp_oracle
 from conftest import rel_err
+from kmvp_bf16_model import bf16_round
 from kernel_matrix_benchmarks_amd import _lib
 from kernel_matrix_benchmarks_amd.algorithms.mi355x import MI355XProduct, MI355XSolver
 
@@ -266,20 +267,6 @@ def test_exp_dot_native_kernel_has_no_range_limit():
             algo.prepare_data(source_points=rs.randn(100, 70) * 2.0, target_points=rs.randn(10, 70), same_points=False)
         finally:
             algo.done()
-
-
-def bf16_round(a, c=None):
-    """What the bf16 packing kernels make of the plugin's float32 inputs, as float64: (float32 a) x (float32 c) -- ONE float32
-    product, as the kernel forms it -- rounded to the nearest bfloat16 (ties to even), then divided by c again.  (Multiplying in
-    float64 instead lands on the other side of a bf16 rounding boundary for about one operand in a million, and a logit of
-    ~1000 then moves by half a unit: a one-row artefact of the emulation that looked like a kernel defect.)"""
-    v = np.ascontiguousarray(a, dtype=np.float32)
-    if c is not None:
-        v = v * np.float32(c)
-    u = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32)
-    r = u.view(np.float32).astype(np.float64)
-    return r if c is None else r / c
 
 
 def test_exp_dot_bfloat16_native_kernel_with_online_shift():

@@ -11,6 +11,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 from kernel_matrix_benchmarks_amd.algorithms.mi355x import MI355XProduct  # noqa: E402
 import kmvp_oracle  # noqa: E402  (checker only)
+from kmvp_bf16_model import bf16_round  # noqa: E402
 
 KERNELS = ("gaussian", "absolute-exponential", "inverse-distance")
 FORMS = (None, None, False, True, "centred", "cells", "cells-valu")
@@ -178,12 +179,7 @@ def check_exp_dot(c, got, y, x, b, rows):
         xt = xt[rows]
     if c["precision"] == "bfloat16":  # the truth on the operands the kernel multiplies: points x sqrt(log2 e), rounded to bf16
         k = 1.2011224087864498
-
-        def bf16(a, c):  # ONE float32 product, as the packing kernel forms it, then round-to-nearest-even to bf16
-            u = (np.ascontiguousarray(a, dtype=np.float32) * np.float32(c)).view(np.uint32)
-            return ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32).astype(np.float64) / c
-
-        y, xt = bf16(y, k), bf16(xt, k)
+        y, xt = bf16_round(y, k), bf16_round(xt, k)
     with np.errstate(over="ignore", invalid="ignore"):
         want = kmvp_oracle.exp_dot_product(source_points=y, target_points=xt, source_signal=b, normalize_rows=c["norm"])
         # the yardstick of a row is its mass: sum_j k |b_j|, or the weighted mean of |b| for a softmax row (means of both signs cancel)

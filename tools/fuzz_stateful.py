@@ -2,7 +2,9 @@
 option changes / products of DIFFERENT kernel functions, and every product is checked against the float64 numpy oracle.
 What it is after: stale packed layouts, buffers sized for an earlier shape, shifts / exponents / cell lists left over from
 another kernel function -- anything a caller of include/kmvp.h can reach by calling the entry points in an unusual order.
-usage: python tools/fuzz_stateful.py [contexts=30] [steps=40] [seed=1]"""
+bfloat16 products are held to the float64 model of the kernels' own arithmetic (oracle/kmvp_bf16_model.py) on up to
+MODEL_ROWS rows, every element within the model's band.
+usage: python tools/fuzz_stateful.py [contexts=30] [steps=40] [seed=1] [precision=random]"""
 import os
 import sys
 
@@ -13,30 +15,19 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 from kernel_matrix_benchmarks_amd import _lib  # noqa: E402
 import kmvp_oracle  # noqa: E402  (checker only)
+from kmvp_bf16_model import bf16_round, mfma_product  # noqa: E402  (checker only)
 
 KERNELS = ("gaussian", "absolute-exponential", "inverse-distance", "exp-dot")
-C_DOT = 1.2011224087864498
-
-
-def bf16(a, c):
-    """(float32 a) x (float32 c) as ONE float32 product -- what the packing kernels form -- rounded to bf16, divided by c again"""
-    u = (np.ascontiguousarray(a, dtype=np.float32) * np.float32(c)).view(np.uint32)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32).astype(np.float64) / c
+MODEL_ROWS = 256
 
 
 def truth(kernel, y, x, b, norm, precision):
     if kernel == "exp-dot":
         ys, xs = y, (y if x is None else x)
-        if precision == "bfloat16":
-            ys, xs = bf16(ys, C_DOT), bf16(xs, C_DOT)
         with np.errstate(over="ignore", invalid="ignore"):
             want = kmvp_oracle.exp_dot_product(source_points=ys, target_points=xs, source_signal=b, normalize_rows=norm)
             mass = kmvp_oracle.exp_dot_product(source_points=ys, target_points=xs, source_signal=np.abs(b), normalize_rows=norm)
         return want, mass, None
-    if precision == "bfloat16":  # the operands the kernel multiplies: points x the kernel's constant, rounded to bf16
-        k = {"gaussian": C_DOT, "absolute-exponential": 1.4426950408889634, "inverse-distance": 1.0}[kernel]
-        y = bf16(y, k)
-        x = None if x is None else bf16(x, k)
     want = kmvp_oracle.product(kernel=kernel, source_points=y, target_points=x, source_signal=b, normalize_rows=norm)
     # the yardstick of a row is its mass sum_j k |b_j| (normalised rows: the weighted mean of |b|): sums of both signs cancel
     mass = kmvp_oracle.product(kernel=kernel, source_points=y, target_points=x, source_signal=np.abs(b), normalize_rows=norm)
@@ -44,8 +35,27 @@ def truth(kernel, y, x, b, norm, precision):
     return want, mass, den.reshape(len(den), -1)[:, 0]
 
 
-def one_context(rs, steps, verbose):
-    precision = ["float32", "float32", "float64", "bfloat16"][rs.randint(4)]
+def check_bf16(kernel, y, x, b, norm, got):
+    """A bfloat16 product against the model of its arithmetic on up to MODEL_ROWS rows: (rows checked, worst err / band)."""
+    N = len(y) if x is None else len(x)
+    rows = np.sort(np.random.RandomState(N).choice(N, MODEL_ROWS, replace=False)) if N > MODEL_ROWS else np.arange(N)
+    # the bf16 Gaussian with targets != sources takes the per-target shift (no mfma_variant is set here)
+    fn = "gaussian-shifted" if kernel == "gaussian" and x is not None else kernel
+    m = mfma_product(fn, y, x, b, norm, rows=rows)
+    ok = ~m.flagged & ~m.nonfinite
+    if not ok.any():
+        return 0, 0.0
+    if not np.isfinite(got[rows][ok]).all():
+        return int(ok.sum()), np.inf
+    err = np.abs(got[rows][ok] - m.value[ok])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        worst = float(np.max(np.where(err > 0, err / m.band[ok], 0.0)))
+    return int(ok.sum()), worst
+
+
+def one_context(rs, steps, verbose, precision=None):
+    draw = ["float32", "float32", "float64", "bfloat16"][rs.randint(4)]
+    precision = precision or draw
     code, host = _lib.dtype_code(precision)
     ctx = _lib.Context(0)
     failures, done = [], 0
@@ -94,6 +104,13 @@ def one_context(rs, steps, verbose):
                     continue
                 got = ctx.get_result(state["N"], state["E"])
                 kname = ctx.last_kernel_name
+                if precision == "bfloat16":
+                    _, worst = check_bf16(kernel, y, x, b, norm, got)
+                    done += 1
+                    if worst > 1.0:
+                        failures.append(f"step {step} {precision} {kernel} norm={norm} {state} -> {kname}: error {worst:.3g} x the "
+                                        "model's band")
+                    continue
                 want, mass, den = truth(kernel, y, x, b, norm, precision)
                 live = np.isfinite(want).all(axis=1) & np.isfinite(mass).all(axis=1)
                 if precision != "float64":
@@ -109,7 +126,7 @@ def one_context(rs, steps, verbose):
                     failures.append(f"step {step} {precision} {kernel} norm={norm} {state} -> {kname}: non-finite rows")
                     continue
                 err = float((np.abs(got[live] - want[live]) / np.maximum(np.abs(mass[live]), 1e-300)).max())
-                tol = {"float64": 1e-10, "float32": 2e-4 if kernel == "inverse-distance" else 5e-5, "bfloat16": 2e-2}[precision]
+                tol = {"float64": 1e-10, "float32": 2e-4 if kernel == "inverse-distance" else 5e-5}[precision]
                 if err > tol:
                     failures.append(f"step {step} {precision} {kernel} norm={norm} {state} -> {kname}: error {err:.3e} > {tol:.0e}")
     finally:
@@ -120,16 +137,23 @@ def one_context(rs, steps, verbose):
     return done, failures
 
 
+def sweep(contexts, steps, seed, precision=None, verbose=True):
+    """contexts random contexts of steps steps each: (products checked, failures)."""
+    rs = np.random.RandomState(seed)
+    total, bad = 0, []
+    for c in range(contexts):
+        done, failures = one_context(rs, steps, verbose, precision)
+        total += done
+        bad += failures
+        if verbose and (c + 1) % 10 == 0:
+            print(f"... {c + 1} contexts, {total} products checked, {len(bad)} failures", flush=True)
+    return total, bad
+
+
 if __name__ == "__main__":
     contexts = int(sys.argv[1]) if len(sys.argv) > 1 else 30
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 40
-    rs = np.random.RandomState(int(sys.argv[3]) if len(sys.argv) > 3 else 1)
-    total, bad = 0, []
-    for c in range(contexts):
-        done, failures = one_context(rs, steps, True)
-        total += done
-        bad += failures
-        if (c + 1) % 10 == 0:
-            print(f"... {c + 1} contexts, {total} products checked, {len(bad)} failures", flush=True)
+    seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    total, bad = sweep(contexts, steps, seed, sys.argv[4] if len(sys.argv) > 4 else None)
     print(f"{contexts} contexts, {total} products checked, {len(bad)} failures")
     sys.exit(1 if bad else 0)
