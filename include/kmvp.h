@@ -113,8 +113,11 @@ int kmvp_invdist_norm(kmvp_ctx* ctx);
  * accuracy, kmvp_fastmm.hpp; bfloat16: plain bf16 operands and a bf16 second product, kmvp_mfma.hpp), the kernel values are
  * taken relative to a per-target running exponent (flash-attention recurrence with integer exponents) and leave the pair
  * loop as (mantissa sums, exponent) pairs, so that
- *   kmvp_expdot_norm  softmax attention  a_i = sum_j e^<x_i,y_j> b_j / sum_j e^<x_i,y_j>   has NO range limit on <x, y>;
+ *   kmvp_expdot_norm  softmax attention  a_i = sum_j e^<x_i,y_j> b_j / sum_j e^<x_i,y_j>   never forms e^max<x,y>;
  *   kmvp_expdot       plain product: overflows to inf exactly where exp(<x, y>) leaves the float64 range.
+ * Range: the exponent is an integer clamped at +-32000 binades, so a row's largest logit must stay below
+ * 32000 ln 2 ~ 2.2e4 (row-normalised: above -2.2e4 as well); a product with such a row fails with KMVP_E_UNSUPPORTED
+ * instead of returning inf / NaN rows.
  * Sharded: all-reduce(min) of the exponents, then the usual all-reduce(sum).  Other dtypes / D: KMVP_E_UNSUPPORTED
  * (the plugin then uses the Gaussian identity, with its range check). */
 int kmvp_expdot(kmvp_ctx* ctx);

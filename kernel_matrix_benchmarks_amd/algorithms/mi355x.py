@@ -32,8 +32,9 @@ SUPPORTED_KERNELS = ("gaussian", "absolute-exponential", "inverse-distance", "ex
 # unpinned, checked against a direct numpy evaluation only (the tests' exp_dot_product).  Two routes:
 #  * NATIVE (float32 / float16 inputs at D <= 64, bfloat16 at D <= 141; include/kmvp.h kmvp_expdot[_norm]): S = X Y^T
 #    straight from the matrix cores, kernel values relative to a per-target running exponent (the flash-attention
-#    recurrence), partial sums merged as (mantissa, exponent) pairs -- softmax attention has NO range limit on
-#    <x, y>; plain products overflow where exp(<x, y>) leaves float64, as numpy's would.
+#    recurrence), partial sums merged as (mantissa, exponent) pairs -- softmax attention never forms exp(max logit),
+#    up to |largest logit| < 32000 ln 2 ~ 2.2e4 (the clamp of the integer exponent; beyond it the library refuses the
+#    product); plain products overflow where exp(<x, y>) leaves float64, as numpy's would.
 #  * IDENTITY (float64, float32 at D > 64, and the solver):
 #        exp(<x, y>) = exp(|x|^2 / 2) * exp(-|x/sqrt2 - y/sqrt2|^2) * exp(|y|^2 / 2)
 #    i.e. a GAUSSIAN product on the points / sqrt(2) with the signal weighted by w_j = exp(|y_j|^2/2 - c)
@@ -141,7 +142,7 @@ class MI355XProduct(BaseProduct):
                 raise NotImplementedError(
                     f"exp-dot through the Gaussian identity: |y_j|^2/2 spans {spread:.4g} > {budget:g}; sources of small norm "
                     f"would silently get weight 0 in {_precision_name(self.precision)}.  Use precision='float32' with D <= "
-                    f"{EXPDOT_NATIVE_MAX_D} (native online-max kernel, no range limit) or float64 (spread <= "
+                    f"{EXPDOT_NATIVE_MAX_D} (native online-max kernel, logits up to ~2.2e4) or float64 (spread <= "
                     f"{EXPDOT_IDENTITY_SPREAD['float64']:g}).")
             self._w = np.exp(hy - shift).reshape(-1, 1)   # source weights, <= 1
             self._hx = hx + shift                         # log of the target factor exp(|x|^2/2 + c)

@@ -121,6 +121,7 @@ struct kmvp_ctx {
   DevBuf part, sums, out;       // fp64 partials, reduced sums, final (N,E)
   DevBuf xchg;                  // sharded runs: sums in the canonical unpadded layout [column][N] for the all-reduce
   DevBuf kexp, kshift, xchgk;   // exp(<x,y>): exponents per (segment, target) / per target / per target after the all-reduce(min)
+  DevBuf kflag;                 // exp(<x,y>): set when a row's exponent reached the shift's clamp (check_shift_range_kernel)
   DevBuf scratch;               // CG vectors / dot products
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold

@@ -48,7 +48,8 @@
 //    loses is below 2^-40 of the row's largest term.
 // The partial sums leave as fp64 at the true scale (x 2^-kop), or -- exp(<x,y>), FastmmArgs::kexp -- at the scale
 // 2^-kop together with kop per (segment, target), for a reduction that never forms exp(max logit)
-// (reduce_shifted_kernel in kmvp_product.hip: "no range limit" for row-normalised attention).
+// (reduce_shifted_kernel in kmvp_product.hip).  The range is that of kop: |largest logit| < 32000 ln 2 ~ 2.2e4; a row
+// whose shift reaches the clamp is reported as an error (check_shift_range_kernel), not returned as inf / NaN.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -289,13 +290,19 @@ __global__ void __launch_bounds__(BLOCK_THREADS) fastmm_kernel(const FastmmArgs 
           const bool first = s == s_begin && q == 0;
           // (half a binade of hysteresis: T up to 2^15.5 < 65504 is still an f16 number, and the rounding noise of s at
           // nearly coincident points must not lower the shift of every such target by one)
-          const bool need = (first || (KERNEL == K_ABSEXP ? m < kop[tt] - 0.5f : m < -((float)FMM_SHIFT + 0.5f))) && m < 3.0e38f;
+          // (a NaN target -- m NaN -- still takes its first tile: kset, so that its NaN sums reach reduce_shifted_kernel
+          // instead of a segment "without live sources"; its shift stays where it was)
+          const bool need = ((first || (KERNEL == K_ABSEXP ? m < kop[tt] - 0.5f : m < -((float)FMM_SHIFT + 0.5f))) && m < 3.0e38f) ||
+                            (KERNEL != K_ABSEXP && first && m != m);
           if (__any(need)) {  // rare: see the header
             fold_one(tt);  // (this tile's accumulator only: a target's sums do not depend on what else its wave owns)
             if (need) {
               float kn;
               if constexpr (KERNEL == K_ABSEXP) kn = floorf(m);
-              else kn = fminf(fmaxf(kop[tt] + floorf(m + (float)FMM_SHIFT), -FMM_MAX_ONLINE_SHIFT), FMM_MAX_ONLINE_SHIFT);
+              else {
+                const float kraw = kop[tt] + floorf(m + (float)FMM_SHIFT);  // NaN for a NaN target: its shift stays put
+                kn = kraw == kraw ? fminf(fmaxf(kraw, -FMM_MAX_ONLINE_SHIFT), FMM_MAX_ONLINE_SHIFT) : kop[tt];
+              }
               const float delta = kop[tt] - kn;  // >= 0 except at the first tile
               if constexpr (KERNEL != K_ABSEXP) {
 #pragma unroll

@@ -334,6 +334,18 @@ int finish_product(kmvp_ctx* c, int64_t count, int64_t N, int64_t n_pad, int E, 
 // Tail of the exp(<x,y>) path: c->sums [NE][n_pad] at the per-target scale 2^-K_i with K in c->kshift [n_pad].  Sharded:
 // the ranks first agree on K (all-reduce MIN: the flash-attention (m, l, o) merge with m an integer exponent), move their
 // sums to it, and then take the common tail (all-reduce SUM, normalise).
+// The per-target exponent is clamped at +-FMM_MAX_ONLINE_SHIFT binades (= MFMA_DOT_MAX_SHIFT: what the two bf16 operand
+// columns of the shift hold).  A row whose exponent reached the clamp has its largest logit at or beyond
+// 32000 ln 2 ~ 2.2e4 (its values overflow the f16 / bf16 pieces: inf or NaN), or -- row-normalised -- every logit at or
+// below -2.2e4 (all its values underflow: 0 / 0).  flag = 1 for such a row (a plain row of tiny logits is 0, rightly).
+static_assert(FMM_MAX_ONLINE_SHIFT == MFMA_DOT_MAX_SHIFT, "one shift range for both native exp(<x,y>) paths");
+__global__ void check_shift_range_kernel(const double* __restrict__ kshift, int64_t n, int normalise, int* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double k = kshift[i];  // +inf: no source at all; a NaN row keeps a finite, unclamped exponent
+  if (k <= -(double)FMM_MAX_ONLINE_SHIFT || (normalise && k >= (double)FMM_MAX_ONLINE_SHIFT && k < 1.0e300)) *flag = 1;
+}
+
 int finish_product_shifted(kmvp_ctx* c, int64_t N, int64_t n_pad, int E, int sig) {
   const int NE = sig == SIG_NORM ? E + 1 : E;
   int rc;
@@ -347,7 +359,27 @@ int finish_product_shifted(kmvp_ctx* c, int64_t N, int64_t n_pad, int E, int sig
     HIP_TRY(c, hipGetLastError());
     kshift = (const double*)c->xchgk.p;
   }
-  return finish_product(c, (int64_t)NE * n_pad, N, n_pad, E, sig, kshift);
+  // the range of the shift (check_shift_range_kernel): an error, never inf / NaN rows as a result.  (Asynchronous
+  // products -- the solvers' inner operator -- leave no point to report it at: unchecked.)
+  const bool check = !c->async_product && N > 0;
+  if (check) {
+    if ((rc = ensure(c, c->kflag, 256))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->kflag.p, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(check_shift_range_kernel, dim3(blocks_for(N)), dim3(256), 0, c->stream, kshift, N,
+                       sig == SIG_NORM ? 1 : 0, (int*)c->kflag.p);
+    HIP_TRY(c, hipGetLastError());
+  }
+  if ((rc = finish_product(c, (int64_t)NE * n_pad, N, n_pad, E, sig, kshift))) return rc;
+  if (check) {
+    int flag = 0;
+    HIP_TRY(c, hipMemcpyAsync(&flag, c->kflag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (flag)
+      return fail(c, KMVP_E_UNSUPPORTED,
+                  "exp(<x,y>): a row's logits reach the native kernels' range |<x, y>| < 32000 ln 2 ~ 2.2e4 (the per-target "
+                  "exponent is clamped at 32000 binades); scale the inputs down");
+  }
+  return KMVP_OK;
 }
 
 // Epilogue of the paths with fp64 partials [segment][column][n_pad] in c->part.  Without a

@@ -1,0 +1,272 @@
+"""Float64 model of the float32 matrix-core products with several signal columns -- TEST INFRASTRUCTURE ONLY.
+
+fastmm_kernel (kmvp_fastmm.hpp: Gaussian, exp(-r), and exp(<x,y>) on the Gaussian build) and cfastmm_kernel
+(kmvp_cfastmm.hpp: Gaussian, exp(-r), 1/r) are float32 paths: the caller's float32 inputs are not rounded to a coarser
+type, so the model's value is the float64 product of those inputs, and the band bounds per element what the kernels'
+arithmetic may add to it.  Every term is an upper bound derived from the code; none is fitted to kernel output.
+
+Arithmetic of the kernels and the bound of each step (u = 2^-24, U = 2^-23: one fp32 ulp, any rounding mode):
+
+* operands (pack_fastmm_targets_kernel, pack_fastmm_rows_kernel): x' = f32(f32(x - c) scale), c the midpoint of the
+  clouds' bounding box (measure_clouds), scale = log2 e (exp(-r)) or sqrt(log2 e) (Gaussian, scale_for); each
+  coordinate split three ways into bf16 (fast_split3), the fp32 norm |x'|^2 (summed in double, rounded once) split the
+  same way.  Two roundings per coordinate: |x'_d - (x_d - c_d) scale| <= 2u |x'_d|, so the expanded S moves by at most
+  4u sqrt(s) (|x'| + |y'|) (Cauchy-Schwarz over d).  The split keeps 24 bits: the three dropped cross products
+  (x_m y_l, x_l y_m, x_l y_l) are below 2^-25 |x'_d y'_d| each -> U sum_d |x'_d y'_d| with the factor 2 of the rows;
+  the norm's rounding and split residual: (u + 2^-27) (|x'|^2 + |y'|^2).
+  exp(<x,y>): targets unscaled and uncentred, the rows hold -2 f32(y scale) with scale = f32(log2 e / 2): the product
+  S = -log2 e <x, y> moves by 2u log2 e sum_d |x_d y_d| (the f32 product and the f32 constant).
+* S from the bf16 MFMAs: KD = 16 KS exact products (bf16 x bf16 fits fp32) summed in fp32 by KS chained MFMAs.  The
+  matrix cores sum an MFMA's products as a k-ordered chain with one round-to-nearest rounding per product (stated for
+  the fp32 MFMA in the CDNA4 programming notes; taken here for the bf16 one, whose products are exact in fp32 as well),
+  so the error is at most u sum_k |P_k| over the chain's partial sums P_k.  The columns come in k order: first the 6 D
+  coordinate products, every partial at most A = 2 sum_d |x'_d y'_d|; then the norm pieces, FMM_SHIFT (Gaussian) and
+  the two online-shift columns -- nine roundings of partials at most T_abs = |x'|^2 + |y'|^2 + A + FMM_SHIFT + |kop|
+  (|kop| <= the row's largest |exponent| + 1; zero columns add exactly).  The online rescale adds delta to S in fp32:
+  one more.  e_S = u (6 D A + 10 T_abs).  exp(<x,y>): A = log2 e sum_d |x_d y_d|, three large columns.
+* exp(-r), fastmm: pairs with S <= tau = FMM_ABSEXP_KAPPA R^4 (R^2 the scaled squared half-diagonal of the bounding
+  box) are recomputed in the difference form (fmm_exact_sqdist): error gamma(D + 1) s.  The kernel decides on its own S,
+  so a pair whose s lies within the expansion's bound of tau takes the larger of the two bounds.
+* cfastmm: S is expanded around the centre c_g of the Morton group of CF_GROUP sources the pair's source falls in
+  (two MFMAs, KD = 32), and a pair is recomputed exactly when the kernel's S is at most tau_g = CF_KAPPA R_g^2
+  (kmvp_cfast.hpp, R_g = max |y - c_g| of the group).  The model restates neither the grouping nor tau_g: it bounds
+  R_g <= Dy (the diameter of the sources' bounding box) and, for a pair NOT recomputed, R_g^2 < S / CF_KAPPA.  Then
+  |x''| <= sqrt(s) + R_g, |y''| <= R_g, T_abs <= (sqrt(s) + 2 R_g)^2 and e_S <= u (KD + 2) T_abs plus the operands'
+  roundings; a recomputed pair has gamma(D + 1) s.  Every pair takes the larger of the two bounds.
+* transcendentals: v_exp_f32 / v_sqrt_f32 / v_rsq_f32, 1 ulp each by the ISA, taken as 2 ulp (2^-22 relative) per
+  instruction; exp(-r)'s argument 15 + kop - r is formed in fp32 (u (15 + |kop| + r) in log2 units).
+    Gaussian / exp(<x,y>)   L = ln2 e_S + 2^-22
+    exp(-r)                 L = ln2 (min(sqrt e_S, e_S / r) + 2^-22 (r + sqrt e_S) + u (15 + |kop| + r)) + 2^-22
+    1/r                     L = -ln(1 - e_S / s) / 2 + 2^-22   (pairs with e_S / s > 2^-8 FLAG their row)
+  relative error of k: expm1(L).
+* T split: T = 2^(15 + kop) k = T_h + T_l in two f16 (11 bits each): 2^-22 T while T_l is normal, 2^-25 absolute below
+  (f16 subnormal spacing 2^-24).  In the caller's units the floor is 2^-25 2^-(15 + kop); kop only decreases within a
+  segment and ends at or above floor(s_min) (the shift is floor of the smallest exponent seen, moved only when the
+  tile's largest T would pass 2^15.5: the half-binade hysteresis), so 2^-kop <= 2 k_max and the floor is at most
+  2^-39 k_max sum_j |b_j| for the row (ONLINE = 0, targets == sources: kop = 0, k_max = 1, the same figure).  T stays
+  below 2^15.5 < 65504 by the hysteresis.
+* b split (fastmm_colscale_kernel, pack_fastmm_signal_kernel): b sigma_e = b_h + b_l (f16), sigma_e = 2^(14 - e_b)
+  with max_j |b_je| = f 2^e_b, f in [0.5, 1), the exponent 14 - e_b clamped to [-100, 100]: 2^-22 |b_j| while b_l is
+  normal and 2^-25 / sigma_e absolute below, i.e. 2^-39 2^e_b <= 2^-38 max_j |b_je| (2^-125 when the clamp binds at
+  +100: a column whose largest entry is below 2^-86).  Beyond the clamp at -100 (max |b| >= 2^114) b sigma passes the
+  f16 range: such columns FLAG every row.  MODE 1 drops the product b_l T_l: 2^-22 |b| T more.
+* fp32 accumulation of the second product: the accumulators are folded into fp64 every 2 x `chunk` sources (and at
+  every shift change), so a chain holds at most n = 4 x min(2 chunk rounded to whole stages, segment) roundings (four
+  f16 products per source in MODE 0).  With independent round-to-nearest errors of mean zero, |error| <=
+  lam sqrt(n) u mass with probability >= 1 - 2 n exp(-lam^2 / 2) (Higham and Mary, SIAM J. Sci. Comput. 2019,
+  Thm 2.4), lam = 8, as in kmvp_bf16_model.  The fp64 folds and the segment reduction: 2^-50 mass.
+* normalised rows: the denominator is the same product with a column of ones (sigma = 1: b_h = 1 exactly, b_l = 0);
+  band = (band_num + |value| band_den) / (den - band_den); rows whose denominator band reaches the denominator are
+  FLAGGED.
+
+band = K (pair + tsplit + bsplit + acc) with K = 2 over the upper bounds (the factor covers the second-order terms the
+bounds drop).  rounding=False gives the plain float64 product with no band.
+
+Parity status: no reference counterpart; checked against kmvp_oracle.product / exp_dot_product with rounding disabled by
+tests/test_f32mm_model.py.
+"""
+from collections import namedtuple
+
+import numpy as np
+
+import kmvp_oracle
+
+C_GAUSSIAN = 1.2011224087864498   # sqrt(log2 e)
+C_ABSEXP = 1.4426950408889634     # log2 e
+LOG2E = C_ABSEXP
+U_ACC = 2.0 ** -23
+U_RNE = 2.0 ** -24
+TRANS = 2.0 ** -22
+FMM_SHIFT = 15.0
+FMM_ABSEXP_KAPPA = 5.0e-3
+CF_GROUP = 128
+CF_KAPPA = 0.03   # kmvp_cfast.hpp: tau_g = CF_KAPPA R_g^2
+LAM = 8.0
+K_BAND = 2.0
+FLAG_1R = 2.0 ** -8
+
+Model = namedtuple("Model", "value band mass pair tsplit bsplit acc flagged nonfinite")
+
+
+def fmm_ksteps(D):
+    """fastmm_kernel's k-steps: K = 6 D + 7 columns plus the two of the online shift (kmvp_fastmm.hpp fmm_ksteps)."""
+    return (6 * D + 9 + 15) // 16
+
+
+def fmm_stage_tiles(ks):
+    return 4 if ks <= 4 else (2 if ks <= 9 else 1)
+
+
+def _gamma(n, u=U_ACC):
+    return n * u / (1.0 - n * u)
+
+
+def chain_length(path, D, M, chunk=512, seg_len=None):
+    """The longest fp32 chain of the second product in sources: 2 chunk rounded to whole stages, at most a segment."""
+    if path == "fastmm":
+        per = 32 * fmm_stage_tiles(fmm_ksteps(D))
+        n = max(1, (2 * chunk) // per) * per
+    else:
+        n = max(1, (2 * chunk) // CF_GROUP) * CF_GROUP
+    return max(1, min(n, seg_len if seg_len else M, M if M else 1))
+
+
+def f32mm_product(kernel, y, x=None, b=None, normalize_rows=False, *, path="fastmm", online=None, rows=None, chunk=512,
+                  seg_len=None, j_offset=0, M_total=None, rounding=True):
+    """Modelled result of run_product_fastmm / run_product_cfastmm and its per-element band.
+
+    kernel: "gaussian", "absolute-exponential", "inverse-distance" (path="cfastmm" only) or "exp-dot" (fastmm).
+    y (M,D) sources, x (N,D) targets (None: the same points), b (M,E) signal (None: a column of ones).  online: the
+    per-target shift (default: targets != sources, always for exp-dot and 1/r).  rows: target indices to model.
+    chunk: the "chunk" option; seg_len: sources per segment (the longest fp32 chain is the shorter of the two).
+    rounding=False: the float64 product, no band.
+    Returns Model(value, band, mass, pair, tsplit, bsplit, acc (n, E) each, flagged (n,), nonfinite (n,))."""
+    y = np.asarray(y, dtype=np.float64)
+    same = x is None
+    xa = y if same else np.asarray(x, dtype=np.float64)
+    if online is None:
+        online = kernel in ("exp-dot", "inverse-distance") or not same
+    rows = np.arange(xa.shape[0], dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64)
+    M, D = y.shape
+    b = np.ones((M, 1)) if b is None else np.asarray(b, dtype=np.float64)
+    # what the kernels see of the clouds: the midpoint and half-diagonal of the bounding box of both (measure_clouds)
+    pts = np.concatenate((y, xa)) if not same else y
+    fin = np.isfinite(pts).all(axis=1)
+    lo = pts[fin].min(axis=0) if fin.any() else np.zeros(D)
+    hi = pts[fin].max(axis=0) if fin.any() else np.zeros(D)
+    radius2 = float((((hi - lo) / 2) ** 2).sum())
+    yf = np.isfinite(y).all(axis=1)
+    ydiam = float(np.sqrt(((y[yf].max(axis=0) - y[yf].min(axis=0)) ** 2).sum())) if yf.any() else 0.0
+    geo = dict(radius2=radius2, ydiam=ydiam, mid=0.5 * (lo + hi))
+    block = max(1, 2 ** 21 // max(1, M))
+    parts = [_block(kernel, y, xa, b, normalize_rows, path, online, rows[r0:r0 + block], chunk, seg_len, j_offset, M_total,
+                    rounding, geo) for r0 in range(0, max(len(rows), 1), block)]
+    return Model(*(np.concatenate(f) for f in zip(*parts)))
+
+
+def _block(kernel, y, xa, b, normalize_rows, path, online, rows, chunk, seg_len, j_offset, M_total, rounding, geo):
+    M, D = y.shape
+    x = xa[rows]
+    n = len(rows)
+    E = b.shape[1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        if kernel == "exp-dot":
+            s = -LOG2E * (x @ y.T)                                  # log2 of 1/k
+        else:
+            s = kmvp_oracle.sqdists_block(x, y, False)              # the difference form: s in the caller's units
+    flagged = np.zeros(n, dtype=bool)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        if kernel == "exp-dot":
+            shift = np.nanmin(np.where(np.isnan(s), np.inf, s), axis=1, keepdims=True) if M else np.zeros((n, 1))
+            shift = np.where(np.isfinite(shift), np.floor(shift), 0.0)
+            k = np.exp2(-(s - shift))                               # relative to 2^-shift: no overflow
+        elif kernel == "gaussian":
+            k = np.exp(-s)
+        elif kernel == "absolute-exponential":
+            k = np.exp(-np.sqrt(s))
+        else:
+            k = 1.0 / np.sqrt(s)
+            jz = kmvp_oracle.zero_column(rows, M if M_total is None else M_total) - j_offset
+            hit = (jz >= 0) & (jz < M)
+            k[np.nonzero(hit)[0], jz[hit]] = 0.0
+        # inf sources contribute 0 (k = 0 at s = inf); NaN stays NaN
+        kf = np.where(np.isfinite(k), k, 0.0)
+        babs = np.abs(b)
+        num = k @ b
+        mass = kf @ babs
+        den = k.sum(axis=1, keepdims=True)
+    scale_back = np.exp2(-shift) if kernel == "exp-dot" else np.ones((n, 1))
+    nonfinite = ~np.isfinite(num).all(axis=1) | (normalize_rows & ~(den[:, 0] > 0))
+    if not rounding:
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            value = num / den if normalize_rows else num * scale_back
+        z = np.zeros_like(value)
+        return Model(value, z, np.abs(kf) @ babs * (1 if normalize_rows else scale_back), z, z, z, z, flagged,
+                     ~np.isfinite(value).all(axis=1))
+
+    # ---- e_S: the bound on the kernel's S (log2 units for the Gaussian / exp-dot, scaled squared distance otherwise)
+    u = U_RNE
+    with np.errstate(invalid="ignore", over="ignore"):
+        if kernel == "exp-dot":
+            absdot = np.abs(x) @ np.abs(y).T
+            kop = np.max(np.where(np.isfinite(s), np.abs(s), 0.0), axis=1, keepdims=True) + 1.0 if M else 1.0
+            A = LOG2E * absdot                                      # any prefix of the 6 D product columns
+            e_s = u * (6 * D * A + 3 * (A + FMM_SHIFT + kop)) + 2 * u * A + U_ACC * A
+            L = np.log(2.0) * e_s + TRANS
+        else:
+            c = C_GAUSSIAN if kernel == "gaussian" else (C_ABSEXP if kernel == "absolute-exponential" else 1.0)
+            ss = s * c * c                                          # scaled squared distance
+            r = np.sqrt(ss)
+            e_exact = _gamma(D + 1) * ss
+            if path == "fastmm":
+                mid = geo["mid"]                                    # (the centre is bounded, not restated)
+                nx = ((x - mid) ** 2).sum(1)[:, None] * c * c
+                ny = ((y - mid) ** 2).sum(1)[None, :] * c * c
+                A = 2 * (np.abs(x - mid) * c) @ (np.abs(y - mid) * c).T  # any prefix of the 6 D product columns
+                Tabs = nx + ny + A
+                if kernel == "gaussian":
+                    smax = np.max(np.where(np.isfinite(ss), ss, 0.0), axis=1, keepdims=True) if M else np.zeros((n, 1))
+                    kopg = (smax + 1.0) if online else 0.0         # |kop| <= the row's largest exponent + 1
+                    Tabs = Tabs + FMM_SHIFT + kopg
+                # k-ordered chain: 6 D roundings of partials <= A, then 9 of partials <= Tabs (norm pieces, shift
+                # columns); the online rescale's fp32 add: one more
+                e_exp = u * (6 * D * A + 10 * Tabs) + 4 * u * r * (np.sqrt(nx) + np.sqrt(ny)) \
+                    + (u + 2.0 ** -27) * (nx + ny) + U_ACC * A / 2
+                if kernel == "gaussian":
+                    e_s = e_exp
+                else:                                               # exp(-r): the closest pairs recomputed
+                    tau = FMM_ABSEXP_KAPPA * (geo["radius2"] * c * c) ** 2
+                    sure = ss + e_exp <= 0.5 * tau
+                    e_s = np.where(sure, e_exact, np.where(ss - e_exp > 2.0 * tau, e_exp, np.maximum(e_exp, e_exact)))
+            else:
+                # a pair the kernel does not recompute has S > tau_g = CF_KAPPA R_g^2, so R_g^2 < S / CF_KAPPA; and
+                # R_g <= Dy.  |x''| <= sqrt(s) + R_g, |y''| <= R_g: T_abs <= (sqrt(s) + 2 R_g)^2
+                dy2 = (geo["ydiam"] * c) ** 2
+                t0 = u * 34 * (r + 2 * np.sqrt(dy2)) ** 2
+                rg2 = np.minimum(dy2, (ss + t0) / CF_KAPPA)
+                Tabs = (r + 2 * np.sqrt(rg2)) ** 2
+                e_nr = u * 34 * Tabs + 8 * u * r * np.sqrt(Tabs) + 2 * u * Tabs
+                e_s = np.maximum(e_nr, e_exact)                     # recomputed or not: either bound
+            if kernel == "gaussian":
+                L = np.log(2.0) * e_s + TRANS
+            elif kernel == "absolute-exponential":
+                kopa = np.max(np.where(np.isfinite(r), r, 0.0), axis=1, keepdims=True) + 1.0 if M else 1.0
+                dr = np.minimum(np.sqrt(e_s), e_s / r) + TRANS * (r + np.sqrt(e_s)) + u * (FMM_SHIFT + kopa + r)
+                L = np.log(2.0) * dr + TRANS
+            else:
+                ratio = e_s / ss
+                L = -0.5 * np.log1p(-np.minimum(ratio, 0.5)) + TRANS
+                live = kf != 0.0
+                flagged |= ((ratio > FLAG_1R) & live).any(axis=1)
+        L = np.where(np.isfinite(L), L, 0.0)
+        pair_rel = np.expm1(L) + TRANS                             # k's own error + the T split's relative part
+    # ---- the absolute floors and the signal's split
+    kmax = kf.max(axis=1, keepdims=True) if M else np.zeros((n, 1))
+    bmax = babs.max(axis=0, keepdims=True) if M else np.zeros((1, E))
+    with np.errstate(divide="ignore"):
+        eb = np.where(bmax > 0, np.floor(np.log2(np.where(bmax > 0, bmax, 1.0))) + 1, 0)
+    ex = np.clip(14 - eb, -100, 100)
+    flagged |= bool((14 - eb < -100).any())                        # b sigma beyond the f16 range
+    b_floor = 2.0 ** -25 * np.exp2(-ex)                             # absolute, per column
+    with np.errstate(invalid="ignore", over="ignore"):
+        pair = kf * pair_rel @ babs
+        tsplit = 2.0 ** -39 * kmax * babs.sum(axis=0, keepdims=True)
+        bsplit = 2.0 * TRANS * mass + kf.sum(axis=1, keepdims=True) * b_floor
+        n_chain = 4.0 * chain_length(path, D, M, chunk, seg_len)
+        acc = LAM * np.sqrt(n_chain) * u * mass + 2.0 ** -50 * mass
+        band_num = K_BAND * (pair + tsplit + bsplit + acc)
+    if not normalize_rows:
+        sb = scale_back
+        with np.errstate(over="ignore", invalid="ignore"):
+            return Model(num * sb, band_num * sb, mass * sb, pair * sb, tsplit * sb, bsplit * sb, acc * sb, flagged,
+                         nonfinite | ~np.isfinite(num * sb).all(axis=1))
+    ksum = kf.sum(axis=1, keepdims=True)
+    bden = K_BAND * ((kf * pair_rel).sum(axis=1, keepdims=True) + 2.0 ** -39 * kmax * M + TRANS * ksum
+                     + LAM * np.sqrt(n_chain) * u * ksum + 2.0 ** -50 * ksum)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        value = num / den
+        room = den - bden
+        band = (band_num + np.abs(value) * bden) / room
+        flagged |= ~(room > 0).all(axis=1)
+        return Model(value, band, mass / den, pair / den, tsplit / den, bsplit / den, acc / den, flagged, nonfinite)
+
