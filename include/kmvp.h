@@ -145,6 +145,18 @@ int kmvp_absexp_cg_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int m
 int kmvp_invdist_minres_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int maxit,
                               double* out_b, int* iters, double* resid);
 
+/* Regularised systems (an extension: no reference method stands behind it -- the reference's lstsq solves the bare
+ * K b = a; this is the `alpha` / nugget / noise term of kernel ridge regression, Kriging and Gaussian processes).
+ * A = K + ridge I + diag(d) for the solvers that follow on this ctx.  d: n doubles (n = number of points of the
+ * solve, i.e. N; always the FULL vector, also on a source shard) or NULL with n == 0.  (NULL, 0, 0.0) switches it
+ * off.  Products (kmvp_gaussian ...) are not affected.  kmvp_set_points clears it.
+ *   The effective diagonal ridge + d_i is kept in float64 on the device for every working precision (the Krylov
+ *   vectors are float64) and is added to K v inside the device-resident iteration, after the all-reduce of a
+ *   sharded product; rtol, *resid and the 1.5 rtol verdict of the solvers are then about A b = a.
+ *   KMVP_E_INVALID: a non-finite ridge or d_i (here); at solve time, n != N, and for the CG entries (Gaussian,
+ *   exp(-r): positive definite only with a non-negative shift) any ridge + d_i < 0.  MINRES takes any sign. */
+int kmvp_set_solver_diagonal(kmvp_ctx* ctx, const double* d_or_null, int64_t n, double ridge);
+
 /* Source sharding over the GPUs of one node, one process per GPU:
  * rank 0 calls kmvp_comm_get_unique_id and hands the 128 bytes to every rank
  * out of band; every rank then calls kmvp_comm_init.  world == 1 is allowed. */

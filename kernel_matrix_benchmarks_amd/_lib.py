@@ -44,6 +44,7 @@ SYMBOLS = [
                                         _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_invdist_minres_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                              _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
+    ("kmvp_set_solver_diagonal", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_double]),
     ("kmvp_comm_get_unique_id", _c.c_int, [_c.c_void_p]),
     ("kmvp_comm_init", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int]),
     ("kmvp_comm_init_host", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int]),
@@ -201,6 +202,18 @@ class Context:
         if rc not in (0, 6):
             self._check(rc)
         return out, iters.value, resid.value, rc == 0
+
+    def set_solver_diagonal(self, d_or_none, ridge=0.0):
+        """A = K + ridge I + diag(d) for the solves that follow (include/kmvp.h kmvp_set_solver_diagonal); d: one float64
+        value per point (the FULL vector, also on a source shard) or None.  (None, 0.0) switches it off; set_points
+        clears it."""
+        if d_or_none is None:
+            self._check(self._lib.kmvp_set_solver_diagonal(self._ctx, None, 0, float(ridge)))
+            return
+        d = np.ascontiguousarray(d_or_none, dtype=np.float64)
+        if d.ndim != 1:  # the library reads d.size doubles and compares the count with the points at solve time
+            raise ValueError(f"the solver diagonal has shape {d.shape}, expected one value per point")
+        self._check(self._lib.kmvp_set_solver_diagonal(self._ctx, d.ctypes.data, d.size, float(ridge)))
 
     def comm_init(self, unique_id, rank, world):
         buf = (ctypes.c_char * UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

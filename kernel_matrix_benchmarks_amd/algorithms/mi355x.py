@@ -18,7 +18,9 @@ Differences a user should know about
  * The solver is conjugate gradients on the product operator with a residual
    stopping rule; the dense ``lstsq`` of the reference cannot be matched
    vector-for-vector on these numerically singular matrices, so it
-   reports (and is tested on) the relative residual.
+   reports (and is tested on) the relative residual.  ``MI355XSolver(ridge=...)``
+   solves the regularised system (K + ridge I) b = a instead, which is well posed
+   and is tested against a dense solve on the solution vector.
 """
 import numpy as np
 
@@ -308,10 +310,15 @@ class MI355XProduct(BaseProduct):
 class MI355XSolver(BaseSolver):
     """Solves K b = a with the HIP product as the operator: conjugate gradients for the positive
     definite Gaussian / exp(-r) matrices, MINRES for the symmetric indefinite inverse-distance
-    matrix (zero diagonal, bruteforce.py:13-14)."""
+    matrix (zero diagonal, bruteforce.py:13-14).
+
+    ``ridge`` (an extension: the reference's lstsq solves the bare system) regularises it: (K + ridge I) b = a with a
+    float, (K + diag(ridge)) b = a with one value per point -- the nugget / noise / ``alpha`` of Kriging, Gaussian
+    processes and kernel ridge regression.  Non-negative for the CG kernels, any sign for inverse-distance.  The
+    residual, ``rtol`` and ``converged`` are then about the regularised system."""
 
     def __init__(self, *, kernel, dimension, normalize_rows=False, precision=np.float64,
-                 device=0, rtol=1e-6, maxit=10000, comm=None, refine=None, inner_rtol=1e-3):
+                 device=0, rtol=1e-6, maxit=10000, comm=None, refine=None, inner_rtol=1e-3, ridge=0.0):
         super().__init__(kernel=kernel, dimension=dimension, normalize_rows=normalize_rows,
                          precision=precision)
         if kernel not in SUPPORTED_KERNELS:
@@ -343,8 +350,63 @@ class MI355XSolver(BaseSolver):
         self._dot = kernel == "exp-dot"  # K = D G D with D = diag(exp(|x|^2/2)), G the Gaussian matrix of the points / sqrt(2)
         self._device_kernel_fn = "gaussian" if self._dot else kernel
         self.method = "minres" if kernel == "inverse-distance" else "cg"
-        self.name = (f"MI355XSolver({_precision_name(precision)}, {self.method}, rtol={rtol:g})" if not refine else
-                     f"MI355XSolver({_precision_name(precision)}, {self.method} + refinement on {refine}, rtol={rtol:g})")
+        self._base_name = (f"MI355XSolver({_precision_name(precision)}, {self.method}, rtol={rtol:g}" if not refine else
+                           f"MI355XSolver({_precision_name(precision)}, {self.method} + refinement on {refine}, rtol={rtol:g}")
+        self._diag_in_ctx = False  # whether the contexts hold a diagonal right now (set_points clears it)
+        self._set_ridge(ridge)
+
+    def _set_ridge(self, ridge):
+        """Validates and stores ``ridge`` (a float, or one value per point); it reaches the library at the next query()."""
+        try:
+            r = np.array(ridge, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"ridge must be a number or an array of one value per point: {e}") from None
+        if r.ndim > 1 or (r.ndim == 1 and r.size == 0):
+            raise ValueError(f"ridge has shape {r.shape}: pass a number or a one-dimensional array of one value per point")
+        if not np.isfinite(r).all():
+            raise ValueError("ridge must be finite")
+        if self.method == "cg" and (r < 0).any():
+            raise ValueError(f"ridge must be non-negative for kernel {self.kernel} (conjugate gradients needs a positive "
+                             "definite system); only inverse-distance (MINRES) takes a negative shift")
+        if r.ndim == 1 and getattr(self, "M", None) is not None and r.size != self.M:
+            raise ValueError(f"ridge has {r.size} values, the point cloud has {self.M} points")
+        self.ridge = float(r) if r.ndim == 0 else r
+        self._diag_dirty = True
+        # (the name moves only when a ridge is set: result files of runs without one keep theirs)
+        if r.ndim == 0:
+            self.name = self._base_name + (f", ridge={self.ridge:g})" if self.ridge != 0.0 else ")")
+        else:
+            self.name = self._base_name + f", ridge=per-point up to {float(np.max(r)):g})"
+
+    def _library_diagonal(self):
+        """(d or None, ridge) as kmvp_set_solver_diagonal takes them.  exp-dot: the library iterates on G z = D^-1 a
+        (z = D b, D = diag(exp(|x|^2/2))), where (K + L) b = a reads (G + D^-1 L D^-1) z = D^-1 a: it is handed the
+        per-point vector l_i exp(-|x_i|^2) = l_i exp(-2 hx_i)."""
+        vector = not isinstance(self.ridge, float)
+        if not vector and self.ridge == 0.0:
+            return None, 0.0
+        if self._dot:
+            return np.ascontiguousarray(self.ridge * np.exp(-2.0 * self._hx), dtype=np.float64), 0.0
+        return (self.ridge, 0.0) if vector else (None, self.ridge)
+
+    def _apply_diagonal(self):
+        """Hands the diagonal to the contexts when it changed since the last query() (or the points did)."""
+        if not self._diag_dirty:
+            return
+        d, ridge = self._library_diagonal()
+        on = d is not None or ridge != 0.0
+        if on or self._diag_in_ctx:
+            for ctx in (self._ctx, self._ctx32):
+                if ctx is not None:
+                    ctx.set_solver_diagonal(d, ridge)
+        self._diag_in_ctx = on
+        # what the host-side residuals (refinement, exp-dot verdict) multiply the iterate by
+        self._host_diag = None if not on else (ridge if d is None else d.reshape(-1, 1))
+        self._diag_dirty = False
+
+    def _diag_term(self, x):
+        """The diagonal's share of A x on the host, as the library applies it (0 without a ridge)."""
+        return 0.0 if self._host_diag is None else self._host_diag * x
 
     def _cast(self, a):
         if self._round is not None:
@@ -367,6 +429,9 @@ class MI355XSolver(BaseSolver):
         y = self._cast(source_points)
         self._y_device = y
         self.M, self.D = y.shape
+        if not isinstance(self.ridge, float) and self.ridge.size != self.M:
+            raise ValueError(f"ridge has {self.ridge.size} values, the point cloud has {self.M} points")
+        self._diag_in_ctx, self._diag_dirty = False, True  # kmvp_set_points clears the library's diagonal
         if self._ctx is None:
             self._ctx = _lib.Context(self.device)
         world = 1 if self.comm is None else self.comm.world
@@ -397,13 +462,16 @@ class MI355XSolver(BaseSolver):
         if self._a.ndim != 2 or self._a.shape[0] != self.M:
             raise ValueError(f"target_signal has shape {a.shape}, expected ({self.M}, E)")
 
-    def set_query_arguments(self, rtol=None, maxit=None):
+    def set_query_arguments(self, rtol=None, maxit=None, ridge=None):
         if rtol is not None:
             self.rtol = rtol
         if maxit is not None:
             self.maxit = maxit
+        if ridge is not None:
+            self._set_ridge(ridge)  # takes effect at the next query()
 
     def query(self):
+        self._apply_diagonal()
         if self.refine:
             self._query_refined()
         else:
@@ -412,11 +480,11 @@ class MI355XSolver(BaseSolver):
         if self._dot:
             # The iteration ran on the SCALED system G z = D^-1 a (z = D b, D = diag(exp(|x|^2/2))); where D varies a lot
             # its residual says little about K b = a.  The verdict is therefore taken on the unscaled system, from one
-            # more product:  a - K b = D (D^-1 a - G z).
+            # more product:  a - K b = D (D^-1 a - G z); with a ridge L:  a - K b - L b = D (D^-1 a - G z - D^-2 L z).
             z = np.ascontiguousarray(self.res, dtype=self._host_dtype)
             self._ctx.set_signal(z)
             self._ctx.run(self._device_kernel_fn, False)
-            r_scaled = np.asarray(self._a, dtype=np.float64) - self._ctx.get_result(self.M, z.shape[1])
+            r_scaled = np.asarray(self._a, dtype=np.float64) - (self._ctx.get_result(self.M, z.shape[1]) + self._diag_term(self.res))
             with np.errstate(over="ignore", invalid="ignore"):
                 d = np.exp(self._hx).reshape(-1, 1)
                 num = np.linalg.norm(d * r_scaled, axis=0)
@@ -429,7 +497,8 @@ class MI355XSolver(BaseSolver):
 
     def _query_refined(self):
         """Mixed-precision iterative refinement (see __init__).  Every outer step: float64 residual (one product of
-        the float64 context), float32 CG on the scaled residual, float64 update."""
+        the float64 context), float32 CG on the scaled residual, float64 update.  With a ridge the inner context
+        iterates on the same regularised operator and the float64 residual is a - (K x + (ridge + d) x)."""
         a = np.asarray(self._a, dtype=np.float64)
         anorm = np.linalg.norm(a, axis=0)
         anorm[anorm == 0] = 1.0
@@ -460,7 +529,7 @@ class MI355XSolver(BaseSolver):
             x_new = x + d * scale
             self._ctx.set_signal(x_new)
             self._ctx.run(self._device_kernel_fn, False)
-            r_new = a - self._ctx.get_result(self.M, a.shape[1])
+            r_new = a - (self._ctx.get_result(self.M, a.shape[1]) + self._diag_term(x_new))
             rel_new = float(np.max(np.linalg.norm(r_new, axis=0) / anorm))
             if not np.isfinite(rel_new):
                 self.stop_reason = "non-finite"
@@ -482,8 +551,11 @@ class MI355XSolver(BaseSolver):
         return 0.0 if self._ctx is None else self._ctx.device_bytes / 1024
 
     def get_additional(self):
+        # (with a ridge the residual keys describe the regularised system (K + ridge) b = a)
         extra = {"cg_iterations": self.iterations, "cg_relative_residual": self.residual,
                  "cg_converged": bool(self.converged), "n_gpus": 1 if self.comm is None else self.comm.world}
+        if not isinstance(self.ridge, float) or self.ridge != 0.0:  # like the name: only when one is set
+            extra["ridge"] = float(np.max(self.ridge))
         if self._ctx is not None:
             extra["device_kernel"] = self._ctx.last_kernel_name  # the operator's pair-loop kernel
             extra["rccl_ranks"] = self._ctx.rccl_ranks

@@ -89,7 +89,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
-                    &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
+                    &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     release(*b);
   for (int i = 0; i < 5; ++i)
@@ -130,6 +130,9 @@ int kmvp_set_points(kmvp_ctx* c, const void* y, int64_t M, const void* x_or_null
   c->m_total = M_total;
   c->have_points = true;
   c->have_signal = false;
+  c->diag_on = false;  // the solver's diagonal belongs to the points it was set for
+  c->diag_n = 0;
+  c->diag_ridge = c->diag_min = 0.0;
   ++c->points_ver;
   return KMVP_OK;
 }
@@ -196,6 +199,36 @@ int kmvp_absexp_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int max
 int kmvp_invdist_minres_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
                               int* iters, double* resid) {
   return minres_solve(c, K_INVDIST, a, E, rtol, maxit, out_b, iters, resid);
+}
+
+int kmvp_set_solver_diagonal(kmvp_ctx* c, const double* d, int64_t n, double ridge) {
+  if (!c) return KMVP_E_INVALID;
+  if (!std::isfinite(ridge)) return fail(c, KMVP_E_INVALID, "solver diagonal: ridge is not finite");
+  if (n < 0 || (d == nullptr) != (n == 0)) return fail(c, KMVP_E_INVALID, "solver diagonal: pass n values, or NULL and n = 0");
+  if (!d) {
+    c->diag_on = ridge != 0.0;
+    c->diag_n = 0;
+    c->diag_ridge = c->diag_min = ridge;
+    return KMVP_OK;
+  }
+  // what the kernels read is ridge + d_i, formed once here (every rank forms the same values)
+  std::vector<double> eff((size_t)n);
+  double lo = INFINITY;
+  for (int64_t i = 0; i < n; ++i) {
+    eff[i] = ridge + d[i];
+    if (!std::isfinite(eff[i])) return fail(c, KMVP_E_INVALID, "solver diagonal: d[" + std::to_string(i) + "] is not finite");
+    lo = std::min(lo, eff[i]);
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = ensure(c, c->sdiag, sizeof(double) * (size_t)n)) return rc;
+  c->diag_on = false;  // (a failed upload leaves no half-written diagonal behind)
+  HIP_TRY(c, hipMemcpyAsync(c->sdiag.p, eff.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->diag_on = true;
+  c->diag_n = n;
+  c->diag_ridge = ridge;
+  c->diag_min = lo;
+  return KMVP_OK;
 }
 
 int kmvp_comm_get_unique_id(void* id128) {
@@ -310,7 +343,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   if (!c) return 0;
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
-                          &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
+                          &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     t += b->cap;
   return (int64_t)t;

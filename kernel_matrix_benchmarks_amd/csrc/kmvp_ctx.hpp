@@ -107,6 +107,10 @@ struct kmvp_ctx {
   bool same_points = false;
   bool have_points = false, have_signal = false, density = false;
   bool async_product = false;   // solvers: run_product() leaves the result on the stream, no host synchronisation
+  // solvers: A = K + ridge I + diag(d) (kmvp_set_solver_diagonal).  diag_n > 0: sdiag holds ridge + d_i; else the scalar
+  bool diag_on = false;
+  int64_t diag_n = 0;
+  double diag_ridge = 0.0, diag_min = 0.0;  // diag_min: the smallest ridge + d_i (CG refuses a negative one)
 
   DevBuf y_raw, x_raw, b_raw;   // caller's arrays in the working precision
   DevBuf xs, rec;               // kernel layouts (specialised path; bf16 path: augmented targets, tile images)
@@ -123,6 +127,7 @@ struct kmvp_ctx {
   DevBuf kexp, kshift, xchgk;   // exp(<x,y>): exponents per (segment, target) / per target / per target after the all-reduce(min)
   DevBuf kflag;                 // exp(<x,y>): set when a row's exponent reached the shift's clamp (check_shift_range_kernel)
   DevBuf scratch;               // CG vectors / dot products
+  DevBuf sdiag;                 // solvers: the effective diagonal ridge + d_i, N doubles (kmvp_set_solver_diagonal)
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
   int packed_layout = -1;  // LAYOUT_* of the path that owns xs / rec right now

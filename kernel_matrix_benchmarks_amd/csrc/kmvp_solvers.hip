@@ -2,6 +2,8 @@
 // gradients (SPD Gaussian / exp(-r) matrices) and MINRES (symmetric indefinite
 // inverse-distance matrix).  The reference solves densely with lstsq (bruteforce.py:205-207);
 // parity is judged on the residual.
+// With kmvp_set_solver_diagonal the operator of both is A = K + ridge I + diag(d): the product is untouched, the
+// diagonal term is added to K v by the first kernel that consumes it (the *_diag_* variants below).
 #include <cstdlib>
 
 #include "kmvp_ctx.hpp"
@@ -47,6 +49,40 @@ __global__ void cg_dot_kernel(const double* __restrict__ u, const double* __rest
   }
 }
 
+// The solver's diagonal (kmvp_set_solver_diagonal) as the kernels take it: dg[i] = ridge + d_i per point, or nullptr and the
+// scalar.  Both are fixed for a whole solve, so a captured burst stays valid.
+struct Diag {
+  const double* dg;
+  double ridge;
+  __device__ __forceinline__ double at(int64_t i) const { return dg ? dg[i] : ridge; }
+};
+
+// CG's first consumer of K p with the diagonal on: Ap[i][e] += diag_i p[i][e] in place (Ap = K p on entry, the full
+// replicated vector after the all-reduce), and partial[block][e] = sum of p . Ap in the same sweep -- the layout of
+// cg_dot_kernel, so cg_scalars_kernel reads it unchanged.
+__global__ void cg_diag_dot_kernel(const double* __restrict__ p, double* __restrict__ Ap, Diag diag, int64_t m, int E,
+                                   double* __restrict__ partial) {
+  __shared__ double red[256];
+  for (int e = 0; e < E; ++e) {
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m;
+         i += (int64_t)gridDim.x * blockDim.x) {
+      const double pv = p[i * E + e];
+      const double av = Ap[i * E + e] + diag.at(i) * pv;
+      Ap[i * E + e] = av;
+      acc += pv * av;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[(int64_t)blockIdx.x * E + e] = red[0];
+    __syncthreads();
+  }
+}
+
 template <typename real>
 __global__ void cg_cast_kernel(const double* __restrict__ in, real* __restrict__ out, int64_t n) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,6 +99,14 @@ __global__ void residual_kernel(const real* __restrict__ a, const double* __rest
                                 int64_t n) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q < n) out[q] = (double)a[q] - Kx[q];
+}
+
+// out = a - (K x + diag x): the residual of the regularised system
+template <typename real>
+__global__ void residual_diag_kernel(const real* __restrict__ a, const double* __restrict__ Kx, const double* __restrict__ x,
+                                     Diag diag, double* __restrict__ out, int64_t n, int E) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < n) out[q] = (double)a[q] - (Kx[q] + diag.at(q / E) * x[q]);
 }
 
 // Sum of the CG_BLOCKS partials of column e by the whole block (fixed tree order: deterministic).
@@ -158,6 +202,9 @@ static int solver_begin(kmvp_ctx* c, const void* a_host, int E, double rtol, int
   if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
   if (int rc = solver_shape(c)) return rc;
   if (!a_host || !out_b || E < 1 || maxit < 0 || !(rtol > 0)) return fail(c, KMVP_E_INVALID, "bad solver arguments");
+  if (c->diag_on && c->diag_n && c->diag_n != c->N)
+    return fail(c, KMVP_E_INVALID, "solver diagonal: " + std::to_string(c->diag_n) + " values for " + std::to_string(c->N) +
+                                       " points (pass the full vector, also on a source shard)");
   HIP_TRY(c, hipSetDevice(c->device));
   k.m = c->N;
   k.E = E;
@@ -192,11 +239,14 @@ static int cg_dots(kmvp_ctx* c, const double* u, const double* v, const Krylov& 
   return KMVP_OK;
 }
 
+static Diag solver_diag(const kmvp_ctx* c) { return Diag{c->diag_n ? (const double*)c->sdiag.p : nullptr, c->diag_ridge}; }
+
 // K applied to the device vector v (N,E) double, N = all points; the result lands in c->out
 // (N,E) double.  With source sharding the Krylov vectors are replicated on every
 // rank, the operator is sharded: this rank's signal is its own slice v[j_offset .. j_offset+M)
 // and run_product() ends with the all-reduce of the (N,E) sums, so every rank continues with
-// bitwise the same vectors.
+// bitwise the same vectors.  The solver's diagonal is NOT applied here: the first consumer of c->out adds it, once, on
+// the full vector.
 static int cg_apply(kmvp_ctx* c, int kernel, const double* v, const Krylov& k) {
   const int64_t n = c->M * k.E;  // this rank's sources
   v += (size_t)c->j_offset * k.E;
@@ -234,7 +284,7 @@ static int load_rhs(kmvp_ctx* c, const void* a_host, double* out, const Krylov& 
   return KMVP_OK;
 }
 
-// r = a - K x with one more product, and r2 = |r|^2 per column
+// r = a - K x (with the diagonal on: a - K x - diag x) with one more product, and r2 = |r|^2 per column
 static int true_residual(kmvp_ctx* c, int kernel, const void* a_host, const double* x, double* r, const Krylov& k,
                          std::vector<double>& r2) {
   int rc = cg_apply(c, kernel, x, k);
@@ -242,7 +292,12 @@ static int true_residual(kmvp_ctx* c, int kernel, const void* a_host, const doub
   if (rc) return rc;
   const int64_t n = (int64_t)k.n;
   const double* Kx = (const double*)c->out.p;
-  if (c->dtype == KMVP_F64)
+  if (c->diag_on) {
+    if (c->dtype == KMVP_F64)
+      hipLaunchKernelGGL((residual_diag_kernel<double>), dim3(blocks_for(n)), dim3(256), 0, c->stream, (const double*)c->b_raw.p, Kx, x, solver_diag(c), r, n, k.E);
+    else
+      hipLaunchKernelGGL((residual_diag_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, c->stream, (const float*)c->b_raw.p, Kx, x, solver_diag(c), r, n, k.E);
+  } else if (c->dtype == KMVP_F64)
     hipLaunchKernelGGL((residual_kernel<double>), dim3(blocks_for(n)), dim3(256), 0, c->stream, (const double*)c->b_raw.p, Kx, r, n);
   else
     hipLaunchKernelGGL((residual_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, c->stream, (const float*)c->b_raw.p, Kx, r, n);
@@ -340,8 +395,13 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
              double* out_b, int* iters, double* resid) {
   Krylov k;  // x, r, p; state: scal = [rs_old | alpha | beta | |a|^2] x E, stop, iterations
   if (int rc = solver_begin(c, a_host, E, rtol, maxit, out_b, 3, 4 * (size_t)E, k)) return rc;
+  if (c->diag_on && c->diag_min < 0.0)
+    return fail(c, KMVP_E_INVALID, "solver diagonal: conjugate gradients needs ridge + d_i >= 0 everywhere (smallest: " +
+                                       std::to_string(c->diag_min) + ")");
   SolveGuard guard{c};
   BurstGraph graph(c);
+  const bool with_diag = c->diag_on;
+  const Diag diag = solver_diag(c);
   const int64_t m = k.m;
   const size_t vec = k.n * sizeof(double);
   double *x = k.vec(0), *r = k.vec(1), *p = k.vec(2), *scal = k.state;
@@ -379,8 +439,11 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
   auto body = [&](int burst) -> int {
     for (int i = 0; i < burst; ++i) {
       if (int rcb = cg_apply(c, kernel, p, k)) return rcb;
-      const double* Ap = (const double*)c->out.p;
-      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, p, Ap, m, E, k.partial);
+      double* Ap = (double*)c->out.p;
+      if (with_diag)  // Ap = K p + diag p, and p . Ap
+        hipLaunchKernelGGL(cg_diag_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, p, Ap, diag, m, E, k.partial);
+      else
+        hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, p, Ap, m, E, k.partial);
       hipLaunchKernelGGL(cg_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, scal, E, 1, rtol);
       hipLaunchKernelGGL(cg_update_xr_kernel, dim3(vblocks), dim3(256), 0, c->stream, x, r, p, Ap, scal, m, E);
       hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, r, r, m, E, k.partial);
@@ -393,7 +456,7 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
   int it = 0;
   double rel = worst(anorm2.data());
   double true_rel = NAN, prev_true = INFINITY;
-  // The iteration stops on the RECURRENCE residual; the verdict is on the TRUE one, a - K x, from one more
+  // The iteration stops on the RECURRENCE residual; the verdict is on the TRUE one, a - K x (- diag x), from one more
   // product.  Where the two have drifted apart (float32 operator, ill-conditioned Gaussian matrices) the
   // recurrence is restarted from the true residual (r = p = a - K x: "residual replacement"), at most
   // CG_MAX_RESTARTS times and only while that still halves the true residual.
@@ -444,6 +507,20 @@ __global__ void vec_lin3_dev_kernel(double* __restrict__ out, const double* a,
   if (c) v += coef[2 * E + e] * c[q];
   out[q] = v;
   if (out2) out2[q] = v;
+}
+
+// MINRES' first consumer of K v with the solver's diagonal on: y = c0 (K v + diag v) + c1 r1, the Lanczos step of
+// A = K + diag (vec_lin3_dev_kernel with the diagonal term folded into its first operand); nothing once stopped.
+__global__ void minres_diag_lanczos_kernel(double* __restrict__ y, const double* __restrict__ Kv, const double* __restrict__ v,
+                                           const double* __restrict__ r1, Diag diag, const double* __restrict__ coef,
+                                           const double* __restrict__ stop, int64_t m, int E) {
+  if (*stop != 0.0) return;
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= m * E) return;
+  const int e = (int)(q % E);
+  double yv = coef[e] * (Kv[q] + diag.at(q / E) * v[q]);
+  yv += coef[E + e] * r1[q];
+  y[q] = yv;
 }
 
 // The three vector updates that close a MINRES iteration, in one launch (each was a ~4.5 us kernel of its own in a solve whose
@@ -543,6 +620,8 @@ int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol
   Krylov k;  // x, r1, r2, y, v, w, w1, w2; state: see MS_* above
   if (int rc = solver_begin(c, a_host, E, rtol, maxit, out_b, 8, ms_stop(E), k)) return rc;
   SolveGuard guard{c};
+  const bool with_diag = c->diag_on;
+  const Diag diag = solver_diag(c);
   const int64_t m = k.m;
   const size_t vec = k.n * sizeof(double);
   double *x = k.vec(0), *r1 = k.vec(1), *r2 = k.vec(2), *y = k.vec(3), *v = k.vec(4);
@@ -595,7 +674,11 @@ int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol
     for (int i = 0; i < burst; ++i) {
       // (v = y / beta was written by the previous iteration's tail, or before the first burst)
       if (int rcb = cg_apply(c, kernel, v, k)) return rcb;
-      dlin3(y, (const double*)c->out.p, r1, nullptr, 1);  // y = K v - (beta / oldb) r1
+      if (with_diag)  // y = (K v + diag v) - (beta / oldb) r1
+        hipLaunchKernelGGL(minres_diag_lanczos_kernel, dim3(vb), dim3(256), 0, c->stream, y, (const double*)c->out.p,
+                           (const double*)v, (const double*)r1, diag, st + ms_triple(E, 1), stop, m, E);
+      else
+        dlin3(y, (const double*)c->out.p, r1, nullptr, 1);  // y = K v - (beta / oldb) r1
       hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, v, y, m, E, k.partial);
       hipLaunchKernelGGL(minres_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, st, E, 1, rtol);
       // y - (alfa / beta) r2, written into the old r1 buffer AND back into y
@@ -622,7 +705,7 @@ int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol
   dlin3(v, y, nullptr, nullptr, 0);  // v = y / beta of the first iteration
   if ((rc = run_bursts(c, k, maxit, rtol, it, rel, state, body, worst, nullptr))) return rc;
 
-  // true residual ||a - K x|| / ||a||
+  // true residual ||a - K x (- diag x)|| / ||a||
   if ((rc = true_residual(c, kernel, a_host, x, v, k, dots))) return rc;
   double true_rel = 0.0;
   for (int e = 0; e < E; ++e) {
