@@ -45,7 +45,7 @@
 
 namespace kmvp {
 
-constexpr int CELL_TILE = 32;
+// CELL_TILE (32 points per tile): kmvp_plan.hpp
 constexpr int CELL_STAGE_TILES = 4;
 constexpr int CELL_A_BYTES = CELL_TILE * 32;                       // 32 rows of 16 bf16
 constexpr int CELL_TILE_BYTES = CELL_A_BYTES + CELL_TILE * 16;     // + (e_x, e_y, e_z, b) per source

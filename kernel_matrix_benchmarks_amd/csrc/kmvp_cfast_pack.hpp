@@ -1,5 +1,5 @@
 // Morton ordering and packing kernels of the centred split-bf16 path (non-template kernels:
-// included by kmvp_product.hip only).  Layouts are documented in kmvp_cfast.hpp.
+// included by kmvp_product.hip only, cfastmm_kernel's packers building on them).  Layouts are documented in kmvp_cfast.hpp.
 #pragma once
 #include "kmvp_cfast.hpp"
 #include "kmvp_fast_pack.hpp"  // aux layout (FAST_AUX_*)
@@ -93,26 +93,8 @@ __device__ __forceinline__ int cfast_pack_group_points(const float* __restrict__
   //      24..31 dim 3 + (0, 0); then 8 bf16 of pad
   __bf16* row = reinterpret_cast<__bf16*>(g + CF_HDR + rr * CF_ROW_BYTES);
   const __bf16 zero = (__bf16)0.f, one = (__bf16)1.f;
-  __bf16 sh, sm, sl;
-  {
-    const float sf = (float)sq;
-    sh = (__bf16)sf;
-    const float r1 = sf - (float)sh;
-    sm = (__bf16)r1;
-    sl = (__bf16)(r1 - (float)sm);
-  }
-  for (int d = 0; d < 4; ++d) {
-    const __bf16 vh = (__bf16)yr[d];
-    const float r1 = yr[d] - (float)vh;
-    const __bf16 vm = (__bf16)r1;
-    const __bf16 vl = (__bf16)(r1 - (float)vm);
-    const __bf16 h2 = (__bf16)(-2.f * (float)vh), m2 = (__bf16)(-2.f * (float)vm), l2 = (__bf16)(-2.f * (float)vl);
-    __bf16* blk = row + 8 * d;
-    blk[0] = h2; blk[1] = h2; blk[2] = m2; blk[3] = h2; blk[4] = m2; blk[5] = l2;
-  }
-  row[6] = live ? sh : (__bf16)INFINITY;
-  row[7] = live ? sm : zero;
-  row[14] = live ? sl : zero;
+  for (int d = 0; d < 4; ++d) fast_row_coord(row + 8 * d, yr[d]);
+  fast_row_norm((float)sq, live, row[6], row[7], row[14]);
   row[15] = one;
   row[22] = one;
   row[23] = one;

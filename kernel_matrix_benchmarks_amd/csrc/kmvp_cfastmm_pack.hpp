@@ -41,8 +41,7 @@ __global__ void pack_cfastmm_signal_kernel(const float* __restrict__ b, const fl
     const int src = perm[k];
     float v = 0.f;
     if (src < m && col < nb) v = col0 + col < E ? b[(int64_t)src * E + col0 + col] * sigma[col] : 1.f;
-    const _Float16 hi = (_Float16)v;
-    out[i] = want_lo ? (_Float16)(v - (float)hi) : hi;
+    out[i] = fmm_signal_piece(v, want_lo);
   }
   *reinterpret_cast<h16x8*>(sig + part * 2048 + g2 * 1024 + lane * 16) = out;
 }

@@ -184,7 +184,6 @@ const char* create_error();
                         std::string(#expr) + ": " + hipGetErrorString(e_));                  \
   } while (0)
 
-inline int64_t round_up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
 inline size_t elem_size(int dtype) { return dtype == KMVP_F64 ? 8 : 4; }
 inline unsigned blocks_for(int64_t n, int threads = 256) { return (unsigned)((n + threads - 1) / threads); }
 

@@ -1,5 +1,5 @@
-// Packing kernels of the split-bf16 MFMA low-D path (non-template kernels: included by
-// kmvp_api.hip only).  Layouts are documented in kmvp_fast.hpp.
+// Packing kernels of the split-bf16 MFMA low-D path (non-template kernels: included by kmvp_product.hip and, for the
+// bounding box, by kmvp_api.hip).  Layouts are documented in kmvp_fast.hpp.
 #pragma once
 #include "kmvp_fast.hpp"
 
@@ -91,6 +91,29 @@ __device__ __forceinline__ void fast_split3(float v, __bf16& hi, __bf16& mid, __
   lo = (__bf16)(r1 - (float)mid);
 }
 
+// The source rows of the split-bf16 expansions (fast, fastmm, cfast, cfastmm).  One coordinate v = h + m + l is six bf16
+// entries -2 v in the order (h, h, m, h, m, l), against the targets' (x_h, x_m, x_h, x_l, x_m, x_h): every product of
+// pieces down to h l and m m.
+__device__ __forceinline__ void fast_row_coord(__bf16* e, float v) {
+  __bf16 vh, vm, vl;
+  fast_split3(v, vh, vm, vl);
+  const __bf16 h2 = (__bf16)(-2.f * (float)vh), m2 = (__bf16)(-2.f * (float)vm), l2 = (__bf16)(-2.f * (float)vl);
+  e[0] = h2;
+  e[1] = h2;
+  e[2] = m2;
+  e[3] = h2;
+  e[4] = m2;
+  e[5] = l2;
+}
+// the three pieces of the squared norm; a pad source (live == false) is infinitely far away
+__device__ __forceinline__ void fast_row_norm(float sq, bool live, __bf16& h, __bf16& m, __bf16& l) {
+  __bf16 sh, sm, sl;
+  fast_split3(sq, sh, sm, sl);
+  h = live ? sh : (__bf16)INFINITY;
+  m = live ? sm : (__bf16)0.f;
+  l = live ? sl : (__bf16)0.f;
+}
+
 // targets [n_pad][RD]: centred scaled coordinates x'_0 .. x'_{D-1}, then |x'|^2 (accumulated in
 // double, rounded once), zeros up to RD = fast_target_row(D); pad targets are all zero.  The
 // kernel splits these into the bf16 operand itself.
@@ -130,21 +153,9 @@ __global__ void pack_fast_sources_kernel(const float* __restrict__ y, const floa
   for (int d = 0; d < D; ++d) {
     const float v = live ? (y[j * D + d] - centre[d]) * scale : 0.f;
     sq += (double)v * (double)v;
-    __bf16 vh, vm, vl;
-    fast_split3(v, vh, vm, vl);
-    const __bf16 h2 = (__bf16)(-2.f * (float)vh), m2 = (__bf16)(-2.f * (float)vm), l2 = (__bf16)(-2.f * (float)vl);
-    row[6 * d + 0] = h2;
-    row[6 * d + 1] = h2;
-    row[6 * d + 2] = m2;
-    row[6 * d + 3] = h2;
-    row[6 * d + 4] = m2;
-    row[6 * d + 5] = l2;
+    fast_row_coord(row + 6 * d, v);
   }
-  __bf16 sh, sm, sl;
-  fast_split3((float)sq, sh, sm, sl);
-  row[6 * D + 0] = live ? sh : (__bf16)INFINITY;
-  row[6 * D + 1] = live ? sm : zero;
-  row[6 * D + 2] = live ? sl : zero;
+  fast_row_norm((float)sq, live, row[6 * D + 0], row[6 * D + 1], row[6 * D + 2]);
   row[6 * D + 3] = one;
   row[6 * D + 4] = one;
   row[6 * D + 5] = one;

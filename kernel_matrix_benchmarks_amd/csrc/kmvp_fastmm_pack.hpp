@@ -26,21 +26,9 @@ __global__ void pack_fastmm_rows_kernel(const float* __restrict__ y, const float
   for (int d = 0; d < D; ++d) {
     const float v = live ? (dot ? y[j * D + d] * scale : (y[j * D + d] - centre[d]) * scale) : 0.f;
     if (!dot) sq += (double)v * (double)v;
-    __bf16 vh, vm, vl;
-    fast_split3(v, vh, vm, vl);
-    const __bf16 h2 = (__bf16)(-2.f * (float)vh), m2 = (__bf16)(-2.f * (float)vm), l2 = (__bf16)(-2.f * (float)vl);
-    row[6 * d + 0] = h2;
-    row[6 * d + 1] = h2;
-    row[6 * d + 2] = m2;
-    row[6 * d + 3] = h2;
-    row[6 * d + 4] = m2;
-    row[6 * d + 5] = l2;
+    fast_row_coord(row + 6 * d, v);
   }
-  __bf16 sh, sm, sl;
-  fast_split3((float)sq, sh, sm, sl);
-  row[6 * D + 0] = live ? sh : (__bf16)INFINITY;
-  row[6 * D + 1] = live ? sm : zero;
-  row[6 * D + 2] = live ? sl : zero;
+  fast_row_norm((float)sq, live, row[6 * D + 0], row[6 * D + 1], row[6 * D + 2]);
   row[6 * D + 3] = one;
   row[6 * D + 4] = one;
   row[6 * D + 5] = one;
@@ -135,6 +123,12 @@ __global__ void __launch_bounds__(256) fastmm_colscale_kernel(const float* __res
   }
 }
 
+// One entry of a signal operand: the f16 high piece of v = b sigma_e, or -- want_lo -- its f16 rest (v = b_h + b_l)
+__device__ __forceinline__ _Float16 fmm_signal_piece(float v, bool want_lo) {
+  const _Float16 hi = (_Float16)v;
+  return want_lo ? (_Float16)(v - (float)hi) : hi;
+}
+
 // the signal part of the stage image.  One thread per 16-byte operand piece: (tile, part, k-step g2, lane); lane
 // (m = lane & 31, h = lane >> 5) element i holds source row 8 (2 g2 + (i >> 2)) + 4 h + (i & 3) of the tile -- the order
 // in which the lane's registers of the S tile hold the sources (acc_row) -- of
@@ -162,8 +156,7 @@ __global__ void pack_fastmm_signal_kernel(const float* __restrict__ b, const flo
     const int64_t j = t * FAST_TILE + 8 * (2 * g2 + (i >> 2)) + 4 * h + (i & 3);
     float v = 0.f;
     if (j < m && col < nb) v = col0 + col < E ? b[j * E + col0 + col] * sigma[col] : 1.f;
-    const _Float16 hi = (_Float16)v;
-    out[i] = want_lo ? (_Float16)(v - (float)hi) : hi;
+    out[i] = fmm_signal_piece(v, want_lo);
   }
   *reinterpret_cast<h16x8*>(tile + FAST_TILE * fmm_row_bytes(KS) + part * 2048 + g2 * 1024 + lane * 16) = out;
 }

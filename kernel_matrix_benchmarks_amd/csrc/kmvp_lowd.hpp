@@ -31,6 +31,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kmvp_plan.hpp"  // WAVES_PER_BLOCK and the other constants the launch plans share with the kernels
+
 namespace kmvp {
 
 enum : int { K_GAUSSIAN = 0, K_ABSEXP = 1, K_INVDIST = 2, K_EXPDOT = 3, K_GAUSSIAN_SHIFTED = 4 };
@@ -154,7 +156,7 @@ __device__ __forceinline__ void block_to_work(int bid, int segments, int tile_bl
   }
 }
 
-constexpr int WAVES_PER_BLOCK = 4;
+// WAVES_PER_BLOCK: kmvp_plan.hpp
 constexpr int BLOCK_THREADS = 64 * WAVES_PER_BLOCK;
 constexpr int LDS_TILE = 256;  // source records per LDS tile (FEED 1)
 

@@ -1,0 +1,246 @@
+// Launch plans of the product: how (N, M, stage size) become padded sizes, segments and a grid, and how sorted cell keys
+// become tile lists.  Pure functions of numbers -- no HIP, no context -- so that they compile into kmvp_product.hip and,
+// with a host compiler alone, into tests/test_host_plan.py.  The segment count decides the order of the fp64 partial sums
+// (bitwise results) and the L2 behaviour (speed); the tile lists are what the cell kernels index without a bounds check.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+namespace kmvp {
+
+constexpr int WAVES_PER_BLOCK = 4;
+constexpr int CELL_TILE = 32;                     // points per tile of the float32 cell lists
+constexpr int CELL_REST_TT = 2;                   // tiles per wavefront of the cell kernels' second launch (the REST list)
+constexpr int STAGED_TILE = 32;                   // targets per tile of the staged matrix-core paths (FAST_TILE)
+constexpr int64_t SMALL_PROBLEM_TARGETS = 32768;  // below: one target tile per wave, one stage per segment
+constexpr int SEG_SPLIT_FROM = 16;                // segments from which the reductions split a sum over SEG_SPLIT lanes
+constexpr int64_t MAX_GRID = 0x7fffffff;          // workgroups of one launch
+
+inline int64_t round_up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
+// Few targets (the reference's own datasets have n <= 1e4): one tile per wave and segments of a single stage spread a
+// launch over more CUs; from ~3e4 targets on the big tiles win, in longer segments.
+inline bool small_problem(int64_t N) { return N < SMALL_PROBLEM_TARGETS; }
+
+// ---- segments ----------------------------------------------------------------------------------------------------
+
+// What a path decides about its segments; everything else follows from the problem's size.
+struct SegmentRule {
+  int64_t stage_bytes;               // bytes of source image per unit (a stage, a record)
+  int cols;                          // columns of fp64 partial sums per segment
+  int64_t min_seg = 1;               // shortest segment, in units (the staged and cell plans: on big problems)
+  bool small = false;                // few targets: about two rounds of resident blocks (4096 workgroups) are aimed at
+  int64_t l2_seg_bytes = 2 << 20;    // L2 budget of one segment
+  int64_t target_blocks = 16384;     // workgroups aimed at otherwise
+  SegmentRule(int64_t stage_bytes_, int cols_) : stage_bytes(stage_bytes_), cols(cols_) {}
+};
+
+// Number of source segments of a launch (specialised kernels).  Three pulls:
+//  * L2 residency: with segments % 8 == 0 each XCD streams one segment at a time
+//    (block_to_work), so a segment of <= 2 MiB of records stays in its 4 MiB L2;
+//  * parallelism: tile_blocks * segments should be many rounds of the 2048 resident
+//    blocks (256 CUs x 8), which only matters when there are few target tiles;
+//  * the fp64 partial buffer segments * cols * n_pad * 8 bytes stays bounded.
+// opt_segments > 0 (the "segments" option) overrides the rule.
+inline int choose_segments(int opt_segments, int64_t tile_blocks, int64_t units, int64_t n_pad, const SegmentRule& r) {
+  int64_t seg;
+  if (opt_segments > 0) {
+    seg = opt_segments;
+  } else {
+    seg = 8 * std::max<int64_t>(1, (units * r.stage_bytes + 8 * r.l2_seg_bytes - 1) / (8 * r.l2_seg_bytes));
+    const int64_t target_blocks = r.small ? 4096 : r.target_blocks;  // small problems: about two rounds of resident blocks
+    const int64_t for_parallelism = (target_blocks + tile_blocks - 1) / tile_blocks;
+    if (for_parallelism > seg) seg = (for_parallelism + 7) / 8 * 8;
+    const int64_t cap_len = std::max<int64_t>(1, units / r.min_seg);  // segment >= min_seg units
+    const int64_t cap_mem = std::max<int64_t>(1, (int64_t)(4e9 / ((double)r.cols * n_pad * 8)));
+    seg = std::min(seg, std::min(cap_len, cap_mem));
+    if (seg >= 8) seg = seg / 8 * 8;
+  }
+  seg = std::max<int64_t>(1, std::min<int64_t>(seg, 65535));
+  return (int)seg;
+}
+
+// Segments are whole numbers of `units` (stages, tiles): `seg` requested segments become ceil(units / ceil(units / seg)),
+// which may be one or two fewer -- and no longer a multiple of 8.  block_to_work() streams one segment per XCD at a time only
+// when the count IS a multiple of 8 (measured, cfast_kernel at 2e5 points: 23 segments 5.65 ms, 16: 5.05, 32: 4.94), so the
+// nearest multiple of 8 that survives the rounding is taken (the request itself below 8).
+inline int settle_segments(int64_t units, int seg) {
+  auto settled = [&](int64_t cand) { return (units + (units + cand - 1) / cand - 1) / ((units + cand - 1) / cand); };
+  if (seg >= 8 && units >= 8)
+    for (int step = 0; step <= 64; step += 8)
+      for (int64_t cand : {(int64_t)seg + step, (int64_t)seg - step})
+        if (cand >= 8 && cand <= units && cand % 8 == 0 && settled(cand) == cand) return (int)cand;
+  seg = (int)std::max<int64_t>(1, std::min<int64_t>(seg, std::max<int64_t>(units, 1)));
+  return (int)settled(seg);
+}
+
+// segments of whole stages: the rule's choice, settled
+inline int stage_segments(int opt_segments, int64_t tile_blocks, int64_t m_stages, int64_t n_pad, const SegmentRule& r) {
+  return settle_segments(m_stages, choose_segments(opt_segments, tile_blocks, m_stages, n_pad, r));
+}
+
+// ---- the staged matrix-core paths (fast, fastmm, cfast, cfastmm) -----------------------------------------------------
+
+// Targets in workgroups of WAVES_PER_BLOCK wavefronts x TT tiles of 32; sources in m_stages stages, cut into segments of
+// seg_stages stages; one workgroup per (target block, segment).  ok == false: more workgroups than a launch takes.
+// TT: as requested (opt_tiles > 0, the "fast_tiles" option) up to tt_max, else 1 for few targets, else tt_default.
+// Segments: r with single stages for few targets, at least r.min_seg stages otherwise.
+struct StagePlan {
+  int64_t n_pad, tile_blocks, m_stages, seg_stages, grid;
+  int TT, segments;
+  bool ok;
+};
+inline StagePlan plan_stages(int64_t N, int64_t m_stages, int opt_tiles, int tt_max, int tt_default, int opt_segments,
+                             SegmentRule r) {
+  StagePlan p;
+  r.small = small_problem(N);
+  if (r.small) r.min_seg = 1;
+  p.TT = opt_tiles > 0 ? std::min(opt_tiles, tt_max) : (r.small ? 1 : std::min(tt_default, tt_max));
+  const int64_t tile = (int64_t)STAGED_TILE * p.TT * WAVES_PER_BLOCK;
+  p.n_pad = round_up(N, tile);
+  p.tile_blocks = p.n_pad / tile;
+  p.m_stages = m_stages;
+  p.segments = stage_segments(opt_segments, p.tile_blocks, m_stages, p.n_pad, r);
+  p.seg_stages = (m_stages + p.segments - 1) / p.segments;
+  p.grid = p.tile_blocks * p.segments;
+  p.ok = p.grid <= MAX_GRID;
+  return p;
+}
+
+// ---- tile lists of the cell paths -------------------------------------------------------------------------------------
+
+// f(first, count, key) for every run of equal keys in the sorted sequence
+template <class F>
+void for_each_key_run(const unsigned* keys, int64_t n, F&& f) {
+  for (int64_t p = 0; p < n;) {
+    int64_t e = p + 1;
+    while (e < n && keys[e] == keys[p]) ++e;
+    f(p, e - p, keys[p]);
+    p = e;
+  }
+}
+
+// A list of tiles: [start][count][key] per tile, the device layout being the three arrays one after the other.
+struct TileList {
+  std::vector<int> start, count;
+  std::vector<unsigned> key;
+  size_t size() const { return start.size(); }
+  void reserve(size_t tiles) {
+    start.reserve(tiles);
+    count.reserve(tiles);
+    key.reserve(tiles);
+  }
+  // `live` tiles of <= tile points covering [at, end) of a cell that starts at `first`, then `empty` tiles of no point
+  void add_cell(int64_t first, int64_t at, int64_t end, unsigned k, int64_t live, int64_t empty, int tile) {
+    for (int64_t t = 0; t < live; ++t, at += tile) push((int)at, (int)std::min<int64_t>(tile, end - at), k);
+    for (int64_t t = 0; t < empty; ++t) push((int)first, 0, k);
+  }
+  void pad_to(size_t mult) {  // empty tiles that repeat the preceding key
+    while (!start.empty() && start.size() % mult) push(start.back(), 0, key.back());
+  }
+  void append(const TileList& o) {
+    start.insert(start.end(), o.start.begin(), o.start.end());
+    count.insert(count.end(), o.count.begin(), o.count.end());
+    key.insert(key.end(), o.key.begin(), o.key.end());
+  }
+
+ private:
+  void push(int s, int c, unsigned k) {
+    start.push_back(s);
+    count.push_back(c);
+    key.push_back(k);
+  }
+};
+
+// Tiles of <= `tile` points that never straddle a cell.
+inline TileList cell_tiles(const unsigned* keys, int64_t n, int tile = CELL_TILE) {
+  TileList l;
+  l.reserve((size_t)n / 24 + 16);
+  for_each_key_run(keys, n, [&](int64_t p, int64_t cnt, unsigned k) { l.add_cell(p, p, p + cnt, k, (cnt + tile - 1) / tile, 0, tile); });
+  return l;
+}
+
+// Target tiles of the float32 cell kernels, in TWO lists.  A wavefront owns TT tiles of ONE cell, so a cell of `tiles`
+// tiles used to be padded to a multiple of TT with empty tiles -- at the headline shape (cells of 1000 +- 32 points: 32
+// tiles, or 33-34 for a fifth of them) 5.6 % of all tile pairs were such padding, and the kernel is bound by the matrix
+// pipe.  Now a cell's tiles are split: whole groups of TT go to the MAIN list; a remainder of at most TT/2 tiles goes to
+// the REST list in groups of two (a larger remainder is still padded to a whole group: the second launch with two tiles
+// per wavefront is ~1.6x less efficient per tile).
+struct CellTiles {
+  int64_t main_live, main_empty, rest_live, rest_empty;
+};
+inline CellTiles split_cell_tiles(int64_t tiles, int TT) {
+  const int64_t rem = tiles % TT;
+  if (TT > CELL_REST_TT && rem > 0 && rem <= TT / 2) return {tiles - rem, 0, rem, round_up(rem, CELL_REST_TT) - rem};
+  return {tiles, round_up(tiles, TT) - tiles, 0, 0};
+}
+
+// Tiles of the two lists for groups of TT, before the padding to whole workgroups
+inline void cell_split_count(const unsigned* keys, int64_t n, int TT, int64_t* n_main, int64_t* n_rest) {
+  *n_main = *n_rest = 0;
+  for_each_key_run(keys, n, [&](int64_t, int64_t cnt, unsigned) {
+    const CellTiles s = split_cell_tiles((cnt + CELL_TILE - 1) / CELL_TILE, TT);
+    *n_main += s.main_live + s.main_empty;
+    *n_rest += s.rest_live + s.rest_empty;
+  });
+}
+
+// Both lists, each padded to whole workgroups (4 wavefronts) with empty tiles, in one list: n_main tiles, then n_rest.
+inline TileList cell_tiles_split(const unsigned* keys, int64_t n, int TT, int64_t* n_main, int64_t* n_rest) {
+  TileList main, rest;
+  main.reserve((size_t)n / 24 + 64);
+  for_each_key_run(keys, n, [&](int64_t p, int64_t cnt, unsigned k) {
+    const CellTiles s = split_cell_tiles((cnt + CELL_TILE - 1) / CELL_TILE, TT);
+    main.add_cell(p, p, p + cnt, k, s.main_live, s.main_empty, CELL_TILE);
+    rest.add_cell(p, p + s.main_live * CELL_TILE, p + cnt, k, s.rest_live, s.rest_empty, CELL_TILE);
+  });
+  main.pad_to((size_t)TT * WAVES_PER_BLOCK);
+  rest.pad_to((size_t)CELL_REST_TT * WAVES_PER_BLOCK);
+  *n_main = (int64_t)main.size();
+  *n_rest = (int64_t)rest.size();
+  main.append(rest);
+  return main;
+}
+
+// The two launches of the float32 cell kernels over the lists of cell_tiles_split(): r = 0 the MAIN list (groups of tt
+// tiles per wavefront), r = 1 the REST list (the cells' leftover tiles, two per wavefront -- few workgroups, latency-bound
+// each, so its own, finer split of the sources).  Each launch has its own segments and its own region
+// [segment][cols][slots] of the partial sums.
+struct CellSplit {
+  int64_t m_stages, n_slots;  // source stages; target slots of both lists
+  int64_t blocks[2], slots[2], seg_stages[2];
+  int segments[2];
+  int64_t grid(int r) const { return blocks[r] * segments[r]; }
+  size_t region_offset(int cols, int r) const { return r ? (size_t)segments[0] * cols * slots[0] : 0; }  // in doubles
+  size_t part_doubles(int cols) const { return ((size_t)segments[0] * slots[0] + (size_t)segments[1] * slots[1]) * cols; }
+};
+
+// N targets in n_main / n_rest tiles; m_tiles source tiles in stages of stage_tiles; `main`: the rule of the main launch
+// (single stages for few targets, as plan_stages)
+inline CellSplit cell_split(int64_t N, int64_t m_tiles, int64_t n_main, int64_t n_rest, int tt, int opt_segments,
+                            int stage_tiles, SegmentRule main) {
+  CellSplit s;
+  main.small = small_problem(N);
+  if (main.small) main.min_seg = 1;
+  s.m_stages = (m_tiles + stage_tiles - 1) / stage_tiles;
+  s.n_slots = (n_main + n_rest) * CELL_TILE;
+  s.blocks[0] = n_main / (tt * WAVES_PER_BLOCK);
+  s.blocks[1] = n_rest / (CELL_REST_TT * WAVES_PER_BLOCK);
+  s.slots[0] = n_main * CELL_TILE;
+  s.slots[1] = n_rest * CELL_TILE;
+  s.segments[0] = stage_segments(opt_segments, std::max<int64_t>(1, s.blocks[0]), s.m_stages, s.n_slots, main);
+  s.seg_stages[0] = (s.m_stages + s.segments[0] - 1) / s.segments[0];
+  s.segments[1] = 0;
+  s.seg_stages[1] = 1;
+  if (s.blocks[1] > 0) {
+    SegmentRule rest = main;  // single stages allowed, ~1536 workgroups
+    rest.min_seg = 1;
+    rest.target_blocks = 1536;
+    const int seg = choose_segments(opt_segments, s.blocks[1], s.m_stages, s.n_slots, rest);
+    s.seg_stages[1] = (s.m_stages + seg - 1) / seg;
+    s.segments[1] = (int)((s.m_stages + s.seg_stages[1] - 1) / s.seg_stages[1]);
+  }
+  return s;
+}
+
+}  // namespace kmvp

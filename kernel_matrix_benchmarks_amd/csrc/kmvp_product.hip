@@ -96,8 +96,7 @@ real scale_for(int kernel) {
 // product): SEG_SPLIT consecutive lanes share a sum -- lane g takes the segments s = g (mod SEG_SPLIT) in index order, a
 // butterfly over the group adds the eight partial sums.  A fixed order either way: results stay bitwise reproducible, and
 // reduce_segments_kernel (the exchange path) and reduce_finish_kernel (the plain one) add in the SAME order.
-constexpr int SEG_SPLIT = 8;
-constexpr int SEG_SPLIT_FROM = 16;  // segments from which the split form is taken
+constexpr int SEG_SPLIT = 8;  // (taken from SEG_SPLIT_FROM segments on: kmvp_plan.hpp)
 __device__ __forceinline__ double seg_sum_one(const double* __restrict__ part, int64_t stride, int64_t q, int segments) {
   double v = 0.0;
   for (int s = 0; s < segments; ++s) v += part[(int64_t)s * stride + q];
@@ -403,46 +402,6 @@ int reduce_and_finish(kmvp_ctx* c, int segments, int NE, int64_t N, int64_t n_pa
   return complete(c, N, E);
 }
 
-// Number of source segments of a launch (specialised kernels).  Three pulls:
-//  * L2 residency: with segments % 8 == 0 each XCD streams one segment at a time
-//    (block_to_work), so a segment of <= 2 MiB of records stays in its 4 MiB L2;
-//  * parallelism: tile_blocks * segments should be many rounds of the 2048 resident
-//    blocks (256 CUs x 8), which only matters when there are few target tiles;
-//  * the fp64 partial buffer segments * NE * n_pad * 8 bytes stays bounded.
-int choose_segments(const kmvp_ctx* c, int64_t tile_blocks, int64_t m_pad, int NE, int64_t n_pad,
-                    int64_t rec_bytes, int64_t min_seg, bool small = false, int64_t l2_seg_bytes = 2 << 20,
-                    int64_t big_target_blocks = 16384) {
-  int64_t seg;
-  if (c->opt_segments > 0) {
-    seg = c->opt_segments;
-  } else {
-    seg = 8 * std::max<int64_t>(1, (m_pad * rec_bytes + 8 * l2_seg_bytes - 1) / (8 * l2_seg_bytes));
-    const int64_t target_blocks = small ? 4096 : big_target_blocks;  // small problems: about two rounds of resident blocks
-    const int64_t for_parallelism = (target_blocks + tile_blocks - 1) / tile_blocks;
-    if (for_parallelism > seg) seg = (for_parallelism + 7) / 8 * 8;
-    const int64_t cap_len = std::max<int64_t>(1, m_pad / min_seg);              // segment >= min_seg sources
-    const int64_t cap_mem = std::max<int64_t>(1, (int64_t)(4e9 / ((double)NE * n_pad * 8)));
-    seg = std::min(seg, std::min(cap_len, cap_mem));
-    if (seg >= 8) seg = seg / 8 * 8;
-  }
-  seg = std::max<int64_t>(1, std::min<int64_t>(seg, 65535));
-  return (int)seg;
-}
-
-// Segments are whole numbers of `units` (stages, tiles): `seg` requested segments become ceil(units / ceil(units / seg)),
-// which may be one or two fewer -- and no longer a multiple of 8.  block_to_work() streams one segment per XCD at a time only
-// when the count IS a multiple of 8 (measured, cfast_kernel at 2e5 points: 23 segments 5.65 ms, 16: 5.05, 32: 4.94), so the
-// nearest multiple of 8 that survives the rounding is taken (the request itself below 8).
-int settle_segments(int64_t units, int seg) {
-  auto settled = [&](int64_t cand) { return (units + (units + cand - 1) / cand - 1) / ((units + cand - 1) / cand); };
-  if (seg >= 8 && units >= 8)
-    for (int step = 0; step <= 64; step += 8)
-      for (int64_t cand : {(int64_t)seg + step, (int64_t)seg - step})
-        if (cand >= 8 && cand <= units && cand % 8 == 0 && settled(cand) == cand) return (int)cand;
-  seg = (int)std::max<int64_t>(1, std::min<int64_t>(seg, std::max<int64_t>(units, 1)));
-  return (int)settled(seg);
-}
-
 // Geometry of the specialised difference-form kernels (kmvp_lowd.hpp): tiles of 64 T targets per wave, source records of
 // R reals in batches, segments of whole batches, `cols` columns of partial sums per segment.  Everything but the buffers.
 constexpr int64_t LOWD_BATCH = 8;  // two ping-pong batches of 4 records
@@ -455,8 +414,11 @@ LowdArgs<real> lowd_geometry(const kmvp_ctx* c, int T, int R, int cols) {
   a.tile_blocks = (int)(a.n_pad / tile);
   a.m_pad = round_up(std::max<int64_t>(c->M, 1), LOWD_BATCH);
   // few targets: short segments, so that the launch still covers the chip (n = 2000, fp64: 121 -> 9 us)
-  const bool small = c->N < SMALL_PROBLEM_TARGETS;
-  const int segments = choose_segments(c, a.n_pad / tile, a.m_pad, cols, a.n_pad, (int64_t)R * sizeof(real), small ? 32 : 1024, small);
+  const bool small = small_problem(c->N);
+  SegmentRule rule((int64_t)R * sizeof(real), cols);
+  rule.min_seg = small ? 32 : 1024;
+  rule.small = small;
+  const int segments = choose_segments(c->opt_segments, a.n_pad / tile, a.m_pad, a.n_pad, rule);
   a.seg_len = round_up((a.m_pad + segments - 1) / segments, LOWD_BATCH);
   a.segments = (int)((a.m_pad + a.seg_len - 1) / a.seg_len);
   a.chunk = (int)round_up(std::max(c->opt_chunk, 8), LOWD_BATCH);
@@ -549,7 +511,9 @@ int run_product_t(kmvp_ctx* c, int kernel, int sig) {
       c->gen_kernel = kernel;
     }
     const int64_t tile_blocks = n_pad / BLOCK_THREADS;
-    segments = choose_segments(c, tile_blocks, M, NE, n_pad, (int64_t)D * sizeof(real), 256);
+    SegmentRule rule((int64_t)D * sizeof(real), NE);
+    rule.min_seg = 256;
+    segments = choose_segments(c->opt_segments, tile_blocks, M, n_pad, rule);
     const int64_t seg_len = (M + segments - 1) / segments;
     segments = (int)((M + seg_len - 1) / seg_len);
     if ((rc = ensure(c, c->part, (size_t)segments * NE * n_pad * sizeof(double)))) return rc;
@@ -633,6 +597,26 @@ int run_product_blocked(kmvp_ctx* c, int kernel, int sig) {
   return finish_product(c, (int64_t)NE * n_pad, N, n_pad, E, sig);
 }
 
+// ---- the staged matrix-core paths: fast, fastmm, cfast, cfastmm ------------------------------------------------------
+
+static_assert(FAST_TILE == STAGED_TILE, "plan_stages() pads the targets to the kernels' tiles");
+
+// The launch plan of a staged path (kmvp_plan.hpp) for the context's targets and options -- up to tt_max tiles per wave,
+// tt_default on big problems, segments of at least four stages there -- refused when no launch takes its grid.
+int stage_plan(kmvp_ctx* c, int64_t m_stages, int tt_max, int tt_default, SegmentRule rule, StagePlan& p) {
+  rule.min_seg = 4;
+  p = plan_stages(c->N, m_stages, c->opt_fast_tiles, tt_max, tt_default, c->opt_segments, rule);
+  return p.ok ? KMVP_OK : fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
+}
+template <class Args>
+void plan_args(const StagePlan& p, Args& a) {
+  a.n_pad = p.n_pad;
+  a.m_stages = p.m_stages;
+  a.seg_stages = p.seg_stages;
+  a.segments = p.segments;
+  a.tile_blocks = (int)p.tile_blocks;
+}
+
 // split-bf16 MFMA low-D path (kmvp_fast.hpp): float32, D <= 7, E == 1, selected by the
 // "fast_sqdists" option (the reference's constructor flag of the same name).
 int run_product_fast(kmvp_ctx* c, int kernel, int sig) {
@@ -642,25 +626,18 @@ int run_product_fast(kmvp_ctx* c, int kernel, int sig) {
   const int EB = sig == SIG_DENSITY ? 0 : 1;
   const int64_t N = c->N, M = c->M;
   const int KS = fast_ksteps(D);
-  // few targets (the reference's own datasets have n <= 1e4): one tile per wave and segments of a
-  // single stage spread the launch over more CUs; from ~3e4 targets on the big tiles win
-  const bool small = N < SMALL_PROBLEM_TARGETS;
   const int tt_max = D > FAST_MAX_D_TWO_TILES ? 1 : (D > FAST_MAX_D_FOUR_TILES ? 2 : 4);  // what is instantiated
-  const int TT = c->opt_fast_tiles > 0 ? std::min(c->opt_fast_tiles, tt_max) : (small ? 1 : std::min(FAST_DEFAULT_TT, tt_max));
   const int64_t SB = fast_stage_bytes(KS, EB);
   const float scale = scale_for<float>(kernel);
   const float* x_raw = (const float*)(c->same_points ? c->y_raw.p : c->x_raw.p);
-  const int64_t tile = (int64_t)FAST_TILE * TT * WAVES_PER_BLOCK;
-  const int64_t n_pad = round_up(N, tile);
-  const int64_t tile_blocks = n_pad / tile;
   const int64_t m_tiles = (M + FAST_TILE - 1) / FAST_TILE;
   const int ST = fast_stage_tiles(KS);
-  const int64_t m_stages = (m_tiles + ST - 1) / ST;
   int rc;
 
-  int segments = choose_segments(c, tile_blocks, m_stages, NE, n_pad, SB, small ? 1 : 4, small);
-  segments = settle_segments(m_stages, segments);
-  const int64_t seg_stages = (m_stages + segments - 1) / segments;
+  StagePlan p;
+  if ((rc = stage_plan(c, (m_tiles + ST - 1) / ST, tt_max, FAST_DEFAULT_TT, SegmentRule(SB, NE), p))) return rc;
+  const int64_t n_pad = p.n_pad, m_stages = p.m_stages;
+  const int TT = p.TT;
 
   const PackKey key = {LAYOUT_FAST, kernel, TT};
   float* centre = (float*)c->aux.p;  // written by kmvp_set_points
@@ -679,39 +656,103 @@ int run_product_fast(kmvp_ctx* c, int kernel, int sig) {
   HIP_TRY(c, hipGetLastError());
   record_packed(c, key, sig);
 
-  if ((rc = ensure(c, c->part, (size_t)segments * NE * n_pad * sizeof(double)))) return rc;
+  if ((rc = ensure(c, c->part, (size_t)p.segments * NE * n_pad * sizeof(double)))) return rc;
   FastArgs a;
+  plan_args(p, a);
   a.xr = (const float*)c->xs.p;
   a.img = (const unsigned char*)c->rec.p;
   a.part = (double*)c->part.p;
-  a.n_pad = n_pad;
   a.m_tiles = m_tiles;
-  a.m_stages = m_stages;
-  a.seg_stages = seg_stages;
-  a.segments = segments;
-  a.tile_blocks = (int)tile_blocks;
   a.chunk_stages = std::max(1, c->opt_chunk / (FAST_TILE * ST));
   a.j_offset = c->j_offset;
   a.m_total = c->m_total;
   a.same_points = (c->same_points || c->opt_same_global) ? 1 : 0;
-  const dim3 grid((unsigned)(tile_blocks * segments));
+  const dim3 grid((unsigned)p.grid);
   HIP_TRY(c, mark(c, 0));
-  hipError_t le;
-  switch (kernel) {
-    case K_GAUSSIAN: le = launch_fast_gaussian(D, sig, TT, a, grid, c->stream, &c->last_kernel_name); break;
-    case K_ABSEXP: le = launch_fast_absexp(D, sig, TT, a, grid, c->stream, &c->last_kernel_name); break;
-    default: le = launch_fast_invdist(D, sig, TT, a, grid, c->stream, &c->last_kernel_name); break;
-  }
+  const auto launch = kernel == K_GAUSSIAN ? launch_fast_gaussian : (kernel == K_ABSEXP ? launch_fast_absexp : launch_fast_invdist);
+  const hipError_t le = launch(D, sig, TT, a, grid, c->stream, &c->last_kernel_name);
   if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "fast_tiles must be 1, 2 or 4");
   HIP_TRY(c, le);
   HIP_TRY(c, mark(c, 1));
 
   // ---- epilogue: segments -> sums, [all-reduce over the source shards], normalise
-  return reduce_and_finish(c, segments, NE, N, n_pad, E, sig);
+  return reduce_and_finish(c, p.segments, NE, N, n_pad, E, sig);
+}
+
+// The column blocks of the matrix-core column products (fastmm_kernel, cfastmm_kernel): NE columns -- the denominator of
+// normalised rows being one more column -- in blocks of up to FMM_MAX_COLS.  The signal part of the source image holds
+// ONE block, so with several blocks it is re-packed on every pass and never reusable as it is (image_sig = -1).
+// sigma / unscale: the current block's column scales (fastmm_colscale_kernel), kept in c->cell_scale behind the slots
+// cellmm_kernel uses there.
+struct ColumnBlocks {
+  int NE, image_sig;
+  bool one_block, sig_stale;
+  float* sigma;
+  double* unscale;
+};
+// (before the points are packed and the image is recorded: sig_stale is about what the buffers held on entry)
+int column_blocks(kmvp_ctx* c, PackKey key, int sig, ColumnBlocks& cb) {
+  int rc;
+  cb.NE = sig == SIG_NORM ? c->E + 1 : c->E;
+  cb.one_block = cb.NE <= FMM_MAX_COLS;
+  cb.image_sig = cb.one_block ? sig : -1;
+  cb.sig_stale = signal_stale(c, key, cb.image_sig);
+  if ((rc = ensure(c, c->cell_scale, 1024))) return rc;
+  cb.sigma = (float*)((char*)c->cell_scale.p + 256);
+  cb.unscale = (double*)((char*)c->cell_scale.p + 512);
+  return KMVP_OK;
+}
+
+// One pass of the pair loop per block: [column scales, pack_signal(col0, nb)] when the image is stale, launch(nb, part),
+// and -- several blocks, or partial sums that carry exponents (shifted) -- the block's segments summed into c->sums.
+// Then the tail: the shifted one (finish_product_shifted), the fused reduce + finish of a single block, or finish_product.
+// `note`: the dispatch note of a pass that ran (nullptr: none).
+template <class PackSignal, class Launch>
+int run_column_blocks(kmvp_ctx* c, PackKey key, int sig, const StagePlan& p, const ColumnBlocks& cb, bool shifted,
+                      const char* note, PackSignal pack_signal, Launch launch) {
+  const int E = c->E, NE = cb.NE;
+  const int64_t n_pad = p.n_pad;
+  int rc;
+  record_packed(c, key, cb.image_sig);
+  if ((rc = ensure(c, c->part, (size_t)p.segments * std::min(NE, FMM_MAX_COLS) * n_pad * sizeof(double)))) return rc;
+  if ((!cb.one_block || shifted) && (rc = ensure(c, c->sums, (size_t)NE * n_pad * sizeof(double)))) return rc;
+  if (shifted) {
+    if ((rc = ensure(c, c->kexp, (size_t)p.segments * n_pad * sizeof(float)))) return rc;
+    if ((rc = ensure(c, c->kshift, (size_t)n_pad * sizeof(double)))) return rc;
+  }
+  HIP_TRY(c, mark(c, 0));
+  for (int col0 = 0; col0 < NE; col0 += FMM_MAX_COLS) {
+    const int nb = std::min(FMM_MAX_COLS, NE - col0);
+    if (cb.sig_stale) {
+      hipLaunchKernelGGL(fastmm_colscale_kernel, dim3(FMM_MAX_COLS), dim3(256), 0, c->stream, (const float*)c->b_raw.p,
+                         c->M, E, col0, nb, cb.sigma, cb.unscale);
+      pack_signal(col0, nb);
+      HIP_TRY(c, hipGetLastError());
+    }
+    if ((rc = launch(nb))) return rc;
+    // signal columns of the block; the one beyond them is the denominator (col0 <= E: never negative)
+    const int Ek = std::min(nb, E - col0);
+    const dim3 blocks(blocks_for((int64_t)nb * n_pad));
+    if (shifted) {
+      // (every pass runs the same distances in the same order: its exponents are the previous pass's, bit for bit)
+      hipLaunchKernelGGL(reduce_shifted_kernel, blocks, dim3(256), 0, c->stream, (const double*)c->part.p,
+                         (const float*)c->kexp.p, (double*)c->sums.p, (double*)c->kshift.p, n_pad, nb, Ek, p.segments, col0, E);
+      HIP_TRY(c, hipGetLastError());
+    } else if (!cb.one_block) {
+      hipLaunchKernelGGL(reduce_block_kernel, blocks, dim3(256), 0, c->stream, (const double*)c->part.p,
+                         (double*)c->sums.p, n_pad, nb, Ek, p.segments, col0, E);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
+  HIP_TRY(c, mark(c, 1));
+  if (note) c->note = note;
+  if (shifted) return finish_product_shifted(c, c->N, n_pad, E, sig);
+  if (cb.one_block) return reduce_and_finish(c, p.segments, NE, c->N, n_pad, E, sig);
+  return finish_product(c, (int64_t)NE * n_pad, c->N, n_pad, E, sig);
 }
 
 // Gaussian products with several signal columns, both matrix products on the matrix cores (kmvp_fastmm.hpp): float32,
-// D <= 64, any E (blocks of up to 32 columns, the denominator of normalised rows being one more column).
+// D <= 64, any E (column blocks as above).
 // dot: k = exp(<x,y>) -- the Gaussian instantiation on operands without norms (S = -log2(e) <x,y>), always with the
 // online shift, partial sums as (mantissa, exponent) pairs (FastmmArgs::kexp) and the shifted tail.
 int run_product_fastmm(kmvp_ctx* c, int kernel, int sig, bool dot = false) {
@@ -720,19 +761,13 @@ int run_product_fastmm(kmvp_ctx* c, int kernel, int sig, bool dot = false) {
   const int64_t N = c->N, M = c->M;
   const int KS = fmm_ksteps(D);
   const int MODE = NE > 16 ? 1 : 0;
-  const bool small = N < SMALL_PROBLEM_TARGETS;
   const int tt_max = KS <= FMM_MAX_KS_TWO_TILES ? 2 : 1;  // (four tiles: no faster, 256 VGPRs)
-  const int TT = c->opt_fast_tiles > 0 ? std::min(c->opt_fast_tiles, tt_max) : (small ? 1 : tt_max);
   const int64_t SB = fmm_stage_bytes(KS, MODE);
+  const int ST = fmm_stage_tiles(KS);
   // dot: the source rows hold -2 (y scale), so scale = log2(e) / 2 gives S = -log2(e) <x, y>
   const float scale = dot ? 0.72134752044448170f : scale_for<float>(kernel);
   const float* x_raw = (const float*)(c->same_points ? c->y_raw.p : c->x_raw.p);
-  const int64_t tile = (int64_t)FAST_TILE * TT * WAVES_PER_BLOCK;
-  const int64_t n_pad = round_up(N, tile);
-  const int64_t tile_blocks = n_pad / tile;
   const int64_t m_tiles = (M + FAST_TILE - 1) / FAST_TILE;
-  const int64_t m_stages = (m_tiles + fmm_stage_tiles(KS) - 1) / fmm_stage_tiles(KS);
-  const int nb_max = std::min(NE, FMM_MAX_COLS);
   // the fixed shift 2^15 assumes every target has a source at distance ~0, i.e. targets == sources (also when the
   // sources are sharded: the all-reduced row then contains the self term); otherwise the per-target running shift
   const int online = (dot || !(c->same_points || c->opt_same_global)) ? 1 : 0;
@@ -740,50 +775,35 @@ int run_product_fastmm(kmvp_ctx* c, int kernel, int sig, bool dot = false) {
 
   // (the kernel's time does not depend on the segment count between 8 and 48 at 1e5 points, the fp64 partial sums --
   // segments x columns x N x 8 bytes -- and their reduction do: about 4096 workgroups instead of 16384)
-  int segments = choose_segments(c, tile_blocks, m_stages, nb_max, n_pad, SB, small ? 1 : 4, small, 2 << 20, 4096);
-  segments = settle_segments(m_stages, segments);
-  const int64_t seg_stages = (m_stages + segments - 1) / segments;
-  if (tile_blocks * segments > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
+  SegmentRule rule(SB, std::min(NE, FMM_MAX_COLS));
+  rule.target_blocks = 4096;
+  StagePlan p;
+  if ((rc = stage_plan(c, (m_tiles + ST - 1) / ST, tt_max, tt_max, rule, p))) return rc;
+  const int64_t n_pad = p.n_pad, m_stages = p.m_stages;
+  const int TT = p.TT;
 
   const PackKey key = {LAYOUT_FASTMM, dot ? K_EXPDOT : kernel, TT + 16 * MODE};
-  const bool one_block = NE <= FMM_MAX_COLS;
-  const int image_sig = one_block ? sig : -1;  // several column blocks: the signal image holds the last one
-  const bool sig_stale = signal_stale(c, key, image_sig);
+  ColumnBlocks cb;
+  if ((rc = column_blocks(c, key, sig, cb))) return rc;
   float* centre = (float*)c->aux.p;  // written by kmvp_set_points
-  if ((rc = ensure(c, c->cell_scale, 1024))) return rc;
-  float* sigma = (float*)((char*)c->cell_scale.p + 256);
-  double* unscale = (double*)((char*)c->cell_scale.p + 512);
   if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)n_pad * KS * 32))) return rc;
     if ((rc = ensure(c, c->rec, (size_t)m_stages * SB))) return rc;
     hipLaunchKernelGGL(pack_fastmm_targets_kernel, dim3(blocks_for(n_pad * KS * 2)), dim3(256), 0, c->stream, x_raw,
                        centre, (unsigned char*)c->xs.p, N, n_pad, D, KS, scale,
                        kernel == K_GAUSSIAN ? (float)FMM_SHIFT : 0.f, dot ? 1 : 0);
-    hipLaunchKernelGGL(pack_fastmm_rows_kernel, dim3(blocks_for(m_stages * fmm_stage_tiles(KS) * FAST_TILE)), dim3(256), 0,
+    hipLaunchKernelGGL(pack_fastmm_rows_kernel, dim3(blocks_for(m_stages * ST * FAST_TILE)), dim3(256), 0,
                        c->stream, (const float*)c->y_raw.p, centre, (unsigned char*)c->rec.p, M, m_stages, D, KS, MODE,
                        scale, dot ? 1 : 0);
     HIP_TRY(c, hipGetLastError());
   }
-  record_packed(c, key, image_sig);
 
-  if ((rc = ensure(c, c->part, (size_t)segments * nb_max * n_pad * sizeof(double)))) return rc;
-  if ((!one_block || dot) && (rc = ensure(c, c->sums, (size_t)NE * n_pad * sizeof(double)))) return rc;
-  if (dot) {
-    if ((rc = ensure(c, c->kexp, (size_t)segments * n_pad * sizeof(float)))) return rc;
-    if ((rc = ensure(c, c->kshift, (size_t)n_pad * sizeof(double)))) return rc;
-  }
   FastmmArgs a;
-  a.kexp = dot ? (float*)c->kexp.p : nullptr;
+  plan_args(p, a);
   a.xop = (const unsigned char*)c->xs.p;
   a.img = (const unsigned char*)c->rec.p;
-  a.unscale = unscale;
-  a.part = (double*)c->part.p;
-  a.n_pad = n_pad;
-  a.m_stages = m_stages;
-  a.seg_stages = seg_stages;
-  a.segments = segments;
-  a.tile_blocks = (int)tile_blocks;
-  a.chunk_stages = std::max(1, 2 * c->opt_chunk / (FAST_TILE * fmm_stage_tiles(KS)));
+  a.unscale = cb.unscale;
+  a.chunk_stages = std::max(1, 2 * c->opt_chunk / (FAST_TILE * ST));
   a.xraw = x_raw;
   a.yraw = (const float*)c->y_raw.p;
   a.n = N;
@@ -794,44 +814,47 @@ int run_product_fastmm(kmvp_ctx* c, int kernel, int sig, bool dot = false) {
     const float r2 = c->cloud_radius2 * scale * scale;  // scaled squared radius of the clouds
     a.tau = kernel == K_ABSEXP ? FMM_ABSEXP_KAPPA * r2 * r2 : 0.f;
   }
-  const dim3 grid((unsigned)(tile_blocks * segments));
-  const int64_t pieces = m_stages * fmm_stage_tiles(KS) * (MODE ? 2 : 1) * 2 * 64;
-  HIP_TRY(c, mark(c, 0));
-  for (int col0 = 0; col0 < NE; col0 += FMM_MAX_COLS) {
-    const int nb = std::min(FMM_MAX_COLS, NE - col0);
-    if (sig_stale) {
-      hipLaunchKernelGGL(fastmm_colscale_kernel, dim3(FMM_MAX_COLS), dim3(256), 0, c->stream, (const float*)c->b_raw.p,
-                         M, E, col0, nb, sigma, unscale);
-      hipLaunchKernelGGL(pack_fastmm_signal_kernel, dim3(blocks_for(pieces)), dim3(256), 0, c->stream,
-                         (const float*)c->b_raw.p, (const float*)sigma, (unsigned char*)c->rec.p, M, m_stages, E, col0,
-                         nb, KS, MODE);
-      HIP_TRY(c, hipGetLastError());
-    }
-    a.NE = nb;
-    hipError_t le = kernel == K_ABSEXP ? launch_fastmm_absexp(KS, MODE, TT, online, a, grid, c->stream, &c->last_kernel_name)
-                                       : launch_fastmm_gaussian(KS, MODE, TT, online, a, grid, c->stream, &c->last_kernel_name);
-    if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "no fastmm_kernel for this dimension / tile count");
-    HIP_TRY(c, le);
-    if (dot) {
-      // (every pass runs the same distances in the same order: its exponents are the previous pass's, bit for bit)
-      const int Ek = std::max(0, std::min(nb, E - col0));
-      hipLaunchKernelGGL(reduce_shifted_kernel, dim3(blocks_for((int64_t)nb * n_pad)), dim3(256), 0, c->stream,
-                         (const double*)c->part.p, (const float*)c->kexp.p, (double*)c->sums.p, (double*)c->kshift.p, n_pad,
-                         nb, Ek, segments, col0, E);
-      HIP_TRY(c, hipGetLastError());
-    } else if (!one_block) {
-      const int Ek = std::min(nb, E - col0);  // signal columns of the block; the one beyond them is the denominator
-      hipLaunchKernelGGL(reduce_block_kernel, dim3(blocks_for((int64_t)nb * n_pad)), dim3(256), 0, c->stream,
-                         (const double*)c->part.p, (double*)c->sums.p, n_pad, nb, Ek, segments, col0, E);
-      HIP_TRY(c, hipGetLastError());
-    }
-  }
-  HIP_TRY(c, mark(c, 1));
-  if (dot) c->note = "exp(<x,y>): fastmm_kernel with the per-target online shift, (mantissa, exponent) partial sums";
-  else if (online) c->note = "fastmm_kernel with the per-target online shift (targets != sources)";
-  if (dot) return finish_product_shifted(c, N, n_pad, E, sig);
-  if (one_block) return reduce_and_finish(c, segments, NE, N, n_pad, E, sig);
-  return finish_product(c, (int64_t)NE * n_pad, N, n_pad, E, sig);
+  const dim3 grid((unsigned)p.grid);
+  const int64_t pieces = m_stages * ST * (MODE ? 2 : 1) * 2 * 64;
+  const char* note = dot      ? "exp(<x,y>): fastmm_kernel with the per-target online shift, (mantissa, exponent) partial sums"
+                     : online ? "fastmm_kernel with the per-target online shift (targets != sources)"
+                              : nullptr;
+  return run_column_blocks(
+      c, key, sig, p, cb, dot, note,
+      [&](int col0, int nb) {
+        hipLaunchKernelGGL(pack_fastmm_signal_kernel, dim3(blocks_for(pieces)), dim3(256), 0, c->stream,
+                           (const float*)c->b_raw.p, (const float*)cb.sigma, (unsigned char*)c->rec.p, M, m_stages, E, col0,
+                           nb, KS, MODE);
+      },
+      [&](int nb) {
+        a.NE = nb;
+        a.part = (double*)c->part.p;
+        a.kexp = dot ? (float*)c->kexp.p : nullptr;
+        hipError_t le = kernel == K_ABSEXP ? launch_fastmm_absexp(KS, MODE, TT, online, a, grid, c->stream, &c->last_kernel_name)
+                                           : launch_fastmm_gaussian(KS, MODE, TT, online, a, grid, c->stream, &c->last_kernel_name);
+        if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "no fastmm_kernel for this dimension / tile count");
+        HIP_TRY(c, le);
+        return (int)KMVP_OK;
+      });
+}
+
+// Scratch of one radix sort of n (key, value) pairs, carved out of c->sortbuf: keys in / out, values in, hipcub's own
+struct SortBufs {
+  unsigned *keys_in, *keys_out;
+  int* vals_in;
+  void* tmp;
+  size_t tmp_bytes;
+};
+int sort_buffers(kmvp_ctx* c, int64_t n, SortBufs& b) {
+  int rc;
+  b.tmp_bytes = 0;
+  HIP_TRY(c, sort_pairs_u32(nullptr, &b.tmp_bytes, nullptr, nullptr, nullptr, nullptr, n, c->stream));
+  if ((rc = ensure(c, c->sortbuf, 3 * (size_t)n * sizeof(unsigned) + b.tmp_bytes + 256))) return rc;
+  b.keys_in = (unsigned*)c->sortbuf.p;
+  b.keys_out = b.keys_in + n;
+  b.vals_in = (int*)(b.keys_out + n);
+  b.tmp = (void*)((((uintptr_t)(b.vals_in + n)) + 255) & ~(uintptr_t)255);
+  return KMVP_OK;
 }
 
 // Morton order of the sources (independent of the kernel; cfast_kernel and cfastmm_kernel): keys -> radix sort -> c->perm
@@ -840,18 +863,12 @@ int morton_order(kmvp_ctx* c, int64_t m_alloc) {
   const float* centre = (const float*)c->aux.p;  // written by measure_clouds()
   if (c->perm_ver == c->points_ver && c->perm.cap >= (size_t)m_alloc * sizeof(int)) return KMVP_OK;
   if ((rc = ensure(c, c->perm, (size_t)m_alloc * sizeof(int)))) return rc;
-  size_t tmp_bytes = 0;
-  HIP_TRY(c, sort_pairs_u32(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, m_alloc, c->stream));
-  const size_t keys_bytes = (size_t)m_alloc * sizeof(unsigned);
-  if ((rc = ensure(c, c->sortbuf, 3 * keys_bytes + tmp_bytes + 256))) return rc;
-  unsigned* keys_in = (unsigned*)c->sortbuf.p;
-  unsigned* keys_out = keys_in + m_alloc;
-  int* vals_in = (int*)(keys_out + m_alloc);
-  void* tmp = (void*)((((uintptr_t)(vals_in + m_alloc)) + 255) & ~(uintptr_t)255);
+  SortBufs b;
+  if ((rc = sort_buffers(c, m_alloc, b))) return rc;
   hipLaunchKernelGGL(cfast_morton_kernel, dim3(blocks_for(m_alloc)), dim3(256), 0, c->stream,
-                     (const float*)c->y_raw.p, centre, keys_in, vals_in, c->M, m_alloc, c->D);
+                     (const float*)c->y_raw.p, centre, b.keys_in, b.vals_in, c->M, m_alloc, c->D);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, sort_pairs_u32(tmp, &tmp_bytes, keys_in, keys_out, vals_in, (int*)c->perm.p, m_alloc, c->stream));
+  HIP_TRY(c, sort_pairs_u32(b.tmp, &b.tmp_bytes, b.keys_in, b.keys_out, b.vals_in, (int*)c->perm.p, m_alloc, c->stream));
   c->perm_ver = c->points_ver;
   c->packed_layout = -1;  // force a re-pack
   return KMVP_OK;
@@ -864,16 +881,9 @@ int run_product_cfast(kmvp_ctx* c, int kernel, int sig) {
   const int NE = sig == SIG_NORM ? 2 : 1;
   const int EB = sig == SIG_DENSITY ? 0 : 1;
   const int64_t N = c->N, M = c->M;
-  const bool small = N < SMALL_PROBLEM_TARGETS;  // see run_product_fast
-  const int TT = c->opt_fast_tiles > 0 ? std::min(c->opt_fast_tiles, 4) : (small ? 1 : CFAST_DEFAULT_TT);
   const float scale = scale_for<float>(kernel);
   const float* x_raw = (const float*)(c->same_points ? c->y_raw.p : c->x_raw.p);
-  const int64_t tile = (int64_t)32 * TT * WAVES_PER_BLOCK;
-  const int64_t n_pad = round_up(N, tile);
-  const int64_t tile_blocks = n_pad / tile;
   const int64_t per_stage = (int64_t)CF_GROUP * CF_STAGE_GROUPS;
-  const int64_t m_stages = (M + per_stage - 1) / per_stage;
-  const int64_t m_alloc = m_stages * per_stage;
   if (c->m_total > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "more than 2^31 sources");
   int rc;
 
@@ -881,9 +891,13 @@ int run_product_cfast(kmvp_ctx* c, int kernel, int sig) {
   // 1e7 x 1.25e6 points (tools/c4_segments.py: 117.2 / 116.5 ms, 1442 / 1447 ms), and every segment costs N x 16 bytes of
   // partial sums written and read back -- config 4's shard: 48 -> 8 segments, 7.7 -> 1.3 GB.  Few targets still get more
   // segments for parallelism (2e5 points: 16).
-  int segments = choose_segments(c, tile_blocks, m_stages, NE, n_pad, CF_STAGE_BYTES, small ? 1 : 4, small, 2 << 20, 24576);
-  segments = settle_segments(m_stages, segments);
-  const int64_t seg_stages = (m_stages + segments - 1) / segments;
+  SegmentRule rule(CF_STAGE_BYTES, NE);
+  rule.target_blocks = 24576;
+  StagePlan p;
+  if ((rc = stage_plan(c, (M + per_stage - 1) / per_stage, 4, CFAST_DEFAULT_TT, rule, p))) return rc;
+  const int64_t n_pad = p.n_pad, m_stages = p.m_stages;
+  const int TT = p.TT;
+  const int64_t m_alloc = m_stages * per_stage;
 
   if ((rc = morton_order(c, m_alloc))) return rc;
   const PackKey key = {LAYOUT_CFAST, kernel, TT};
@@ -901,73 +915,53 @@ int run_product_cfast(kmvp_ctx* c, int kernel, int sig) {
   HIP_TRY(c, hipGetLastError());
   record_packed(c, key, sig);
 
-  if ((rc = ensure(c, c->part, (size_t)segments * NE * n_pad * sizeof(double)))) return rc;
+  if ((rc = ensure(c, c->part, (size_t)p.segments * NE * n_pad * sizeof(double)))) return rc;
   CfastArgs a;
+  plan_args(p, a);
   a.xraw = (const float*)c->xs.p;
   a.scale = scale;
   a.img = (const unsigned char*)c->rec.p;
   a.part = (double*)c->part.p;
-  a.n_pad = n_pad;
-  a.m_stages = m_stages;
-  a.seg_stages = seg_stages;
-  a.segments = segments;
-  a.tile_blocks = (int)tile_blocks;
   a.chunk_stages = std::max<int>(1, c->opt_chunk / (int)per_stage);
   a.j_offset = c->j_offset;
   a.m_total = c->m_total;
-  const dim3 grid((unsigned)(tile_blocks * segments));
+  const dim3 grid((unsigned)p.grid);
   HIP_TRY(c, mark(c, 0));
-  hipError_t le;
-  switch (kernel) {
-    case K_GAUSSIAN: le = launch_cfast_gaussian(sig, TT, a, grid, c->stream, &c->last_kernel_name); break;
-    case K_ABSEXP: le = launch_cfast_absexp(sig, TT, a, grid, c->stream, &c->last_kernel_name); break;
-    default: le = launch_cfast_invdist(sig, TT, a, grid, c->stream, &c->last_kernel_name); break;
-  }
+  const auto launch = kernel == K_GAUSSIAN ? launch_cfast_gaussian : (kernel == K_ABSEXP ? launch_cfast_absexp : launch_cfast_invdist);
+  const hipError_t le = launch(sig, TT, a, grid, c->stream, &c->last_kernel_name);
   if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "fast_tiles must be 1, 2 or 4");
   HIP_TRY(c, le);
   HIP_TRY(c, mark(c, 1));
 
   // ---- epilogue: segments -> sums, [all-reduce over the source shards], normalise
-  return reduce_and_finish(c, segments, NE, N, n_pad, E, sig);
+  return reduce_and_finish(c, p.segments, NE, N, n_pad, E, sig);
 }
 
-// ---- cell-reduced Gaussian path (kmvp_cell.hpp): float32, D <= 3, E == 1 -----------------------------
-
 // Several signal columns on cfast_kernel's distances (kmvp_cfastmm.hpp): exp(-r), and the Gaussian outside the radius
-// rule; float32, D <= 4, any E (blocks of up to 32 columns, the denominator of normalised rows being one more column).
+// rule; float32, D <= 4, any E (column blocks as for fastmm_kernel).
 int run_product_cfastmm(kmvp_ctx* c, int kernel, int sig) {
   const int D = c->D, E = c->E;
   const int NE = sig == SIG_NORM ? E + 1 : E;
   const int64_t N = c->N, M = c->M;
   const int MODE = NE > 16 ? 1 : 0;
-  const bool small = N < SMALL_PROBLEM_TARGETS;
-  const int TT = c->opt_fast_tiles > 0 ? std::min(c->opt_fast_tiles, 2) : (small ? 1 : 2);
   const int64_t SB = cfm_stage_bytes(MODE);
   const float scale = scale_for<float>(kernel);
   const float* x_raw = (const float*)(c->same_points ? c->y_raw.p : c->x_raw.p);
-  const int64_t tile = (int64_t)32 * TT * WAVES_PER_BLOCK;
-  const int64_t n_pad = round_up(N, tile);
-  const int64_t tile_blocks = n_pad / tile;
-  const int64_t m_stages = (M + CF_GROUP - 1) / CF_GROUP;  // one group per stage
-  const int64_t m_alloc = m_stages * CF_GROUP;
-  const int nb_max = std::min(NE, FMM_MAX_COLS);
   if (c->m_total > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "more than 2^31 sources");
   const int online = (kernel == K_INVDIST || !(c->same_points || c->opt_same_global)) ? 1 : 0;  // see run_product_fastmm; 1/r: always
   int rc;
 
-  int segments = choose_segments(c, tile_blocks, m_stages, nb_max, n_pad, SB, small ? 1 : 4, small, 2 << 20, 4096);
-  segments = settle_segments(m_stages, segments);
-  const int64_t seg_stages = (m_stages + segments - 1) / segments;
-  if (tile_blocks * segments > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
+  SegmentRule rule(SB, std::min(NE, FMM_MAX_COLS));  // as run_product_fastmm
+  rule.target_blocks = 4096;
+  StagePlan p;
+  if ((rc = stage_plan(c, (M + CF_GROUP - 1) / CF_GROUP, 2, 2, rule, p))) return rc;  // one group per stage
+  const int64_t n_pad = p.n_pad, m_stages = p.m_stages;
+  const int TT = p.TT;
 
-  if ((rc = morton_order(c, m_alloc))) return rc;
+  if ((rc = morton_order(c, m_stages * CF_GROUP))) return rc;
   const PackKey key = {LAYOUT_CFASTMM, kernel, TT + 16 * MODE};
-  const bool one_block = NE <= FMM_MAX_COLS;
-  const int image_sig = one_block ? sig : -1;  // as in run_product_fastmm
-  const bool sig_stale = signal_stale(c, key, image_sig);
-  if ((rc = ensure(c, c->cell_scale, 1024))) return rc;
-  float* sigma = (float*)((char*)c->cell_scale.p + 256);
-  double* unscale = (double*)((char*)c->cell_scale.p + 512);
+  ColumnBlocks cb;
+  if ((rc = column_blocks(c, key, sig, cb))) return rc;
   if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)n_pad * 4 * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->rec, (size_t)m_stages * SB))) return rc;
@@ -977,52 +971,35 @@ int run_product_cfastmm(kmvp_ctx* c, int kernel, int sig) {
                        (const float*)c->y_raw.p, (const int*)c->perm.p, (unsigned char*)c->rec.p, M, D, MODE, scale, c->j_offset);
     HIP_TRY(c, hipGetLastError());
   }
-  record_packed(c, key, image_sig);
 
-  if ((rc = ensure(c, c->part, (size_t)segments * nb_max * n_pad * sizeof(double)))) return rc;
-  if (!one_block && (rc = ensure(c, c->sums, (size_t)NE * n_pad * sizeof(double)))) return rc;
   CfastmmArgs a;
+  plan_args(p, a);
   a.xraw = (const float*)c->xs.p;
   a.img = (const unsigned char*)c->rec.p;
-  a.unscale = unscale;
-  a.part = (double*)c->part.p;
-  a.n_pad = n_pad;
-  a.m_stages = m_stages;
-  a.seg_stages = seg_stages;
-  a.segments = segments;
-  a.tile_blocks = (int)tile_blocks;
+  a.unscale = cb.unscale;
   a.chunk_stages = std::max(1, 2 * c->opt_chunk / CF_GROUP);
   a.scale = scale;
   a.m_total = c->m_total;
-  const dim3 grid((unsigned)(tile_blocks * segments));
+  const dim3 grid((unsigned)p.grid);
   const int64_t pieces = m_stages * (CF_GROUP / 32) * (MODE ? 2 : 1) * 2 * 64;
-  HIP_TRY(c, mark(c, 0));
-  for (int col0 = 0; col0 < NE; col0 += FMM_MAX_COLS) {
-    const int nb = std::min(FMM_MAX_COLS, NE - col0);
-    if (sig_stale) {
-      hipLaunchKernelGGL(fastmm_colscale_kernel, dim3(FMM_MAX_COLS), dim3(256), 0, c->stream, (const float*)c->b_raw.p,
-                         M, E, col0, nb, sigma, unscale);
-      hipLaunchKernelGGL(pack_cfastmm_signal_kernel, dim3(blocks_for(pieces)), dim3(256), 0, c->stream,
-                         (const float*)c->b_raw.p, (const float*)sigma, (const int*)c->perm.p, (unsigned char*)c->rec.p,
-                         M, m_stages, E, col0, nb, MODE);
-      HIP_TRY(c, hipGetLastError());
-    }
-    a.NE = nb;
-    hipError_t le = launch_cfastmm(kernel, MODE, TT, online, a, grid, c->stream, &c->last_kernel_name);
-    if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "no cfastmm_kernel for this kernel / tile count");
-    HIP_TRY(c, le);
-    if (!one_block) {
-      const int Ek = std::max(0, std::min(nb, E - col0));
-      hipLaunchKernelGGL(reduce_block_kernel, dim3(blocks_for((int64_t)nb * n_pad)), dim3(256), 0, c->stream,
-                         (const double*)c->part.p, (double*)c->sums.p, n_pad, nb, Ek, segments, col0, E);
-      HIP_TRY(c, hipGetLastError());
-    }
-  }
-  HIP_TRY(c, mark(c, 1));
-  if (online) c->note = "cfastmm_kernel with the per-target online shift (targets != sources)";
-  if (one_block) return reduce_and_finish(c, segments, NE, N, n_pad, E, sig);
-  return finish_product(c, (int64_t)NE * n_pad, N, n_pad, E, sig);
+  return run_column_blocks(
+      c, key, sig, p, cb, false, online ? "cfastmm_kernel with the per-target online shift (targets != sources)" : nullptr,
+      [&](int col0, int nb) {
+        hipLaunchKernelGGL(pack_cfastmm_signal_kernel, dim3(blocks_for(pieces)), dim3(256), 0, c->stream,
+                           (const float*)c->b_raw.p, (const float*)cb.sigma, (const int*)c->perm.p, (unsigned char*)c->rec.p,
+                           M, m_stages, E, col0, nb, MODE);
+      },
+      [&](int nb) {
+        a.NE = nb;
+        a.part = (double*)c->part.p;
+        hipError_t le = launch_cfastmm(kernel, MODE, TT, online, a, grid, c->stream, &c->last_kernel_name);
+        if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "no cfastmm_kernel for this kernel / tile count");
+        HIP_TRY(c, le);
+        return (int)KMVP_OK;
+      });
 }
+
+// ---- the cell paths: cell order and tile lists ---------------------------------------------------------------------------
 
 // Cell order of one cloud: keys -> radix sort; the sorted keys come back to the host, where the
 // tile lists are built (one pass over n keys, once per kmvp_set_points).
@@ -1030,140 +1007,36 @@ int cell_sort(kmvp_ctx* c, const void* pts, int64_t n, const CellGrid& grid, kmv
               std::vector<unsigned>& keys, kmvp_ctx::DevBuf* keys_dev = nullptr) {
   int rc;
   const int D = c->D;
-  size_t tmp_bytes = 0;
-  HIP_TRY(c, sort_pairs_u32(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, n, c->stream));
   const size_t keys_bytes = (size_t)n * sizeof(unsigned);
-  if ((rc = ensure(c, c->sortbuf, 3 * keys_bytes + tmp_bytes + 256))) return rc;
+  SortBufs b;
+  if ((rc = sort_buffers(c, n, b))) return rc;
   if ((rc = ensure(c, perm, (size_t)n * sizeof(int)))) return rc;
-  unsigned* keys_in = (unsigned*)c->sortbuf.p;
-  unsigned* keys_out = keys_in + n;
-  int* vals_in = (int*)(keys_out + n);
-  void* tmp = (void*)((((uintptr_t)(vals_in + n)) + 255) & ~(uintptr_t)255);
   if (c->dtype == KMVP_F64)
     hipLaunchKernelGGL(cell64_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, (const double*)pts, n, D, grid,
-                       keys_in, vals_in);
+                       b.keys_in, b.vals_in);
   else
     hipLaunchKernelGGL(cell_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, (const float*)pts, n, D, grid,
-                       keys_in, vals_in);
+                       b.keys_in, b.vals_in);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, sort_pairs_u32(tmp, &tmp_bytes, keys_in, keys_out, vals_in, (int*)perm.p, n, c->stream));
+  HIP_TRY(c, sort_pairs_u32(b.tmp, &b.tmp_bytes, b.keys_in, b.keys_out, b.vals_in, (int*)perm.p, n, c->stream));
   keys.resize((size_t)n);
-  HIP_TRY(c, hipMemcpyAsync(keys.data(), keys_out, keys_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(keys.data(), b.keys_out, keys_bytes, hipMemcpyDeviceToHost, c->stream));
   if (keys_dev) {  // the float64 path keeps the sorted keys on the device too (source records are packed from them)
     if ((rc = ensure(c, *keys_dev, keys_bytes))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(keys_dev->p, keys_out, keys_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(keys_dev->p, b.keys_out, keys_bytes, hipMemcpyDeviceToDevice, c->stream));
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return KMVP_OK;
 }
 
-// Tiles of <= 32 points that never straddle a cell; every cell gets a multiple of `mult` tiles (the
-// extra ones are empty), so that the `mult` target tiles of a wavefront always share their cell.
-// Device layout of the list: [start][count][key], n_tiles entries each.
-int cell_tiles(kmvp_ctx* c, const std::vector<unsigned>& keys, int mult, kmvp_ctx::DevBuf& grp, int64_t* n_tiles,
-               int tile = CELL_TILE) {
-  const int64_t n = (int64_t)keys.size();
-  std::vector<int> start, count;
-  std::vector<unsigned> gkey;
-  start.reserve((size_t)n / 24 + 16);
-  count.reserve((size_t)n / 24 + 16);
-  gkey.reserve((size_t)n / 24 + 16);
-  for (int64_t p = 0; p < n;) {
-    int64_t e = p + 1;
-    while (e < n && keys[(size_t)e] == keys[(size_t)p]) ++e;
-    int tiles = 0;
-    for (int64_t t = p; t < e; t += tile, ++tiles) {
-      start.push_back((int)t);
-      count.push_back((int)std::min<int64_t>(tile, e - t));
-      gkey.push_back(keys[(size_t)p]);
-    }
-    for (; tiles % mult; ++tiles) {
-      start.push_back((int)p);
-      count.push_back(0);
-      gkey.push_back(keys[(size_t)p]);
-    }
-    p = e;
-  }
-  const size_t G = start.size();
-  int rc;
-  if ((rc = ensure(c, grp, 3 * G * sizeof(int)))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(grp.p, start.data(), G * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync((int*)grp.p + G, count.data(), G * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync((int*)grp.p + 2 * G, gkey.data(), G * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
-  *n_tiles = (int64_t)G;
-  return KMVP_OK;
-}
-
-// Target tiles of the float32 cell kernels, in TWO lists that share one array.  A wavefront owns TT tiles of ONE cell,
-// so a cell of `tiles` tiles used to be padded to a multiple of TT with empty tiles -- at the headline shape (cells of
-// 1000 +- 32 points: 32 tiles, or 33-34 for a fifth of them) 5.6 % of all tile pairs were such padding, and the kernel
-// is bound by the matrix pipe.  Now a cell's tiles are split: whole groups of TT go to the MAIN list; a remainder of at
-// most TT/2 tiles goes to the REST list in groups of two (a larger remainder is still padded to a whole group: the
-// second launch with two tiles per wavefront is ~1.6x less efficient per tile).  Both lists are padded to whole
-// workgroups (4 wavefronts) with empty tiles that repeat the preceding key.  Layout as cell_tiles().
-int cell_tiles_split(kmvp_ctx* c, const std::vector<unsigned>& keys, int TT, kmvp_ctx::DevBuf& grp, int64_t* n_main,
-                     int64_t* n_rest) {
-  const int64_t n = (int64_t)keys.size();
-  const int RT = 2;  // tiles per wavefront of the second launch
-  std::vector<int> start, count, rstart, rcount;
-  std::vector<unsigned> gkey, rkey;
-  start.reserve((size_t)n / 24 + 64);
-  count.reserve((size_t)n / 24 + 64);
-  gkey.reserve((size_t)n / 24 + 64);
-  for (int64_t p = 0; p < n;) {
-    int64_t e = p + 1;
-    while (e < n && keys[(size_t)e] == keys[(size_t)p]) ++e;
-    const int64_t tiles = (e - p + CELL_TILE - 1) / CELL_TILE;
-    const int64_t rem = tiles % TT;
-    const bool split = TT > RT && rem > 0 && rem <= TT / 2;
-    const int64_t main_tiles = split ? tiles - rem : tiles;
-    int64_t t = p, k = 0;
-    for (; k < main_tiles; ++k, t += CELL_TILE) {
-      start.push_back((int)t);
-      count.push_back((int)std::min<int64_t>(CELL_TILE, e - t));
-      gkey.push_back(keys[(size_t)p]);
-    }
-    for (; !split && k % TT; ++k) {  // an unsplit remainder: empty tiles up to a whole group
-      start.push_back((int)p);
-      count.push_back(0);
-      gkey.push_back(keys[(size_t)p]);
-    }
-    if (split) {
-      int64_t r = 0;
-      for (; r < rem; ++r, t += CELL_TILE) {
-        rstart.push_back((int)t);
-        rcount.push_back((int)std::min<int64_t>(CELL_TILE, e - t));
-        rkey.push_back(keys[(size_t)p]);
-      }
-      for (; r % RT; ++r) {
-        rstart.push_back((int)p);
-        rcount.push_back(0);
-        rkey.push_back(keys[(size_t)p]);
-      }
-    }
-    p = e;
-  }
-  auto pad_to = [](std::vector<int>& st, std::vector<int>& ct, std::vector<unsigned>& ky, size_t mult) {
-    while (!st.empty() && st.size() % mult) {
-      st.push_back(st.back());
-      ct.push_back(0);
-      ky.push_back(ky.back());
-    }
-  };
-  pad_to(start, count, gkey, (size_t)TT * WAVES_PER_BLOCK);
-  pad_to(rstart, rcount, rkey, (size_t)RT * WAVES_PER_BLOCK);
-  *n_main = (int64_t)start.size();
-  *n_rest = (int64_t)rstart.size();
-  start.insert(start.end(), rstart.begin(), rstart.end());
-  count.insert(count.end(), rcount.begin(), rcount.end());
-  gkey.insert(gkey.end(), rkey.begin(), rkey.end());
-  const size_t G = start.size();
+// A tile list (kmvp_plan.hpp) in its device layout: [start][count][key], l.size() entries each
+int upload_tiles(kmvp_ctx* c, const TileList& l, kmvp_ctx::DevBuf& grp) {
+  const size_t G = l.size();
   int rc;
   if ((rc = ensure(c, grp, 3 * std::max<size_t>(G, 1) * sizeof(int)))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(grp.p, start.data(), G * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync((int*)grp.p + G, count.data(), G * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync((int*)grp.p + 2 * G, gkey.data(), G * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(grp.p, l.start.data(), G * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync((int*)grp.p + G, l.count.data(), G * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync((int*)grp.p + 2 * G, l.key.data(), G * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
   return KMVP_OK;
 }
@@ -1206,26 +1079,6 @@ void cell_load_grid(const kmvp_ctx* c, CellGrid& grid) {
   }
 }
 
-// Tiles of the two target lists cell_tiles_split() builds for groups of TT (before the padding to whole workgroups)
-void cell_split_count(const std::vector<unsigned>& keys, int TT, int64_t* n_main, int64_t* n_rest) {
-  const int64_t n = (int64_t)keys.size();
-  const int RT = 2;
-  *n_main = *n_rest = 0;
-  for (int64_t p = 0; p < n;) {
-    int64_t e = p + 1;
-    while (e < n && keys[(size_t)e] == keys[(size_t)p]) ++e;
-    const int64_t tiles = (e - p + CELL_TILE - 1) / CELL_TILE;
-    const int64_t rem = tiles % TT;
-    if (TT > RT && rem > 0 && rem <= TT / 2) {
-      *n_main += tiles - rem;
-      *n_rest += round_up(rem, RT);
-    } else {
-      *n_main += round_up(tiles, TT);
-    }
-    p = e;
-  }
-}
-
 // picoseconds per 32 x 32 tile of pairs of the float32 cell kernels, whole chip, by the tiles a wavefront owns
 // (cellmm_kernel at the headline shape: TT = 8 / 4 / 2: 26.9 / 30.7 / 44.2 ms for 1.03e9 tiles)
 inline double cell_ps_per_tile(int TT) { return TT >= 8 ? CMM_PS_PER_TILE_MAIN : (TT >= 4 ? CMM_PS_PER_TILE_TT4 : CMM_PS_PER_TILE_REST); }
@@ -1250,7 +1103,9 @@ int cell_prepare(kmvp_ctx* c, int TT) {
   int rc;
   std::vector<unsigned> keys;
   if ((rc = cell_sort(c, c->y_raw.p, c->M, grid, c->cell_sperm, keys))) return rc;
-  if ((rc = cell_tiles(c, keys, 1, c->cell_sgrp, &c->cell_m_tiles))) return rc;
+  const TileList sources = cell_tiles(keys.data(), c->M);
+  if ((rc = upload_tiles(c, sources, c->cell_sgrp))) return rc;
+  c->cell_m_tiles = (int64_t)sources.size();
   if (!c->same_points && (rc = cell_sort(c, c->x_raw.p, c->N, grid, c->cell_tperm, keys))) return rc;
   if (TT == 0) {
     // auto: the group size whose two lists cost least (sparse cells of 3 - 5 tiles: groups of four and a leftover list
@@ -1258,7 +1113,7 @@ int cell_prepare(kmvp_ctx* c, int TT) {
     double best = INFINITY;
     for (int t : {8, 4, 2}) {
       int64_t nm, nr;
-      cell_split_count(keys, t, &nm, &nr);
+      cell_split_count(keys.data(), (int64_t)keys.size(), t, &nm, &nr);
       const double cost = cell_ps_per_tile(t) * (double)nm + cell_ps_per_tile(2) * (double)nr;
       if (cost < best) {
         best = cost;
@@ -1266,7 +1121,8 @@ int cell_prepare(kmvp_ctx* c, int TT) {
       }
     }
   }
-  if ((rc = cell_tiles_split(c, keys, TT, c->cell_tgrp, &c->cell_n_main, &c->cell_n_rest))) return rc;
+  if ((rc = upload_tiles(c, cell_tiles_split(keys.data(), (int64_t)keys.size(), TT, &c->cell_n_main, &c->cell_n_rest), c->cell_tgrp)))
+    return rc;
   c->cell_n_tiles = c->cell_n_main + c->cell_n_rest;  // (both lists already padded to whole workgroups)
   c->cell_tt = TT;
   cell_store_grid(c, grid);
@@ -1282,79 +1138,61 @@ double cell_padding(const kmvp_ctx* c) {  // (empty tiles included)
   return std::max(t, s);
 }
 
-// The two launches of the float32 cell kernels over the target lists of cell_tiles_split(): r = 0 the MAIN list (groups
-// of cell_tt tiles per wavefront), r = 1 the REST list (the cells' leftover tiles, two per wavefront -- few workgroups,
-// latency-bound each, so its own, finer split of the sources).  Each launch has its own segments and its own region
-// [segment][cols][slots] of the partial sums in c->part.
-struct CellSplit {
-  int64_t m_stages, n_slots;  // source stages; target slots of both lists
-  int64_t blocks[2], slots[2], seg_stages[2];
-  int segments[2];
-  int tt(const kmvp_ctx* c, int r) const { return r ? 2 : c->cell_tt; }
-  dim3 grid(int r) const { return dim3((unsigned)(blocks[r] * segments[r])); }
-  size_t part_doubles(int cols) const { return ((size_t)segments[0] * slots[0] + (size_t)segments[1] * slots[1]) * cols; }
-  double* region(const kmvp_ctx* c, int cols, int r) const { return (double*)c->part.p + (r ? (size_t)segments[0] * cols * slots[0] : 0); }
-  template <class Args>
-  void args(const kmvp_ctx* c, int cols, int r, Args& a) const {
-    a.part = region(c, cols, r);
-    a.n_slots = slots[r];
-    a.tile_base = r ? c->cell_n_main : 0;
-    a.seg_stages = seg_stages[r];
-    a.segments = segments[r];
-    a.tile_blocks = (int)blocks[r];
-  }
-};
-
+// The context's side of a CellSplit (kmvp_plan.hpp): the plan of the two launches of the float32 cell kernels for the
+// current lists, a launch's region of c->part and its share of the kernel's arguments.
 // Per path: the stage of its source image, and for the main launch the shortest segment on big problems, the L2 budget
-// of a segment and the target number of workgroups (choose_segments)
-CellSplit cell_split(const kmvp_ctx* c, int cols, int stage_tiles, int64_t stage_bytes, int min_seg, int64_t l2_seg_bytes,
-                     int64_t target_blocks) {
-  const bool small = c->N < SMALL_PROBLEM_TARGETS;
-  CellSplit s;
-  s.m_stages = (c->cell_m_tiles + stage_tiles - 1) / stage_tiles;
-  s.n_slots = c->cell_n_tiles * CELL_TILE;
-  s.blocks[0] = c->cell_n_main / (c->cell_tt * WAVES_PER_BLOCK);
-  s.blocks[1] = c->cell_n_rest / (2 * WAVES_PER_BLOCK);
-  s.slots[0] = c->cell_n_main * CELL_TILE;
-  s.slots[1] = c->cell_n_rest * CELL_TILE;
-  s.segments[0] = settle_segments(s.m_stages, choose_segments(c, std::max<int64_t>(1, s.blocks[0]), s.m_stages, cols, s.n_slots,
-                                                              stage_bytes, small ? 1 : min_seg, small, l2_seg_bytes, target_blocks));
-  s.seg_stages[0] = (s.m_stages + s.segments[0] - 1) / s.segments[0];
-  s.segments[1] = 0;
-  s.seg_stages[1] = 1;
-  if (s.blocks[1] > 0) {
-    const int seg = choose_segments(c, s.blocks[1], s.m_stages, cols, s.n_slots, stage_bytes, 1, small, l2_seg_bytes, 1536);
-    s.seg_stages[1] = (s.m_stages + seg - 1) / seg;
-    s.segments[1] = (int)((s.m_stages + s.seg_stages[1] - 1) / s.seg_stages[1]);
-  }
-  return s;
+// of a segment and the target number of workgroups.
+CellSplit cell_plan(const kmvp_ctx* c, int stage_tiles, SegmentRule main) {
+  return cell_split(c->N, c->cell_m_tiles, c->cell_n_main, c->cell_n_rest, c->cell_tt, c->opt_segments, stage_tiles, main);
 }
+double* cell_region(const kmvp_ctx* c, const CellSplit& s, int cols, int r) { return (double*)c->part.p + s.region_offset(cols, r); }
+template <class Args>
+void cell_args(const kmvp_ctx* c, const CellSplit& s, int cols, int r, Args& a) {
+  a.part = cell_region(c, s, cols, r);
+  a.n_slots = s.slots[r];
+  a.tile_base = r ? c->cell_n_main : 0;
+  a.seg_stages = s.seg_stages[r];
+  a.segments = s.segments[r];
+  a.tile_blocks = (int)s.blocks[r];
+}
+inline int cell_tt(const kmvp_ctx* c, int r) { return r ? CELL_REST_TT : c->cell_tt; }
+
+// The targets of the float32 cell kernels (cell_kernel, cellmm_kernel): coordinates in tile order (xs), tile centres
+// (cell_tmeta), the slot of every target (cell_slot)
+int pack_cell_targets(kmvp_ctx* c, const CellGrid& grid) {
+  const int64_t n_tiles = c->cell_n_tiles;
+  const float* x_raw = (const float*)(c->same_points ? c->y_raw.p : c->x_raw.p);
+  const int* tperm = (const int*)(c->same_points ? c->cell_sperm.p : c->cell_tperm.p);
+  const int* tgrp = (const int*)c->cell_tgrp.p;
+  int rc;
+  if ((rc = ensure(c, c->xs, (size_t)n_tiles * CELL_TILE * 4 * sizeof(float)))) return rc;
+  if ((rc = ensure(c, c->cell_tmeta, (size_t)n_tiles * 4 * sizeof(float)))) return rc;
+  if ((rc = ensure(c, c->cell_slot, (size_t)c->N * sizeof(int)))) return rc;
+  hipLaunchKernelGGL(pack_cell_targets_kernel, dim3((unsigned)n_tiles), dim3(CELL_TILE), 0, c->stream, x_raw, tperm,
+                     tgrp, tgrp + n_tiles, (const unsigned*)(tgrp + 2 * n_tiles), n_tiles, c->D,
+                     grid, (float*)c->xs.p, (float*)c->cell_tmeta.p, (int*)c->cell_slot.p);
+  return KMVP_OK;
+}
+
+// ---- cell-reduced Gaussian path (kmvp_cell.hpp): float32, D <= 3, E == 1 -----------------------------
 
 int run_product_cell(kmvp_ctx* c, int sig) {
   const int D = c->D;
   const int E = 1;
   const int NE = sig == SIG_NORM ? 2 : 1;
   const int64_t N = c->N;
-  const int64_t n_tiles = c->cell_n_tiles;  // whole groups of cell_tt, then leftover tiles in groups of 2 (cell_tiles_split)
-  const CellSplit s = cell_split(c, NE, CELL_STAGE_TILES, CELL_STAGE_BYTES, 4, 2 << 20, 16384);
+  // target tiles: whole groups of cell_tt, then leftover tiles in groups of 2 (cell_tiles_split)
+  SegmentRule rule(CELL_STAGE_BYTES, NE);
+  rule.min_seg = 4;
+  const CellSplit s = cell_plan(c, CELL_STAGE_TILES, rule);
   const int64_t m_stages = s.m_stages, n_slots = s.n_slots;
   int rc;
   CellGrid grid;
   cell_load_grid(c, grid);
 
   const PackKey key = {LAYOUT_CELL, K_GAUSSIAN, c->cell_tt};
-  const float* x_raw = (const float*)(c->same_points ? c->y_raw.p : c->x_raw.p);
-  const int* tperm = (const int*)(c->same_points ? c->cell_sperm.p : c->cell_tperm.p);
-  const int* tgrp = (const int*)c->cell_tgrp.p;
   const int* sgrp = (const int*)c->cell_sgrp.p;
-  if (points_stale(c, key)) {
-    if ((rc = ensure(c, c->xs, (size_t)n_slots * 4 * sizeof(float)))) return rc;
-    if ((rc = ensure(c, c->cell_tmeta, (size_t)n_tiles * 4 * sizeof(float)))) return rc;
-    if ((rc = ensure(c, c->cell_slot, (size_t)N * sizeof(int)))) return rc;
-    hipLaunchKernelGGL(pack_cell_targets_kernel, dim3((unsigned)n_tiles), dim3(CELL_TILE), 0, c->stream, x_raw, tperm,
-                       tgrp, tgrp + c->cell_n_tiles, (const unsigned*)(tgrp + 2 * c->cell_n_tiles), c->cell_n_tiles, D,
-                       grid, (float*)c->xs.p, (float*)c->cell_tmeta.p, (int*)c->cell_slot.p);
-  }
+  if (points_stale(c, key) && (rc = pack_cell_targets(c, grid))) return rc;
   if (signal_stale(c, key, sig)) {
     if ((rc = ensure(c, c->rec, (size_t)m_stages * CELL_STAGE_BYTES))) return rc;
     hipLaunchKernelGGL(pack_cell_sources_kernel, dim3((unsigned)(m_stages * CELL_STAGE_TILES)), dim3(CELL_TILE), 0,
@@ -1378,8 +1216,8 @@ int run_product_cell(kmvp_ctx* c, int sig) {
   hipError_t le = hipSuccess;
   for (int r = 0; r < 2 && le == hipSuccess; ++r)
     if (s.blocks[r] > 0) {
-      s.args(c, NE, r, a);
-      le = launch_cell_gaussian(sig, s.tt(c, r), a, s.grid(r), c->stream, &c->last_kernel_name);
+      cell_args(c, s, NE, r, a);
+      le = launch_cell_gaussian(sig, cell_tt(c, r), a, dim3((unsigned)s.grid(r)), c->stream, &c->last_kernel_name);
     }
   if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "fast_tiles must be 1, 2, 4 or 8");
   HIP_TRY(c, le);
@@ -1391,7 +1229,7 @@ int run_product_cell(kmvp_ctx* c, int sig) {
   for (int r = 0; r < 2; ++r)
     if (s.blocks[r] > 0)
       hipLaunchKernelGGL(reduce_region_kernel, dim3(blocks_for((int64_t)NE * s.slots[r])), dim3(256), 0, c->stream,
-                         (const double*)s.region(c, NE, r), (double*)c->cell_sums.p, s.slots[r], NE, s.segments[r], n_slots,
+                         (const double*)cell_region(c, s, NE, r), (double*)c->cell_sums.p, s.slots[r], NE, s.segments[r], n_slots,
                          r ? s.slots[0] : (int64_t)0);
   hipLaunchKernelGGL(gather_cells_kernel, dim3(blocks_for((int64_t)NE * N)), dim3(256), 0, c->stream,
                      (const double*)c->cell_sums.p, (const int*)c->cell_slot.p, (double*)c->sums.p, N, n_slots, NE);
@@ -1418,12 +1256,15 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
   const int NE = sig == SIG_NORM ? E + 1 : E;
   const int64_t N = c->N;
   const int TT = c->cell_tt;  // the target tile lists were built for it (cell_prepare)
-  const int64_t n_tiles = c->cell_n_tiles;  // whole groups of TT, then leftover tiles in groups of 2 (cell_tiles_split)
   // segments of <= 3 MiB of source image (one per XCD at a time in its 4 MiB L2) and ~14 rounds of resident
   // workgroups: 8 at the headline shape.  tools/cellmm_segments.py: 8 ... 32 segments run alike (28.3-28.5 ms),
   // 4 is slower (29.0); every segment costs n_slots x 8 bytes of partial sums written and read back and one more
   // pass over the targets, so the fewest that keep the chip full are taken (HBM-side traffic 0.44 -> 0.25 GB).
-  const CellSplit s = cell_split(c, 1, CMM_STAGE_TILES, CMM_STAGE_BYTES, 2, 3 << 20, 7168);
+  SegmentRule rule(CMM_STAGE_BYTES, 1);
+  rule.min_seg = 2;
+  rule.l2_seg_bytes = 3 << 20;
+  rule.target_blocks = 7168;
+  const CellSplit s = cell_plan(c, CMM_STAGE_TILES, rule);
   const int64_t m_stages = s.m_stages, n_slots = s.n_slots;
   int rc;
   CellGrid grid;
@@ -1433,22 +1274,14 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
   // the image holds ONE column's signal: it can be reused only by single-column products
   const int image_sig = NE > 1 ? -1 : sig;
   const bool sig_stale = signal_stale(c, key, image_sig);
-  const float* x_raw = (const float*)(c->same_points ? c->y_raw.p : c->x_raw.p);
-  const int* tperm = (const int*)(c->same_points ? c->cell_sperm.p : c->cell_tperm.p);
-  const int* tgrp = (const int*)c->cell_tgrp.p;
   const int* sgrp = (const int*)c->cell_sgrp.p;
   if ((rc = ensure(c, c->cell_scale, 64))) return rc;
   float* scale = (float*)c->cell_scale.p;
   unsigned* bmax = (unsigned*)c->cell_scale.p + 4;
   HIP_TRY(c, mark(c, 0));
   if (points_stale(c, key)) {
-    if ((rc = ensure(c, c->xs, (size_t)n_slots * 4 * sizeof(float)))) return rc;
-    if ((rc = ensure(c, c->cell_tmeta, (size_t)n_tiles * 4 * sizeof(float)))) return rc;
-    if ((rc = ensure(c, c->cell_slot, (size_t)N * sizeof(int)))) return rc;
+    if ((rc = pack_cell_targets(c, grid))) return rc;
     if ((rc = ensure(c, c->rec, (size_t)m_stages * CMM_STAGE_BYTES))) return rc;
-    hipLaunchKernelGGL(pack_cell_targets_kernel, dim3((unsigned)n_tiles), dim3(CELL_TILE), 0, c->stream, x_raw, tperm,
-                       tgrp, tgrp + c->cell_n_tiles, (const unsigned*)(tgrp + 2 * c->cell_n_tiles), c->cell_n_tiles, D,
-                       grid, (float*)c->xs.p, (float*)c->cell_tmeta.p, (int*)c->cell_slot.p);
     hipLaunchKernelGGL(pack_cellmm_points_kernel, dim3((unsigned)(m_stages * CMM_STAGE_TILES)), dim3(CELL_TILE), 0,
                        c->stream, (const float*)c->y_raw.p, (const int*)c->cell_sperm.p, sgrp, sgrp + c->cell_m_tiles,
                        (const unsigned*)(sgrp + 2 * c->cell_m_tiles), c->cell_m_tiles, D, grid, (unsigned char*)c->rec.p);
@@ -1489,8 +1322,8 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
     hipError_t le = hipSuccess;
     for (int r = 0; r < 2 && le == hipSuccess; ++r)
       if (s.blocks[r] > 0) {
-        s.args(c, 1, r, a);
-        le = launch_cellmm_gaussian(s.tt(c, r), shape, a, s.grid(r), c->stream, &c->last_kernel_name);
+        cell_args(c, s, 1, r, a);
+        le = launch_cellmm_gaussian(cell_tt(c, r), shape, a, dim3((unsigned)s.grid(r)), c->stream, &c->last_kernel_name);
       }
     if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "fast_tiles must be 1, 2, 4 or 8");
     HIP_TRY(c, le);
@@ -1500,7 +1333,7 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
     for (int r = 0; r < 2; ++r)
       if (s.blocks[r] > 0)
         hipLaunchKernelGGL(reduce_segments_kernel, dim3(blocks_for(s.slots[r])), dim3(256), 0, c->stream,
-                           (const double*)s.region(c, 1, r), col_sums + (r ? s.slots[0] : 0), s.slots[r], s.segments[r], 0);
+                           (const double*)cell_region(c, s, 1, r), col_sums + (r ? s.slots[0] : 0), s.slots[r], s.segments[r], 0);
     HIP_TRY(c, hipGetLastError());
   }
   if (NE > 1) HIP_TRY(c, mark(c, 1));  // several columns: the "kernel" time covers every column's pack + pair loop
@@ -1532,15 +1365,12 @@ int cell64_prepare(kmvp_ctx* c) {
   // source cells: [first record, count] and centres
   std::vector<int> runs;
   std::vector<double> centres;
-  for (int64_t p = 0; p < c->M;) {
-    int64_t e = p + 1;
-    while (e < c->M && keys[(size_t)e] == keys[(size_t)p]) ++e;
-    runs.push_back((int)p);
-    runs.push_back((int)(e - p));
-    for (int a = 0; a < 3; ++a) centres.push_back(a < D ? cell64_centre(keys[(size_t)p], a, grid) : 0.0);
+  for_each_key_run(keys.data(), c->M, [&](int64_t first, int64_t count, unsigned key) {
+    runs.push_back((int)first);
+    runs.push_back((int)count);
+    for (int a = 0; a < 3; ++a) centres.push_back(a < D ? cell64_centre(key, a, grid) : 0.0);
     centres.push_back(0.0);
-    p = e;
-  }
+  });
   c->cell_m_tiles = (int64_t)runs.size() / 2;  // number of source cells
   if ((rc = ensure(c, c->cell_sgrp, runs.size() * sizeof(int)))) return rc;
   if ((rc = ensure(c, c->cell_scentre, centres.size() * sizeof(double)))) return rc;
@@ -1548,7 +1378,9 @@ int cell64_prepare(kmvp_ctx* c) {
   HIP_TRY(c, hipMemcpyAsync(c->cell_scentre.p, centres.data(), centres.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (!c->same_points && (rc = cell_sort(c, c->x_raw.p, c->N, grid, c->cell_tperm, keys))) return rc;
-  if ((rc = cell_tiles(c, keys, 1, c->cell_tgrp, &c->cell_n_tiles, CELL64_TILE))) return rc;
+  const TileList targets = cell_tiles(keys.data(), (int64_t)keys.size(), CELL64_TILE);
+  if ((rc = upload_tiles(c, targets, c->cell_tgrp))) return rc;
+  c->cell_n_tiles = (int64_t)targets.size();
   c->cell_tt = 1;
   cell_store_grid(c, grid);
   c->cell_state = 1;
