@@ -123,6 +123,29 @@ int kmvp_invdist_norm(kmvp_ctx* ctx);
 int kmvp_expdot(kmvp_ctx* ctx);
 int kmvp_expdot_norm(kmvp_ctx* ctx);
 
+/* Gradient of the product with respect to the target points (an extension: no reference method stands behind it --
+ * the force field of an N-body sum, the gradient of a kernel density estimate, the derivative of a Kriging / GP mean).
+ * For targets x (N,D), sources y (M,D) and signal b (M,E):
+ *     G[i, e, :] = sum_j w(s_ij) (x_i - y_j) b[j, e],     s = |x_i - y_j|^2, r = sqrt(s), k the kernel value
+ *   kmvp_gaussian_grad  w = -2 k
+ *   kmvp_absexp_grad    w = -k / r.  A pair with s == 0 contributes exactly 0: exp(-r) is not differentiable there, 0 is
+ *                       the symmetric subgradient, and the own pair of same_points vanishes as it must.  (float32: s below
+ *                       the smallest normal number, r < 1.1e-19, counts as 0.)
+ *   kmvp_invdist_grad   w = -1 / r^3.  The pairs zeroed by the flat-index rule (bruteforce.py:13-14; j_offset / M_total as
+ *                       in the product) contribute 0.  A coincident pair that is NOT zeroed gives inf * 0: that row of G is
+ *                       NaN in every component -- exactly the rows where kmvp_invdist is inf.
+ * The targets are independent variables, also with same_points: this is the derivative in the first argument (a
+ * caller who wants the total derivative of a symmetric sum adds the transpose term).  Density estimation (b == NULL)
+ * means b = 1, E = 1.  Row normalisation is not differentiated.
+ * Synchronous like the products; the result is read with kmvp_get_result as (N, E D) float64 row-major, d fastest.
+ * float32 and float64 contexts, D <= 8, E <= 4 (lowd_grad_kernel, difference form: as accurate far from the origin as
+ * near it); KMVP_E_UNSUPPORTED beyond that and for bfloat16 contexts.  Honours "segments", "chunk" and "partial_shard";
+ * with a communicator attached the (N, E D) sums of all ranks are all-reduced like a product's.  Results are bitwise
+ * reproducible run to run (fixed summation order, no atomics). */
+int kmvp_gaussian_grad(kmvp_ctx* ctx);
+int kmvp_absexp_grad(kmvp_ctx* ctx);
+int kmvp_invdist_grad(kmvp_ctx* ctx);
+
 /* BaseProduct.get_result (base.py:107-116): (N,E) float64 row-major. */
 int kmvp_get_result(kmvp_ctx* ctx, double* out, int64_t out_len);
 

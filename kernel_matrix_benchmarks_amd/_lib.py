@@ -37,6 +37,9 @@ SYMBOLS = [
     ("kmvp_invdist_norm", _c.c_int, [_c.c_void_p]),
     ("kmvp_expdot", _c.c_int, [_c.c_void_p]),
     ("kmvp_expdot_norm", _c.c_int, [_c.c_void_p]),
+    ("kmvp_gaussian_grad", _c.c_int, [_c.c_void_p]),
+    ("kmvp_absexp_grad", _c.c_int, [_c.c_void_p]),
+    ("kmvp_invdist_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_get_result", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("kmvp_gaussian_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
@@ -175,6 +178,17 @@ class Context:
             ("exp-dot", False): self._lib.kmvp_expdot,
             ("exp-dot", True): self._lib.kmvp_expdot_norm,
         }[(kernel, bool(normalize_rows))]
+        self._check(entry(self._ctx))
+
+    def run_grad(self, kernel):
+        """Gradient with respect to the targets (include/kmvp.h kmvp_<kernel>_grad); read it with get_result(N, E * D)."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_grad,
+            "absolute-exponential": self._lib.kmvp_absexp_grad,
+            "inverse-distance": self._lib.kmvp_invdist_grad,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no gradient for kernel {kernel}")
         self._check(entry(self._ctx))
 
     def get_result(self, N, E):

@@ -45,6 +45,7 @@ SUPPORTED_KERNELS = ("gaussian", "absolute-exponential", "inverse-distance", "ex
 #    |y_j|^2/2 spans less than the exponent range of the working precision: checked in prepare_data
 #    (EXPDOT_IDENTITY_SPREAD), NotImplementedError beyond it -- never a silent zero weight.
 SQRT_HALF = 0.7071067811865476
+GRADIENT_MAX_D, GRADIENT_MAX_E = 8, 4  # lowd_grad_kernel's instantiations (csrc/kmvp_internal.hpp LOWD_MAX_D, LOWD_MAX_E)
 EXPDOT_NATIVE_MAX_D = 64
 EXPDOT_NATIVE_MAX_D_BF16 = 141  # 16 * 9 k-steps - 3 operand columns (kmvp_mfma.hpp MFMA_DOT_AUG)
 # largest spread max_j |y_j|^2/2 - min_j |y_j|^2/2 the identity route accepts: the smallest weight is exp(-spread);
@@ -251,6 +252,33 @@ class MI355XProduct(BaseProduct):
         # synchronous: the device (and the all-reduce) is done when this returns
         self._ctx.run(self._device_kernel_fn, self.normalize_rows and (self._dot_native or not self._dot))
         self.res = None  # the result stays on the device until get_result()
+
+    def query_gradient(self):
+        """G[i, e, :] = grad_{x_i} sum_j k(x_i, y_j) b[j, e] (include/kmvp.h kmvp_<kernel>_grad): the timed part, like
+        query().  The targets are independent variables, also with same_points.  Synchronous."""
+        self._check_gradient_supported()
+        self._ctx.run_grad(self.kernel)
+        self.res = None
+
+    def _check_gradient_supported(self):
+        """What lowd_grad_kernel is not built for, refused before the library is called."""
+        what = None
+        if self.normalize_rows:
+            what = "normalize_rows=True (the gradient of a ratio of sums is not built)"
+        elif self.kernel == "exp-dot":
+            what = "kernel='exp-dot'"
+        elif self._dtype_code == _lib.KMVP_BF16:
+            what = "precision='bfloat16' (float16, float32 and float64 only)"
+        elif self.D > GRADIENT_MAX_D:
+            what = f"D = {self.D} > {GRADIENT_MAX_D}"
+        elif self.E > GRADIENT_MAX_E:
+            what = f"E = {self.E} > {GRADIENT_MAX_E} signal columns (pass them in blocks of {GRADIENT_MAX_E})"
+        if what is not None:
+            raise NotImplementedError(f"MI355XProduct.query_gradient doesn't support {what}.")
+
+    def get_gradient(self):
+        """(N, E, D) float64, C-contiguous: the result of the last query_gradient()."""
+        return np.ascontiguousarray(self._ctx.get_result(self.N, self.E * self.D).reshape(self.N, self.E, self.D))
 
     # -- bookkeeping ---------------------------------------------------------------
     def set_query_arguments(self, **kwargs):

@@ -173,6 +173,9 @@ int kmvp_invdist(kmvp_ctx* c) { return run_product(c, K_INVDIST, false); }
 int kmvp_invdist_norm(kmvp_ctx* c) { return run_product(c, K_INVDIST, true); }
 int kmvp_expdot(kmvp_ctx* c) { return run_product(c, K_EXPDOT, false); }
 int kmvp_expdot_norm(kmvp_ctx* c) { return run_product(c, K_EXPDOT, true); }
+int kmvp_gaussian_grad(kmvp_ctx* c) { return run_gradient(c, K_GAUSSIAN); }
+int kmvp_absexp_grad(kmvp_ctx* c) { return run_gradient(c, K_ABSEXP); }
+int kmvp_invdist_grad(kmvp_ctx* c) { return run_gradient(c, K_INVDIST); }
 
 int kmvp_get_result(kmvp_ctx* c, double* out, int64_t out_len) {
   if (!c) return KMVP_E_INVALID;

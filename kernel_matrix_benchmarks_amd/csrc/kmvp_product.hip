@@ -540,6 +540,66 @@ int run_product_t(kmvp_ctx* c, int kernel, int sig) {
   return reduce_and_finish(c, segments, NE, N, n_pad, E, sig);
 }
 
+// Gradient with respect to the targets (kmvp_lowd_grad.hpp): lowd_grad_kernel on the product's own target image and
+// source records (LAYOUT_LOWD, one target per lane), E D columns of partial sums per segment, the product's epilogue.
+hipError_t launch_lowd_grad(int kernel, int D, int E, int sig, const LowdArgs<float>& args, dim3 grid, hipStream_t s,
+                            const char** name) {
+  switch (kernel) {
+    case K_GAUSSIAN: return launch_lowd_grad_gaussian_f32(D, E, sig, args, grid, s, name);
+    case K_ABSEXP: return launch_lowd_grad_absexp_f32(D, E, sig, args, grid, s, name);
+    default: return launch_lowd_grad_invdist_f32(D, E, sig, args, grid, s, name);
+  }
+}
+hipError_t launch_lowd_grad(int kernel, int D, int E, int sig, const LowdArgs<double>& args, dim3 grid, hipStream_t s,
+                            const char** name) {
+  switch (kernel) {
+    case K_GAUSSIAN: return launch_lowd_grad_gaussian_f64(D, E, sig, args, grid, s, name);
+    case K_ABSEXP: return launch_lowd_grad_absexp_f64(D, E, sig, args, grid, s, name);
+    default: return launch_lowd_grad_invdist_f64(D, E, sig, args, grid, s, name);
+  }
+}
+
+template <typename real>
+int run_gradient_t(kmvp_ctx* c, int kernel, int sig) {
+  const int D = c->D;
+  const int E = sig == SIG_DENSITY ? 1 : c->E;
+  const int NC = E * D;  // columns of the result: e D + d
+  const int64_t N = c->N, M = c->M;
+  const real* x_raw = (const real*)(c->same_points ? c->y_raw.p : c->x_raw.p);
+  int rc;
+  const int EB = sig == SIG_DENSITY ? 0 : E;
+  const int R = (D + EB + 3) / 4 * 4;
+  LowdArgs<real> a = lowd_geometry<real>(c, 1, R, NC);
+
+  HIP_TRY(c, mark(c, 0));
+  // the product's layouts under the product's key: whichever of the two runs first on these points and this signal packs
+  const PackKey key = {LAYOUT_LOWD, kernel, 1};
+  if (points_stale(c, key)) {
+    if ((rc = ensure(c, c->xs, (size_t)D * a.n_pad * sizeof(real)))) return rc;
+    hipLaunchKernelGGL((pack_targets_kernel<real>), dim3(blocks_for(a.n_pad)), dim3(256), 0, c->stream, x_raw,
+                       (real*)c->xs.p, N, a.n_pad, D, (real)1);
+  }
+  if (signal_stale(c, key, sig)) {
+    if ((rc = ensure(c, c->rec, (size_t)(a.m_pad + LOWD_BATCH) * R * sizeof(real)))) return rc;
+    hipLaunchKernelGGL((pack_sources_kernel<real>), dim3(blocks_for(a.m_pad + LOWD_BATCH)), dim3(256), 0, c->stream,
+                       (const real*)c->y_raw.p, (const real*)c->b_raw.p, (real*)c->rec.p, M, a.m_pad + LOWD_BATCH, D, EB,
+                       R, (real)1);
+  }
+  HIP_TRY(c, hipGetLastError());
+  record_packed(c, key, sig);
+
+  if ((rc = ensure(c, c->part, (size_t)a.segments * NC * a.n_pad * sizeof(double)))) return rc;
+  a.xs = (const real*)c->xs.p;
+  a.rec = (const real*)c->rec.p;
+  a.part = (double*)c->part.p;
+  const int64_t nblocks = (int64_t)a.tile_blocks * a.segments;
+  if (nblocks > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
+  HIP_TRY(c, mark(c, 0));
+  HIP_TRY(c, launch_lowd_grad(kernel, D, E, sig, a, dim3((unsigned)nblocks), c->stream, &c->last_kernel_name));
+  HIP_TRY(c, mark(c, 1));
+  return reduce_and_finish(c, a.segments, NC, N, a.n_pad, NC, SIG_PRODUCT);
+}
+
 // Low D, many signal columns (D <= LOWD_MAX_D, E > LOWD_MAX_E): the specialised pair loop run
 // once per block of LOWD_MAX_E columns (the kernel values are recomputed per block: E = 16 costs
 // four passes of 14 issue slots per pair, against a generic kernel that is 4-5x slower).  The
@@ -1868,5 +1928,53 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
   return run_product_t<float>(c, kernel, sig);
 }
 
+
+// kmvp_<kernel>_grad: G[i, e, :] = sum_j w(s_ij) (x_i - y_j) b[j, e], left as (N, E D) in c->out.  Linear in the sources,
+// so shards, the exchange and the empty cases go through the product's tail with E D plain columns.
+int run_gradient(kmvp_ctx* c, int kernel) {
+  if (!c) return KMVP_E_INVALID;
+  c->note.clear();
+  if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
+  if (!c->have_signal) return fail(c, KMVP_E_INVALID, "kmvp_set_signal has not been called");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->M < c->m_total && !(c->exchanges() && c->world > 1) && !c->opt_partial)
+    return fail(c, KMVP_E_INVALID,
+                "the sources are a shard (M < M_total) but no multi-rank communicator is attached: call kmvp_comm_init, "
+                "or set option partial_shard = 1 to get this shard's partial sums on purpose");
+  if (c->dtype == KMVP_BF16)
+    return fail(c, KMVP_E_UNSUPPORTED, "gradient: built for float32 and float64 contexts, not for bfloat16");
+  const int E = c->density ? 1 : c->E;
+  if (c->D > LOWD_MAX_D)
+    return fail(c, KMVP_E_UNSUPPORTED, "gradient: D = " + std::to_string(c->D) + " is beyond the kernels' D <= " +
+                                           std::to_string(LOWD_MAX_D));
+  if (E > LOWD_MAX_E)
+    return fail(c, KMVP_E_UNSUPPORTED, "gradient: E = " + std::to_string(E) + " signal columns are beyond the kernels' E <= " +
+                                           std::to_string(LOWD_MAX_E) + " (run it per block of columns)");
+  const int64_t NC = (int64_t)E * c->D;
+  if (c->N == 0 || c->M == 0) {
+    int rc;
+    if (c->N > 0 && c->exchanges() && c->world > 1) {
+      // a rank whose source slice is empty still owes the other ranks its (zero) share of the sums
+      if ((rc = ensure(c, c->sums, (size_t)NC * c->N * sizeof(double)))) return rc;
+      HIP_TRY(c, mark(c, 0));
+      HIP_TRY(c, hipMemsetAsync(c->sums.p, 0, (size_t)NC * c->N * sizeof(double), c->stream));
+      HIP_TRY(c, mark(c, 1));
+      c->last_kernel_name = "none";
+      return finish_product(c, NC * c->N, c->N, c->N, (int)NC, SIG_PRODUCT);
+    }
+    if ((rc = ensure(c, c->out, (size_t)std::max<int64_t>(c->N, 1) * NC * sizeof(double)))) return rc;
+    if (c->N > 0) {
+      HIP_TRY(c, hipMemsetAsync(c->out.p, 0, (size_t)c->N * NC * sizeof(double), c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    c->out_n = c->N;
+    c->out_e = (int)NC;
+    c->last_kernel_ms = c->last_total_ms = 0.f;
+    c->last_kernel_name = "none";
+    return KMVP_OK;
+  }
+  const int sig = c->density ? SIG_DENSITY : SIG_PRODUCT;
+  return c->dtype == KMVP_F64 ? run_gradient_t<double>(c, kernel, sig) : run_gradient_t<float>(c, kernel, sig);
+}
 
 }  // namespace kmvp
