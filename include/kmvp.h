@@ -84,7 +84,8 @@ int kmvp_set_points(kmvp_ctx* ctx, const void* y, int64_t M, const void* x_or_nu
 /* BaseAlgorithm.fit (base.py:84, bruteforce.py:113-120: the reference builds its kernel matrix
  * there, timed as build_time).  Nothing of the matrix is ever built here; what CAN be built from the
  * points alone is: for the Gaussian on clouds that qualify for the cell form (fast_sqdists 3 / auto),
- * the grid, the cell order (radix sort) and the tile lists.  kernel: 0 gaussian, 1 absexp, 2 invdist.
+ * the grid, the cell order (radix sort) and the tile lists.  kernel: 0 gaussian, 1 absexp, 2 invdist, 3 matern32,
+ * 4 matern52 (accepted; nothing is built for them).
  * Optional: the first query does the same work when fit was not called. */
 int kmvp_fit(kmvp_ctx* ctx, int kernel);
 
@@ -122,6 +123,24 @@ int kmvp_invdist_norm(kmvp_ctx* ctx);
  * (the plugin then uses the Gaussian identity, with its range check). */
 int kmvp_expdot(kmvp_ctx* ctx);
 int kmvp_expdot_norm(kmvp_ctx* ctx);
+/* Matern covariances nu = 3/2 and nu = 5/2 (an extension: the reference has exp(-r), which is nu = 1/2, and no other
+ * member of the family).  With s = |x - y|^2, r = sqrt(s):
+ *   kmvp_matern32  t = sqrt(3) r,  k = (1 + t) e^-t
+ *   kmvp_matern52  t = sqrt(5) r,  k = (1 + t + t^2 / 3) e^-t
+ * at length scale 1 -- sklearn.gaussian_process.kernels.Matern(length_scale=1, nu=1.5 / 2.5); a length scale l is the
+ * caller's scaling of the points by 1 / l, as for the Gaussian.  Both matrices are symmetric positive definite.
+ * A pair at infinite distance (a float32 squared distance that overflowed included) contributes exactly 0, never
+ * inf * 0.
+ * float32 and float64 contexts, any D and E, _norm and density estimation as for the other kernels, always in the
+ * difference form (lowd_kernel up to D = 8, lowd_mid_kernel up to D = 128, lowd_big_kernel beyond; more than four
+ * signal columns at D <= 8 in blocks of four); sharded like the others (no index-based rule: j_offset / M_total do not
+ * enter the values).  KMVP_E_UNSUPPORTED for bfloat16 contexts and when "fast_sqdists" asks for a matrix-core form
+ * (1 .. 4) explicitly: none is built for them; the default -1 and 0 take the difference form, and
+ * kmvp_last_dispatch_note is "". */
+int kmvp_matern32(kmvp_ctx* ctx);
+int kmvp_matern32_norm(kmvp_ctx* ctx);
+int kmvp_matern52(kmvp_ctx* ctx);
+int kmvp_matern52_norm(kmvp_ctx* ctx);
 
 /* Gradient of the product with respect to the target points (an extension: no reference method stands behind it --
  * the force field of an N-body sum, the gradient of a kernel density estimate, the derivative of a Kriging / GP mean).
@@ -134,6 +153,10 @@ int kmvp_expdot_norm(kmvp_ctx* ctx);
  *   kmvp_invdist_grad   w = -1 / r^3.  The pairs zeroed by the flat-index rule (bruteforce.py:13-14; j_offset / M_total as
  *                       in the product) contribute 0.  A coincident pair that is NOT zeroed gives inf * 0: that row of G is
  *                       NaN in every component -- exactly the rows where kmvp_invdist is inf.
+ *   kmvp_matern32_grad  w = -3 e^-t,  t = sqrt(3) r
+ *   kmvp_matern52_grad  w = -(5/3) (1 + t) e^-t,  t = sqrt(5) r.  Both weights are finite and smooth at r = 0: a
+ *                       coincident pair (the own pair of same_points) contributes w * 0 = 0 by itself; a pair at
+ *                       infinite distance contributes exactly 0.
  * The targets are independent variables, also with same_points: this is the derivative in the first argument (a
  * caller who wants the total derivative of a symmetric sum adds the transpose term).  Density estimation (b == NULL)
  * means b = 1, E = 1.  Row normalisation is not differentiated.
@@ -145,6 +168,8 @@ int kmvp_expdot_norm(kmvp_ctx* ctx);
 int kmvp_gaussian_grad(kmvp_ctx* ctx);
 int kmvp_absexp_grad(kmvp_ctx* ctx);
 int kmvp_invdist_grad(kmvp_ctx* ctx);
+int kmvp_matern32_grad(kmvp_ctx* ctx);
+int kmvp_matern52_grad(kmvp_ctx* ctx);
 
 /* BaseProduct.get_result (base.py:107-116): (N,E) float64 row-major. */
 int kmvp_get_result(kmvp_ctx* ctx, double* out, int64_t out_len);
@@ -163,6 +188,11 @@ int kmvp_gaussian_cg_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int
                            double* out_b, int* iters, double* resid);
 int kmvp_absexp_cg_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int maxit,
                          double* out_b, int* iters, double* resid);
+/* The Matern matrices are positive definite: conjugate gradients, same contract (float32 / float64 contexts). */
+int kmvp_matern32_cg_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int maxit,
+                           double* out_b, int* iters, double* resid);
+int kmvp_matern52_cg_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int maxit,
+                           double* out_b, int* iters, double* resid);
 /* Same contract for the inverse-distance kernel, whose matrix (zero diagonal,
  * bruteforce.py:13-14) is symmetric but INDEFINITE: MINRES instead of CG. */
 int kmvp_invdist_minres_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int maxit,
@@ -177,7 +207,7 @@ int kmvp_invdist_minres_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, 
  *   vectors are float64) and is added to K v inside the device-resident iteration, after the all-reduce of a
  *   sharded product; rtol, *resid and the 1.5 rtol verdict of the solvers are then about A b = a.
  *   KMVP_E_INVALID: a non-finite ridge or d_i (here); at solve time, n != N, and for the CG entries (Gaussian,
- *   exp(-r): positive definite only with a non-negative shift) any ridge + d_i < 0.  MINRES takes any sign. */
+ *   exp(-r), Matern: positive definite only with a non-negative shift) any ridge + d_i < 0.  MINRES takes any sign. */
 int kmvp_set_solver_diagonal(kmvp_ctx* ctx, const double* d_or_null, int64_t n, double ridge);
 
 /* Source sharding over the GPUs of one node, one process per GPU:

@@ -37,14 +37,24 @@ SYMBOLS = [
     ("kmvp_invdist_norm", _c.c_int, [_c.c_void_p]),
     ("kmvp_expdot", _c.c_int, [_c.c_void_p]),
     ("kmvp_expdot_norm", _c.c_int, [_c.c_void_p]),
+    ("kmvp_matern32", _c.c_int, [_c.c_void_p]),
+    ("kmvp_matern32_norm", _c.c_int, [_c.c_void_p]),
+    ("kmvp_matern52", _c.c_int, [_c.c_void_p]),
+    ("kmvp_matern52_norm", _c.c_int, [_c.c_void_p]),
     ("kmvp_gaussian_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_absexp_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_invdist_grad", _c.c_int, [_c.c_void_p]),
+    ("kmvp_matern32_grad", _c.c_int, [_c.c_void_p]),
+    ("kmvp_matern52_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_get_result", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("kmvp_gaussian_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_absexp_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                         _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
+    ("kmvp_matern32_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
+                                          _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
+    ("kmvp_matern52_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
+                                          _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_invdist_minres_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                              _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_set_solver_diagonal", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_double]),
@@ -64,6 +74,8 @@ SYMBOLS = [
 
 HOST_ALLREDUCE_FN = _c.CFUNCTYPE(_c.c_int, _c.c_void_p, _c.POINTER(_c.c_double), _c.c_int64, _c.c_int)
 OP_SUM, OP_MIN = 0, 1
+# kernel codes of kmvp_fit (include/kmvp.h)
+FIT_CODES = {"gaussian": 0, "absolute-exponential": 1, "inverse-distance": 2, "matern-3/2": 3, "matern-5/2": 4}
 
 _lib = None
 
@@ -155,7 +167,7 @@ class Context:
             int(j_offset), int(M if M_total is None else M_total)))
 
     def fit(self, kernel):
-        self._check(self._lib.kmvp_fit(self._ctx, {"gaussian": 0, "absolute-exponential": 1, "inverse-distance": 2}[kernel]))
+        self._check(self._lib.kmvp_fit(self._ctx, FIT_CODES[kernel]))
 
     def set_signal(self, b):
         if b is None:
@@ -177,6 +189,10 @@ class Context:
             ("inverse-distance", True): self._lib.kmvp_invdist_norm,
             ("exp-dot", False): self._lib.kmvp_expdot,
             ("exp-dot", True): self._lib.kmvp_expdot_norm,
+            ("matern-3/2", False): self._lib.kmvp_matern32,
+            ("matern-3/2", True): self._lib.kmvp_matern32_norm,
+            ("matern-5/2", False): self._lib.kmvp_matern52,
+            ("matern-5/2", True): self._lib.kmvp_matern52_norm,
         }[(kernel, bool(normalize_rows))]
         self._check(entry(self._ctx))
 
@@ -186,6 +202,8 @@ class Context:
             "gaussian": self._lib.kmvp_gaussian_grad,
             "absolute-exponential": self._lib.kmvp_absexp_grad,
             "inverse-distance": self._lib.kmvp_invdist_grad,
+            "matern-3/2": self._lib.kmvp_matern32_grad,
+            "matern-5/2": self._lib.kmvp_matern52_grad,
         }.get(kernel)
         if entry is None:
             raise NotImplementedError(f"no gradient for kernel {kernel}")
@@ -204,6 +222,8 @@ class Context:
             "gaussian": self._lib.kmvp_gaussian_cg_solve,
             "absolute-exponential": self._lib.kmvp_absexp_cg_solve,
             "inverse-distance": self._lib.kmvp_invdist_minres_solve,  # indefinite: MINRES
+            "matern-3/2": self._lib.kmvp_matern32_cg_solve,
+            "matern-5/2": self._lib.kmvp_matern52_cg_solve,
         }.get(kernel)
         if entry is None:
             raise NotImplementedError(f"no solver for kernel {kernel}")

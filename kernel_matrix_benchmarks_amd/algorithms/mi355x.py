@@ -28,7 +28,13 @@ from kernel_matrix_benchmarks_amd import _lib
 from kernel_matrix_benchmarks_amd.algorithms.base import BaseProduct, BaseSolver
 from kernel_matrix_benchmarks_amd import sharding
 
-SUPPORTED_KERNELS = ("gaussian", "absolute-exponential", "inverse-distance", "exp-dot")
+SUPPORTED_KERNELS = ("gaussian", "absolute-exponential", "inverse-distance", "exp-dot", "matern-3/2", "matern-5/2")
+# "matern-3/2", "matern-5/2": the Matern covariances (1 + t) e^-t, t = sqrt(3) r, and (1 + t + t^2/3) e^-t, t = sqrt(5) r,
+# at length scale 1 (sklearn's Matern(length_scale=1, nu=1.5 / 2.5); a length scale is the caller's scaling of the
+# points).  An extension -- the reference has nu = 1/2 only, as "absolute-exponential" -- checked against the
+# definition (the tests' matern_reference).  float16 / float32 / float64, difference form only: bfloat16 and an
+# explicit fast_sqdists are refused.
+MATERN_KERNELS = ("matern-3/2", "matern-5/2")
 # "exp-dot": k(x, y) = exp(<x, y>), the transformer attention kernel the reference's README defines
 # (README.md:51-59) but its plugins do not implement (bruteforce.py:18-22 has the other three): parity
 # unpinned, checked against a direct numpy evaluation only (the tests' exp_dot_product).  Two routes:
@@ -102,6 +108,14 @@ class MI355XProduct(BaseProduct):
         # None lets the library pick the cheapest form that is as accurate as the difference form.
         if fast_sqdists not in (None, False, True, "centred", "cells", "cells-valu"):
             raise ValueError("fast_sqdists must be None, False, True, 'centred', 'cells' or 'cells-valu'")
+        if kernel in MATERN_KERNELS:
+            # what the library has no kernel for (it would answer KMVP_E_UNSUPPORTED), refused before it is called
+            if self._dtype_code == _lib.KMVP_BF16:
+                raise NotImplementedError(f"MI355XProduct doesn't support kernel {kernel} with precision='bfloat16' "
+                                          "(float16, float32 and float64 only).")
+            if fast_sqdists not in (None, False):
+                raise NotImplementedError(f"MI355XProduct doesn't support kernel {kernel} with fast_sqdists={fast_sqdists!r}: "
+                                          "the Matern kernels run in the difference form only (None or False).")
         self.fast_sqdists = fast_sqdists
         self._options = dict(targets_per_lane=targets_per_lane, feed=feed, segments=segments,
                              chunk=chunk, fast_tiles=fast_tiles)
@@ -172,6 +186,7 @@ class MI355XProduct(BaseProduct):
             lo, hi = self._shard
             # Gaussian (no index-based rule): shard the sources cell by cell instead of in the caller's
             # order -- every rank derives the same permutation from the full cloud it was handed
+            # (every other kernel, the Matern kernels included, keeps the caller's source order)
             self._order = (sharding.spatial_order(y) if self._device_kernel_fn == "gaussian" and self._host_dtype == np.float32
                            else None)
             if self._order is not None:
@@ -337,7 +352,7 @@ class MI355XProduct(BaseProduct):
 
 class MI355XSolver(BaseSolver):
     """Solves K b = a with the HIP product as the operator: conjugate gradients for the positive
-    definite Gaussian / exp(-r) matrices, MINRES for the symmetric indefinite inverse-distance
+    definite Gaussian / exp(-r) / Matern matrices, MINRES for the symmetric indefinite inverse-distance
     matrix (zero diagonal, bruteforce.py:13-14).
 
     ``ridge`` (an extension: the reference's lstsq solves the bare system) regularises it: (K + ridge I) b = a with a

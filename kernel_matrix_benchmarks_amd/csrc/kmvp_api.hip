@@ -140,7 +140,8 @@ int kmvp_set_points(kmvp_ctx* c, const void* y, int64_t M, const void* x_or_null
 int kmvp_fit(kmvp_ctx* c, int kernel) {
   if (!c) return KMVP_E_INVALID;
   if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
-  if (kernel < 0 || kernel > 2) return fail(c, KMVP_E_INVALID, "kernel must be 0, 1 or 2");
+  if (kernel < 0 || kernel > 4) return fail(c, KMVP_E_INVALID, "kernel must be 0, 1, 2, 3 or 4");
+  if (kernel > 2) return KMVP_OK;  // Matern 3/2, 5/2: the difference form has nothing the points alone determine
   HIP_TRY(c, hipSetDevice(c->device));
   return prepare_points(c, kernel);
 }
@@ -173,9 +174,15 @@ int kmvp_invdist(kmvp_ctx* c) { return run_product(c, K_INVDIST, false); }
 int kmvp_invdist_norm(kmvp_ctx* c) { return run_product(c, K_INVDIST, true); }
 int kmvp_expdot(kmvp_ctx* c) { return run_product(c, K_EXPDOT, false); }
 int kmvp_expdot_norm(kmvp_ctx* c) { return run_product(c, K_EXPDOT, true); }
+int kmvp_matern32(kmvp_ctx* c) { return run_product(c, K_MATERN32, false); }
+int kmvp_matern32_norm(kmvp_ctx* c) { return run_product(c, K_MATERN32, true); }
+int kmvp_matern52(kmvp_ctx* c) { return run_product(c, K_MATERN52, false); }
+int kmvp_matern52_norm(kmvp_ctx* c) { return run_product(c, K_MATERN52, true); }
 int kmvp_gaussian_grad(kmvp_ctx* c) { return run_gradient(c, K_GAUSSIAN); }
 int kmvp_absexp_grad(kmvp_ctx* c) { return run_gradient(c, K_ABSEXP); }
 int kmvp_invdist_grad(kmvp_ctx* c) { return run_gradient(c, K_INVDIST); }
+int kmvp_matern32_grad(kmvp_ctx* c) { return run_gradient(c, K_MATERN32); }
+int kmvp_matern52_grad(kmvp_ctx* c) { return run_gradient(c, K_MATERN52); }
 
 int kmvp_get_result(kmvp_ctx* c, double* out, int64_t out_len) {
   if (!c) return KMVP_E_INVALID;
@@ -197,6 +204,14 @@ int kmvp_gaussian_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int m
 int kmvp_absexp_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
                          int* iters, double* resid) {
   return cg_solve(c, K_ABSEXP, a, E, rtol, maxit, out_b, iters, resid);
+}
+int kmvp_matern32_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
+                           int* iters, double* resid) {
+  return cg_solve(c, K_MATERN32, a, E, rtol, maxit, out_b, iters, resid);
+}
+int kmvp_matern52_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
+                           int* iters, double* resid) {
+  return cg_solve(c, K_MATERN52, a, E, rtol, maxit, out_b, iters, resid);
 }
 
 int kmvp_invdist_minres_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,

@@ -40,6 +40,10 @@ KMVP_DECLARE_LOWD(launch_lowd_invdist_f32, float)
 KMVP_DECLARE_LOWD(launch_lowd_gaussian_f64, double)
 KMVP_DECLARE_LOWD(launch_lowd_absexp_f64, double)
 KMVP_DECLARE_LOWD(launch_lowd_invdist_f64, double)
+KMVP_DECLARE_LOWD(launch_lowd_matern32_f32, float)
+KMVP_DECLARE_LOWD(launch_lowd_matern52_f32, float)
+KMVP_DECLARE_LOWD(launch_lowd_matern32_f64, double)
+KMVP_DECLARE_LOWD(launch_lowd_matern52_f64, double)
 
 // Gradient with respect to the targets (kmvp_lowd_grad.hpp; kmvp_lowd_grad_inst.hip, one unit per kernel x precision):
 // D <= LOWD_MAX_D, E <= LOWD_MAX_E, sig SIG_PRODUCT or SIG_DENSITY; hipErrorInvalidValue otherwise.
@@ -52,6 +56,10 @@ KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_invdist_f32, float)
 KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_gaussian_f64, double)
 KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_absexp_f64, double)
 KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_invdist_f64, double)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_matern32_f32, float)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_matern52_f32, float)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_matern32_f64, double)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_matern52_f64, double)
 
 // bf16 MFMA path (kmvp_mfma.hpp): largest shapes instantiated
 constexpr int MFMA_MAX_KS = 9;  // D <= 16*9 - 6 = 138

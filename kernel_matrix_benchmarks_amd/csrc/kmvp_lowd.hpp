@@ -35,9 +35,10 @@
 
 namespace kmvp {
 
-enum : int { K_GAUSSIAN = 0, K_ABSEXP = 1, K_INVDIST = 2, K_EXPDOT = 3, K_GAUSSIAN_SHIFTED = 4 };
+enum : int { K_GAUSSIAN = 0, K_ABSEXP = 1, K_INVDIST = 2, K_EXPDOT = 3, K_GAUSSIAN_SHIFTED = 4, K_MATERN32 = 5, K_MATERN52 = 6 };
 // K_EXPDOT: host-side only (run_product) and the bf16 matrix-core kernels; K_GAUSSIAN_SHIFTED: the bf16 matrix-core kernels
 // only -- the Gaussian with exp(<x,y>)'s per-target running shift, taken when targets != sources (kmvp_mfma.hpp)
+// K_MATERN32 / K_MATERN52: the Matern covariances nu = 3/2, 5/2 at length scale 1 (include/kmvp.h), difference form only
 
 // signal mode of a launch
 enum : int {
@@ -68,12 +69,44 @@ __device__ __forceinline__ float kexp2(float v) { return __builtin_amdgcn_exp2f(
 // bruteforce.py:53-54).  The constant that turns exp() into the hardware's exp2() multiplies
 // the squared distance, not the coordinates: scaling x and y before the subtraction would
 // round every coordinate by eps |x| and lose the pairs of clouds far from the origin.
+//
+// Matern family at length scale 1: t = sqrt(2 nu) r and P_DEG(t) e^{-t} with
+//   P_0 = 1,  P_1 = 1 + t,  P_2 = 1 + t + t^2 / 3
+//   value:            nu = 3/2: P_1 e^{-t}        nu = 5/2: P_2 e^{-t}
+//   gradient weight:  nu = 3/2: -3 P_0 e^{-t}     nu = 5/2: -(5/3) P_1 e^{-t}      (kmvp_lowd_grad.hpp)
+// s = +inf reaches this from pad records (y = +inf), from a float32 squared distance that overflowed and from
+// kexp_neg_f64's own clamp; P(inf) * 0 would be NaN where the other kernels give 0.  The exponent is therefore clamped from
+// above BEFORE the polynomial, at a point where e^{-t} is exactly 0 already, so that s = inf returns exactly 0 and no
+// finite result changes.
+// float32: a = min(sqrt(2 nu) log2(e) r, 192) is the exponent of exp2 itself (2^-192 is below the smallest denormal
+// 2^-149: v_exp_f32 returns 0 from a = 150 on) and the polynomial is taken in a, t = a ln 2.  Per pair after s:
+// v_sqrt, v_mul, v_min, v_exp, DEG v_fma, v_mul -- nu = 3/2: 6 instructions, nu = 5/2: 7 (two of them quarter-rate
+// transcendentals), against exp(-r)'s 3.
+template <int KERNEL>
+constexpr double matern_sqrt_2nu() {
+  return KERNEL == K_MATERN32 ? 1.7320508075688772 : 2.23606797749979;  // sqrt(3), sqrt(5)
+}
+template <int KERNEL, int DEG>
+__device__ __forceinline__ float matern_value(float s) {
+  constexpr float c = (float)(matern_sqrt_2nu<KERNEL>() * 1.4426950408889634);
+  constexpr float LN2 = 0.6931471805599453f;
+  const float a = __builtin_fminf(__builtin_amdgcn_sqrtf(s) * c, 192.0f);
+  const float e = kexp2(-a);
+  if constexpr (DEG == 0) return e;
+  else if constexpr (DEG == 1) return fmaf(a, LN2, 1.0f) * e;
+  else return fmaf(a, fmaf(a, (float)(0.6931471805599453 * 0.6931471805599453 / 3.0), LN2), 1.0f) * e;
+}
+
 template <int KERNEL>
 __device__ __forceinline__ float kval(float s) {
   if constexpr (KERNEL == K_GAUSSIAN) {
     return kexp2(s * -1.4426950408889634f);  // exp(-s) = 2^(-s log2 e)
   } else if constexpr (KERNEL == K_ABSEXP) {
     return kexp2(__builtin_amdgcn_sqrtf(s) * -1.4426950408889634f);
+  } else if constexpr (KERNEL == K_MATERN32) {
+    return matern_value<K_MATERN32, 1>(s);
+  } else if constexpr (KERNEL == K_MATERN52) {
+    return matern_value<K_MATERN52, 2>(s);
   } else {
     return __builtin_amdgcn_rsqf(s);  // 1/sqrt(0) = inf, as the reference's 1/np.sqrt
   }
@@ -101,10 +134,34 @@ __device__ __forceinline__ double kexp_neg_f64(double s, const double* __restric
   return ldexp(t * p, ni >> 6);
 }
 
+// float64 Matern (see matern_value above): r from the same rsq + one-step form as exp(-r) below, t = sqrt(2 nu) r clamped
+// at kexp_neg_f64's own 800 (e^-800 = 2^-1154: exactly 0), then the polynomial.  Per pair after s: exp(-r)'s
+// instructions (v_rsq_f64, 6 fp64 operations and the two compares with their selects for r; 15 in kexp_neg_f64, whose own
+// v_min folds into this one) + v_mul, DEG v_fma, v_mul: nu = 3/2 three more fp64 operations than exp(-r), nu = 5/2 four.
+template <int KERNEL, int DEG>
+__device__ __forceinline__ double matern_value(double s, const double* __restrict__ tab) {
+  const double y0 = __builtin_amdgcn_rsq(s);
+  const double e = fma(-s * y0, y0, 1.0);
+  const double r = s * fma(y0 * e, fma(e, 0.375, 0.5), y0);
+  const double t = fmin(((s == 0.0 || s == (double)INFINITY) ? s : r) * matern_sqrt_2nu<KERNEL>(), 800.0);
+  const double ex = kexp_neg_f64(t, tab);
+  if constexpr (DEG == 0) return ex;
+  else if constexpr (DEG == 1) return (1.0 + t) * ex;
+  else return fma(t, fma(t, 1.0 / 3.0, 1.0), 1.0) * ex;
+}
+template <int KERNEL, int DEG>
+__device__ __forceinline__ float matern_value(float s, const double*) {
+  return matern_value<KERNEL, DEG>(s);
+}
+
 template <int KERNEL>
 __device__ __forceinline__ double kval(double s, const double* __restrict__ tab) {
   if constexpr (KERNEL == K_GAUSSIAN) {
     return kexp_neg_f64(s, tab);
+  } else if constexpr (KERNEL == K_MATERN32) {
+    return matern_value<K_MATERN32, 1>(s, tab);
+  } else if constexpr (KERNEL == K_MATERN52) {
+    return matern_value<K_MATERN52, 2>(s, tab);
   } else if constexpr (KERNEL == K_ABSEXP) {
     // sqrt(s) = s / sqrt(s) from the same estimate-and-one-step as 1/sqrt(s) below (the compiler's IEEE sqrt spends about
     // twice the instructions on scaling and a second correction; s is a sum of squares: never negative, denormal only

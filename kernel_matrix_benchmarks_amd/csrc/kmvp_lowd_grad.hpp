@@ -2,6 +2,8 @@
 // stands behind it; include/kmvp.h kmvp_<kernel>_grad):
 //   G[i, e, :] = sum_j w(s_ij) (x_i - y_j) b[j, e],   s = |x_i - y_j|^2
 //   gaussian exp(-s):  w = -2 k        absexp exp(-r):  w = -k / r        invdist 1/r:  w = -1 / r^3
+//   Matern nu = 3/2, t = sqrt(3) r:  w = -3 e^{-t}        nu = 5/2, t = sqrt(5) r:  w = -(5/3) (1 + t) e^{-t}
+//   (both finite and smooth at r = 0: no convention, no select; the own pair of same_points gives w * 0 = 0 by itself)
 //
 // lowd_kernel's structure (kmvp_lowd.hpp) with one variant per (D, E): lanes = targets, one target per lane,
 // LDS-staged source records -- the SAME records and target image the product packs (LAYOUT_LOWD), so a product and
@@ -29,11 +31,16 @@ namespace kmvp {
 __device__ __forceinline__ bool positive_normal(float s) { return __builtin_amdgcn_classf(s, 0x100); }
 __device__ __forceinline__ bool positive_normal(double s) { return __builtin_amdgcn_class(s, 0x100); }
 
-// |w(s)| without its constant: k (gaussian), q^3 (1/r), k q (exp(-r)), q = 1/sqrt(s) as kval<K_INVDIST> computes it
+// |w(s)| without its constant: k (gaussian), q^3 (1/r), k q (exp(-r)), q = 1/sqrt(s) as kval<K_INVDIST> computes it;
+// Matern: the polynomial of one degree less than the value's (matern_value, kmvp_lowd.hpp: exactly 0 at s = inf)
 template <int KERNEL, typename real>
 __device__ __forceinline__ real grad_weight(real s, const double* __restrict__ tab) {
   if constexpr (KERNEL == K_GAUSSIAN) {
     return kval<K_GAUSSIAN>(s, tab);
+  } else if constexpr (KERNEL == K_MATERN32) {
+    return matern_value<K_MATERN32, 0>(s, tab);
+  } else if constexpr (KERNEL == K_MATERN52) {
+    return matern_value<K_MATERN52, 1>(s, tab);
   } else {
     const real q = kval<K_INVDIST>(s, tab);
     if constexpr (KERNEL == K_INVDIST) return q * q * q;
@@ -43,7 +50,7 @@ __device__ __forceinline__ real grad_weight(real s, const double* __restrict__ t
 // the constant: applied to the partial sums
 template <int KERNEL>
 __device__ __forceinline__ constexpr double grad_constant() {
-  return KERNEL == K_GAUSSIAN ? -2.0 : -1.0;
+  return KERNEL == K_GAUSSIAN ? -2.0 : KERNEL == K_MATERN32 ? -3.0 : KERNEL == K_MATERN52 ? -5.0 / 3.0 : -1.0;
 }
 
 template <int D, int E, int SIG>

@@ -1,6 +1,6 @@
 // Instantiations of the gradient pair-loop kernel (kmvp_lowd_grad.hpp) for ONE kernel function and ONE precision.
-// Compiled six times (see Makefile), as kmvp_lowd_inst.hip:
-//   -DKMVP_KERNEL={0,1,2}  -DKMVP_REAL={float,double}  -DKMVP_FN=launch_lowd_grad_<k>_<p>
+// Compiled ten times (see Makefile), as kmvp_lowd_inst.hip:
+//   -DKMVP_KERNEL={0,1,2,5,6}  -DKMVP_REAL={float,double}  -DKMVP_FN=launch_lowd_grad_<k>_<p>
 // One variant per (D, E): D = 1 .. LOWD_MAX_D, E = 1 .. LOWD_MAX_E and density mode.
 #include "kmvp_internal.hpp"
 #include "kmvp_lowd_grad.hpp"

@@ -1,8 +1,8 @@
 // Instantiations of the low-D pair-loop kernels for ONE kernel function and ONE
-// precision.  Compiled six times (see Makefile):
-//   -DKMVP_KERNEL={0,1,2}  -DKMVP_REAL={float,double}  -DKMVP_FN=launch_lowd_<k>_<p>
+// precision.  Compiled ten times (see Makefile):
+//   -DKMVP_KERNEL={0,1,2,5,6}  -DKMVP_REAL={float,double}  -DKMVP_FN=launch_lowd_<k>_<p>
 // so that each kernel function is its own set of device kernels (no runtime
-// kernel dispatch inside device code) and the six units build in parallel.
+// kernel dispatch inside device code) and the ten units build in parallel.
 #include "kmvp_internal.hpp"
 
 #ifndef KMVP_KERNEL

@@ -27,7 +27,10 @@ hipError_t launch_lowd<float>(int kernel, int D, int E, int sig, LowdTuning tune
   switch (kernel) {
     case K_GAUSSIAN: return launch_lowd_gaussian_f32(D, E, sig, tune, args, grid, s, name);
     case K_ABSEXP: return launch_lowd_absexp_f32(D, E, sig, tune, args, grid, s, name);
-    default: return launch_lowd_invdist_f32(D, E, sig, tune, args, grid, s, name);
+    case K_INVDIST: return launch_lowd_invdist_f32(D, E, sig, tune, args, grid, s, name);
+    case K_MATERN32: return launch_lowd_matern32_f32(D, E, sig, tune, args, grid, s, name);
+    case K_MATERN52: return launch_lowd_matern52_f32(D, E, sig, tune, args, grid, s, name);
+    default: return hipErrorInvalidValue;  // (an id without a difference-form unit never reaches a launch)
   }
 }
 template <>
@@ -37,7 +40,10 @@ hipError_t launch_lowd<double>(int kernel, int D, int E, int sig, LowdTuning tun
   switch (kernel) {
     case K_GAUSSIAN: return launch_lowd_gaussian_f64(D, E, sig, tune, args, grid, s, name);
     case K_ABSEXP: return launch_lowd_absexp_f64(D, E, sig, tune, args, grid, s, name);
-    default: return launch_lowd_invdist_f64(D, E, sig, tune, args, grid, s, name);
+    case K_INVDIST: return launch_lowd_invdist_f64(D, E, sig, tune, args, grid, s, name);
+    case K_MATERN32: return launch_lowd_matern32_f64(D, E, sig, tune, args, grid, s, name);
+    case K_MATERN52: return launch_lowd_matern52_f64(D, E, sig, tune, args, grid, s, name);
+    default: return hipErrorInvalidValue;  // (an id without a difference-form unit never reaches a launch)
   }
 }
 
@@ -58,9 +64,17 @@ hipError_t launch_generic<float>(int kernel, int sig, const float* x, const floa
     case K_ABSEXP:
       return launch_lowd_absexp_f32_generic(sig, x, y, b, part, n, n_pad, m, D, E, NE, segments,
                                             seg_len, j_offset, m_total, s, name);
-    default:
+    case K_INVDIST:
       return launch_lowd_invdist_f32_generic(sig, x, y, b, part, n, n_pad, m, D, E, NE, segments,
                                              seg_len, j_offset, m_total, s, name);
+    case K_MATERN32:
+      return launch_lowd_matern32_f32_generic(sig, x, y, b, part, n, n_pad, m, D, E, NE, segments,
+                                              seg_len, j_offset, m_total, s, name);
+    case K_MATERN52:
+      return launch_lowd_matern52_f32_generic(sig, x, y, b, part, n, n_pad, m, D, E, NE, segments,
+                                              seg_len, j_offset, m_total, s, name);
+    default:
+      return hipErrorInvalidValue;
   }
 }
 template <>
@@ -76,9 +90,17 @@ hipError_t launch_generic<double>(int kernel, int sig, const double* x, const do
     case K_ABSEXP:
       return launch_lowd_absexp_f64_generic(sig, x, y, b, part, n, n_pad, m, D, E, NE, segments,
                                             seg_len, j_offset, m_total, s, name);
-    default:
+    case K_INVDIST:
       return launch_lowd_invdist_f64_generic(sig, x, y, b, part, n, n_pad, m, D, E, NE, segments,
                                              seg_len, j_offset, m_total, s, name);
+    case K_MATERN32:
+      return launch_lowd_matern32_f64_generic(sig, x, y, b, part, n, n_pad, m, D, E, NE, segments,
+                                              seg_len, j_offset, m_total, s, name);
+    case K_MATERN52:
+      return launch_lowd_matern52_f64_generic(sig, x, y, b, part, n, n_pad, m, D, E, NE, segments,
+                                              seg_len, j_offset, m_total, s, name);
+    default:
+      return hipErrorInvalidValue;
   }
 }
 
@@ -547,7 +569,10 @@ hipError_t launch_lowd_grad(int kernel, int D, int E, int sig, const LowdArgs<fl
   switch (kernel) {
     case K_GAUSSIAN: return launch_lowd_grad_gaussian_f32(D, E, sig, args, grid, s, name);
     case K_ABSEXP: return launch_lowd_grad_absexp_f32(D, E, sig, args, grid, s, name);
-    default: return launch_lowd_grad_invdist_f32(D, E, sig, args, grid, s, name);
+    case K_INVDIST: return launch_lowd_grad_invdist_f32(D, E, sig, args, grid, s, name);
+    case K_MATERN32: return launch_lowd_grad_matern32_f32(D, E, sig, args, grid, s, name);
+    case K_MATERN52: return launch_lowd_grad_matern52_f32(D, E, sig, args, grid, s, name);
+    default: return hipErrorInvalidValue;
   }
 }
 hipError_t launch_lowd_grad(int kernel, int D, int E, int sig, const LowdArgs<double>& args, dim3 grid, hipStream_t s,
@@ -555,7 +580,10 @@ hipError_t launch_lowd_grad(int kernel, int D, int E, int sig, const LowdArgs<do
   switch (kernel) {
     case K_GAUSSIAN: return launch_lowd_grad_gaussian_f64(D, E, sig, args, grid, s, name);
     case K_ABSEXP: return launch_lowd_grad_absexp_f64(D, E, sig, args, grid, s, name);
-    default: return launch_lowd_grad_invdist_f64(D, E, sig, args, grid, s, name);
+    case K_INVDIST: return launch_lowd_grad_invdist_f64(D, E, sig, args, grid, s, name);
+    case K_MATERN32: return launch_lowd_grad_matern32_f64(D, E, sig, args, grid, s, name);
+    case K_MATERN52: return launch_lowd_grad_matern52_f64(D, E, sig, args, grid, s, name);
+    default: return hipErrorInvalidValue;
   }
 }
 
@@ -1751,6 +1779,16 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
   if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
   if (!c->have_signal) return fail(c, KMVP_E_INVALID, "kmvp_set_signal has not been called");
   HIP_TRY(c, hipSetDevice(c->device));
+  const bool matern = kernel == K_MATERN32 || kernel == K_MATERN52;
+  if (matern) {
+    // Matern 3/2, 5/2: the difference form only (lowd_kernel, lowd_mid_kernel, lowd_big_kernel).  What is not built is
+    // refused, never served by another kernel's path
+    if (c->dtype == KMVP_BF16)
+      return fail(c, KMVP_E_UNSUPPORTED, "Matern kernels: built for float32 and float64 contexts, not for bfloat16");
+    if (c->opt_fast >= 1)
+      return fail(c, KMVP_E_UNSUPPORTED, "Matern kernels: fast_sqdists = " + std::to_string(c->opt_fast) +
+                                             " asks for a matrix-core form that is not built for them (-1 or 0: the difference form)");
+  }
   if (c->M < c->m_total && !(c->exchanges() && c->world > 1) && !c->opt_partial)
     // a slice of the sources and nobody to sum the shards with: the result would be this rank's partial
     // sums passed off as the product
@@ -1818,6 +1856,11 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
     return run_product_fastmm(c, K_GAUSSIAN, sig, true);
   }
   if (c->dtype == KMVP_BF16) return run_product_mfma(c, kernel, sig);
+  if (matern) {  // always the difference form, with an empty dispatch note: no faster form exists that could have applied
+    if (c->D <= LOWD_MAX_D && !c->density && c->E > LOWD_MAX_E)
+      return c->dtype == KMVP_F64 ? run_product_blocked<double>(c, kernel, sig) : run_product_blocked<float>(c, kernel, sig);
+    return c->dtype == KMVP_F64 ? run_product_t<double>(c, kernel, sig) : run_product_t<float>(c, kernel, sig);
+  }
   const bool f32 = c->dtype == KMVP_F32 && c->centre_ver == c->points_ver;  // float32, clouds measured (measure_clouds)
   bool cells = false;  // the float32 Gaussian's cell form serves this product (cells_usable)
   if (f32 && kernel == K_GAUSSIAN && c->D <= CELL_MAX_D) {
