@@ -171,6 +171,37 @@ int kmvp_invdist_grad(kmvp_ctx* ctx);
 int kmvp_matern32_grad(kmvp_ctx* ctx);
 int kmvp_matern52_grad(kmvp_ctx* ctx);
 
+/* Log-sum-exp reduction of the Gaussian and exp(-r) kernels (an extension: no reference method stands behind it -- the
+ * half-iteration of entropic optimal transport (Sinkhorn), log-densities far from the data, the log-partition of a
+ * kernel-attention row).  For targets x (N,D), sources y (M,D) and log-weights c (M,E):
+ *     L[i, e] = log sum_j exp( l(x_i, y_j) + c[j, e] )            (natural logarithm)
+ *   kmvp_gaussian_logsumexp  l = -|x - y|^2
+ *   kmvp_absexp_logsumexp    l = -|x - y|
+ * The signal given to kmvp_set_signal is READ AS c; density estimation (b == NULL) means c = 0, E = 1.  A temperature
+ * eps -- L = log sum_j exp((g_j - C(x_i, y_j)) / eps) -- is the caller's scaling of the points (by 1 / sqrt(eps) for
+ * C = |x - y|^2, by 1 / eps for C = |x - y|) and of c (= g / eps + log weight), as the length scale is for every other
+ * kernel.  Every column has its own shift: columns are independent.  Row normalisation does not exist for this reduction,
+ * and the other kernels have no such entry point.
+ * Conventions
+ *  - c[j, e] = -inf: source j has weight 0 in column e.
+ *  - a row / column without a live term -- M == 0, every c = -inf, or (float32) every squared distance overflowed to
+ *    inf -- is exactly -inf, never NaN.  Pad records and pairs at infinite distance contribute exactly 0.
+ *  - a NaN target coordinate makes that row NaN in every column, and no other row.
+ *  - c = +inf or NaN: the result of that column is unspecified but not finite.
+ *  - the result never depends on exp(largest logit) being representable: the pair loop keeps a per-target, per-column
+ *    integer shift in log2 units and sums 2^(u - shift) <= 1 (csrc/kmvp_lowd_lse.hpp); the shift is unbounded (no
+ *    +-32000-binade range as for exp(<x, y>)).  Logits below -3e38 (float32) / -1e299 (float64) in log2 units count as -inf.
+ *  - bitwise reproducible run to run: fixed summation order, no atomics, every rescale an exact power of two.
+ * Synchronous like the products; the result is read with kmvp_get_result as (N, E) float64 row-major.
+ * float32 and float64 contexts, D <= 8, E <= 4 (lowd_lse_kernel, difference form, on the product's own packed layouts);
+ * KMVP_E_UNSUPPORTED beyond that, for bfloat16 contexts and when "fast_sqdists" asks for a matrix-core form (1 .. 4)
+ * explicitly; kmvp_last_dispatch_note is "".  Honours "segments", "chunk" and "partial_shard" (the shard's own L is
+ * returned: the caller merges shards with logaddexp).  With a communicator attached the ranks merge their
+ * (sum, exponent) pairs: all-reduce(min) of the (N, E) exponents, then all-reduce(sum) -- also on a rank whose source
+ * slice is empty. */
+int kmvp_gaussian_logsumexp(kmvp_ctx* ctx);
+int kmvp_absexp_logsumexp(kmvp_ctx* ctx);
+
 /* BaseProduct.get_result (base.py:107-116): (N,E) float64 row-major. */
 int kmvp_get_result(kmvp_ctx* ctx, double* out, int64_t out_len);
 

@@ -46,6 +46,8 @@ SYMBOLS = [
     ("kmvp_invdist_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_matern32_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_matern52_grad", _c.c_int, [_c.c_void_p]),
+    ("kmvp_gaussian_logsumexp", _c.c_int, [_c.c_void_p]),
+    ("kmvp_absexp_logsumexp", _c.c_int, [_c.c_void_p]),
     ("kmvp_get_result", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("kmvp_gaussian_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
@@ -207,6 +209,17 @@ class Context:
         }.get(kernel)
         if entry is None:
             raise NotImplementedError(f"no gradient for kernel {kernel}")
+        self._check(entry(self._ctx))
+
+    def run_lse(self, kernel):
+        """Log-sum-exp with the signal read as log-weights (include/kmvp.h kmvp_<kernel>_logsumexp); read it with
+        get_result(N, E)."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_logsumexp,
+            "absolute-exponential": self._lib.kmvp_absexp_logsumexp,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no log-sum-exp for kernel {kernel}")
         self._check(entry(self._ctx))
 
     def get_result(self, N, E):

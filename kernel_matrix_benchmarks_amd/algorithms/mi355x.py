@@ -52,6 +52,9 @@ MATERN_KERNELS = ("matern-3/2", "matern-5/2")
 #    (EXPDOT_IDENTITY_SPREAD), NotImplementedError beyond it -- never a silent zero weight.
 SQRT_HALF = 0.7071067811865476
 GRADIENT_MAX_D, GRADIENT_MAX_E = 8, 4  # lowd_grad_kernel's instantiations (csrc/kmvp_internal.hpp LOWD_MAX_D, LOWD_MAX_E)
+# lowd_lse_kernel: the log-sum-exp reduction is built for these kernels, at the gradient's shapes
+LOGSUMEXP_KERNELS = ("gaussian", "absolute-exponential")
+LOGSUMEXP_MAX_D, LOGSUMEXP_MAX_E = 8, 4
 EXPDOT_NATIVE_MAX_D = 64
 EXPDOT_NATIVE_MAX_D_BF16 = 141  # 16 * 9 k-steps - 3 operand columns (kmvp_mfma.hpp MFMA_DOT_AUG)
 # largest spread max_j |y_j|^2/2 - min_j |y_j|^2/2 the identity route accepts: the smallest weight is exp(-spread);
@@ -294,6 +297,37 @@ class MI355XProduct(BaseProduct):
     def get_gradient(self):
         """(N, E, D) float64, C-contiguous: the result of the last query_gradient()."""
         return np.ascontiguousarray(self._ctx.get_result(self.N, self.E * self.D).reshape(self.N, self.E, self.D))
+
+    def query_logsumexp(self):
+        """L[i, e] = log sum_j exp(l(x_i, y_j) + c[j, e]), l = -|x - y|^2 (gaussian) or -|x - y| (absolute-exponential),
+        with the array given to prepare_query(source_signal=c) read as LOG-weights (density estimation: c = 0; c = -inf:
+        weight 0); include/kmvp.h kmvp_<kernel>_logsumexp.  A temperature is the caller's scaling of the points and of
+        c.  The timed part, like query().  Synchronous."""
+        self._check_logsumexp_supported()
+        self._ctx.run_lse(self.kernel)
+        self.res = None
+
+    def _check_logsumexp_supported(self):
+        """What lowd_lse_kernel is not built for, refused before the library is called."""
+        what = None
+        if self.kernel not in LOGSUMEXP_KERNELS:
+            what = f"kernel={self.kernel!r} (gaussian and absolute-exponential only)"
+        elif self.normalize_rows:
+            what = "normalize_rows=True (row normalisation does not exist for this reduction)"
+        elif self._dtype_code == _lib.KMVP_BF16:
+            what = "precision='bfloat16' (float16, float32 and float64 only)"
+        elif self.D > LOGSUMEXP_MAX_D:
+            what = f"D = {self.D} > {LOGSUMEXP_MAX_D}"
+        elif self.E > LOGSUMEXP_MAX_E:
+            what = f"E = {self.E} > {LOGSUMEXP_MAX_E} columns (they are independent: pass them in blocks of {LOGSUMEXP_MAX_E})"
+        elif self.fast_sqdists not in (None, False):
+            what = f"fast_sqdists={self.fast_sqdists!r} (the difference form only: None or False)"
+        if what is not None:
+            raise NotImplementedError(f"MI355XProduct.query_logsumexp doesn't support {what}.")
+
+    def get_logsumexp(self):
+        """(N, E) float64, C-contiguous: the result of the last query_logsumexp()."""
+        return np.ascontiguousarray(self._ctx.get_result(self.N, self.E))
 
     # -- bookkeeping ---------------------------------------------------------------
     def set_query_arguments(self, **kwargs):

@@ -125,6 +125,7 @@ struct kmvp_ctx {
   DevBuf part, sums, out;       // fp64 partials, reduced sums, final (N,E)
   DevBuf xchg;                  // sharded runs: sums in the canonical unpadded layout [column][N] for the all-reduce
   DevBuf kexp, kshift, xchgk;   // exp(<x,y>): exponents per (segment, target) / per target / per target after the all-reduce(min)
+                                // (log-sum-exp: kshift and xchgk per (column, target); xchgk holds the rank's own and the common ones)
   DevBuf kflag;                 // exp(<x,y>): set when a row's exponent reached the shift's clamp (check_shift_range_kernel)
   DevBuf scratch;               // CG vectors / dot products
   DevBuf sdiag;                 // solvers: the effective diagonal ridge + d_i, N doubles (kmvp_set_solver_diagonal)
@@ -196,6 +197,7 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise);
 int measure_clouds(kmvp_ctx* c, int dtype, int64_t M, int64_t N, int D);
 int prepare_points(kmvp_ctx* c, int kernel);  // kmvp_fit: whatever can be built from the points alone
 int run_gradient(kmvp_ctx* c, int kernel);    // kmvp_<kernel>_grad: (N, E D) into c->out, synchronous
+int run_logsumexp(kmvp_ctx* c, int kernel);   // kmvp_<kernel>_logsumexp: (N, E) into c->out, synchronous
 
 // kmvp_solvers.hip
 int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit, double* out_b,

@@ -61,6 +61,17 @@ KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_matern52_f32, float)
 KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_matern32_f64, double)
 KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_matern52_f64, double)
 
+// Log-sum-exp reduction (kmvp_lowd_lse.hpp; kmvp_lowd_lse_inst.hip, one unit per kernel x precision): the Gaussian and
+// exp(-r), D <= LOWD_MAX_D, E <= LOWD_MAX_E, sig SIG_PRODUCT or SIG_DENSITY; hipErrorInvalidValue otherwise.
+// args.part: [segments][2 NC][n_pad] -- NC columns of sums, then NC columns of exponents.
+#define KMVP_DECLARE_LOWD_LSE(NAME, REAL)                                                            \
+  hipError_t NAME(int D, int E, int sig, const LowdArgs<REAL>& args, dim3 grid, hipStream_t stream, \
+                  const char** kernel_name);
+KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_gaussian_f32, float)
+KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_absexp_f32, float)
+KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_gaussian_f64, double)
+KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_absexp_f64, double)
+
 // bf16 MFMA path (kmvp_mfma.hpp): largest shapes instantiated
 constexpr int MFMA_MAX_KS = 9;  // D <= 16*9 - 6 = 138
 constexpr int MFMA_MAX_NT = 4;  // E <= 128
