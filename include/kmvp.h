@@ -202,6 +202,44 @@ int kmvp_matern52_grad(kmvp_ctx* ctx);
 int kmvp_gaussian_logsumexp(kmvp_ctx* ctx);
 int kmvp_absexp_logsumexp(kmvp_ctx* ctx);
 
+/* Gradient of the log-sum-exp with respect to the target points (an extension, the companion of kmvp_<kernel>_logsumexp:
+ * the barycentric map and the displacement field of entropic optimal transport, the gradient of a Sinkhorn loss with
+ * respect to the points, the score grad log p of a kernel density, a mean-shift step).  A softmax-weighted sum:
+ *     G[i, e, :] = grad_{x_i} L[i, e] = sum_j p_ij^e g(x_i, y_j)
+ *     p_ij^e     = exp( l(x_i, y_j) + c[j, e] ) / sum_j' exp( l(x_i, y_j') + c[j', e] )
+ *   kmvp_gaussian_logsumexp_grad  l = -|x - y|^2   g = -2 (x - y)          so G = -2 (x_i - ybar_i^e), ybar the
+ *                                                                          softmax-weighted barycentre of the sources
+ *   kmvp_absexp_logsumexp_grad    l = -|x - y|     g = -(x - y) / r,  r = |x - y|
+ * The signal is READ AS log-weights c exactly as for kmvp_<kernel>_logsumexp (b == NULL: c = 0, E = 1); the targets are
+ * independent variables, also with same_points (as for kmvp_<kernel>_grad).  Synchronous; the result is read with
+ * kmvp_get_result as (N, E * D) float64 row-major, d fastest.  The other kernels have no such entry point, and row
+ * normalisation does not exist for this reduction.
+ * Conventions
+ *  - exp(-r), a coincident pair (s = |x - y|^2 == 0; float32: s not a positive normal number, as for kmvp_absexp_grad):
+ *    the pair contributes 0 to the numerator and keeps its weight in the denominator -- the symmetric subgradient; the
+ *    own pair of same_points drops out of the numerator as it must.
+ *  - c[j, e] = -inf, pad records and pairs whose squared distance overflowed contribute exactly 0 to both sums -- as
+ *    long as the difference x - y itself is finite: a coordinate difference that overflows (float32: |x_d - y_d| > 3.4e38)
+ *    or an infinite coordinate gives 0 * inf, and that row is NaN although other pairs are live.
+ *  - a (row, column) without a live term -- M == 0, every c = -inf, or (float32) every squared distance overflowed -- is
+ *    NaN in all D components: exactly the entries where kmvp_<kernel>_logsumexp is -inf.  Never finite, never inf.
+ *  - a NaN target coordinate makes that row NaN in every column, and touches no other row.
+ *  - c = +inf or NaN in one entry: no entry of that column is finite, for any target; the
+ *    other columns are untouched.
+ *  - the result never depends on exp(largest logit) being representable: numerator and denominator share the
+ *    log-sum-exp's per-target, per-column integer shift (csrc/kmvp_lowd_lse_grad.hpp), which is unbounded.
+ *  - bitwise reproducible run to run: fixed summation order, no atomics, every rescale an exact power of two.
+ * float32 and float64 contexts, D <= 8, E <= 4 (lowd_lse_grad_kernel, difference form, on the product's own packed
+ * layouts: one pack serves product, gradient, log-sum-exp and this); KMVP_E_UNSUPPORTED with a message beyond that, for
+ * bfloat16 contexts and when "fast_sqdists" asks for a matrix-core form (1 .. 4) explicitly; kmvp_last_dispatch_note is
+ * "".  Honours "segments", "chunk" and "partial_shard": a partial shard returns its OWN G_s, and the caller merges shards
+ * as G = sum_s exp(L_s - L) G_s with the shards' L_s from kmvp_<kernel>_logsumexp and L their logaddexp (a shard whose
+ * L_s is -inf has weight 0 and a NaN G_s: leave it out).  With a communicator attached the ranks merge (D + 1 sums,
+ * exponent) tuples: all-reduce(min) of the (N, E) exponents, then ONE all-reduce(sum) of the (D + 1) E N sums -- also on
+ * a rank whose source slice is empty. */
+int kmvp_gaussian_logsumexp_grad(kmvp_ctx* ctx);
+int kmvp_absexp_logsumexp_grad(kmvp_ctx* ctx);
+
 /* BaseProduct.get_result (base.py:107-116): (N,E) float64 row-major. */
 int kmvp_get_result(kmvp_ctx* ctx, double* out, int64_t out_len);
 

@@ -48,6 +48,8 @@ SYMBOLS = [
     ("kmvp_matern52_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_gaussian_logsumexp", _c.c_int, [_c.c_void_p]),
     ("kmvp_absexp_logsumexp", _c.c_int, [_c.c_void_p]),
+    ("kmvp_gaussian_logsumexp_grad", _c.c_int, [_c.c_void_p]),
+    ("kmvp_absexp_logsumexp_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_get_result", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("kmvp_gaussian_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
@@ -220,6 +222,17 @@ class Context:
         }.get(kernel)
         if entry is None:
             raise NotImplementedError(f"no log-sum-exp for kernel {kernel}")
+        self._check(entry(self._ctx))
+
+    def run_lse_grad(self, kernel):
+        """Gradient of the log-sum-exp with respect to the target points (include/kmvp.h kmvp_<kernel>_logsumexp_grad);
+        read it with get_result(N, E * D)."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_logsumexp_grad,
+            "absolute-exponential": self._lib.kmvp_absexp_logsumexp_grad,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no log-sum-exp gradient for kernel {kernel}")
         self._check(entry(self._ctx))
 
     def get_result(self, N, E):

@@ -307,8 +307,8 @@ class MI355XProduct(BaseProduct):
         self._ctx.run_lse(self.kernel)
         self.res = None
 
-    def _check_logsumexp_supported(self):
-        """What lowd_lse_kernel is not built for, refused before the library is called."""
+    def _check_logsumexp_supported(self, method="query_logsumexp"):
+        """What lowd_lse_kernel and lowd_lse_grad_kernel are not built for, refused before the library is called."""
         what = None
         if self.kernel not in LOGSUMEXP_KERNELS:
             what = f"kernel={self.kernel!r} (gaussian and absolute-exponential only)"
@@ -323,11 +323,25 @@ class MI355XProduct(BaseProduct):
         elif self.fast_sqdists not in (None, False):
             what = f"fast_sqdists={self.fast_sqdists!r} (the difference form only: None or False)"
         if what is not None:
-            raise NotImplementedError(f"MI355XProduct.query_logsumexp doesn't support {what}.")
+            raise NotImplementedError(f"MI355XProduct.{method} doesn't support {what}.")
 
     def get_logsumexp(self):
         """(N, E) float64, C-contiguous: the result of the last query_logsumexp()."""
         return np.ascontiguousarray(self._ctx.get_result(self.N, self.E))
+
+    def query_logsumexp_gradient(self):
+        """G[i, e, :] = grad_{x_i} L[i, e] of query_logsumexp()'s L: the softmax-weighted sum of -2 (x_i - y_j) (gaussian:
+        G = -2 (x_i - barycentre)) or -(x_i - y_j) / |x_i - y_j| (absolute-exponential), with the array given to
+        prepare_query(source_signal=c) read as LOG-weights; include/kmvp.h kmvp_<kernel>_logsumexp_grad.  The targets
+        are independent variables, also with same_points.  A (row, column) without a live term is NaN.  The timed part,
+        like query().  Synchronous."""
+        self._check_logsumexp_supported("query_logsumexp_gradient")
+        self._ctx.run_lse_grad(self.kernel)
+        self.res = None
+
+    def get_logsumexp_gradient(self):
+        """(N, E, D) float64, C-contiguous: the result of the last query_logsumexp_gradient()."""
+        return np.ascontiguousarray(self._ctx.get_result(self.N, self.E * self.D).reshape(self.N, self.E, self.D))
 
     # -- bookkeeping ---------------------------------------------------------------
     def set_query_arguments(self, **kwargs):

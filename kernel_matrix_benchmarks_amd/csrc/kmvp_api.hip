@@ -185,6 +185,8 @@ int kmvp_matern32_grad(kmvp_ctx* c) { return run_gradient(c, K_MATERN32); }
 int kmvp_matern52_grad(kmvp_ctx* c) { return run_gradient(c, K_MATERN52); }
 int kmvp_gaussian_logsumexp(kmvp_ctx* c) { return run_logsumexp(c, K_GAUSSIAN); }
 int kmvp_absexp_logsumexp(kmvp_ctx* c) { return run_logsumexp(c, K_ABSEXP); }
+int kmvp_gaussian_logsumexp_grad(kmvp_ctx* c) { return run_logsumexp_grad(c, K_GAUSSIAN); }
+int kmvp_absexp_logsumexp_grad(kmvp_ctx* c) { return run_logsumexp_grad(c, K_ABSEXP); }
 
 int kmvp_get_result(kmvp_ctx* c, double* out, int64_t out_len) {
   if (!c) return KMVP_E_INVALID;

@@ -198,6 +198,7 @@ int measure_clouds(kmvp_ctx* c, int dtype, int64_t M, int64_t N, int D);
 int prepare_points(kmvp_ctx* c, int kernel);  // kmvp_fit: whatever can be built from the points alone
 int run_gradient(kmvp_ctx* c, int kernel);    // kmvp_<kernel>_grad: (N, E D) into c->out, synchronous
 int run_logsumexp(kmvp_ctx* c, int kernel);   // kmvp_<kernel>_logsumexp: (N, E) into c->out, synchronous
+int run_logsumexp_grad(kmvp_ctx* c, int kernel);  // kmvp_<kernel>_logsumexp_grad: (N, E D) into c->out, synchronous
 
 // kmvp_solvers.hip
 int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit, double* out_b,

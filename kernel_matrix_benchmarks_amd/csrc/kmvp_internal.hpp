@@ -72,6 +72,14 @@ KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_absexp_f32, float)
 KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_gaussian_f64, double)
 KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_absexp_f64, double)
 
+// Gradient of the log-sum-exp with respect to the targets (kmvp_lowd_lse_grad.hpp; kmvp_lowd_lse_grad_inst.hip, one unit
+// per kernel x precision): the same shapes.  args.part: [segments][(D + 2) NC][n_pad] -- row k NC + c holds sum k of
+// column c (k = 0: the denominator, k = 1 + d: component d of the numerator), rows (D + 1) NC + c the exponents.
+KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_grad_gaussian_f32, float)
+KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_grad_absexp_f32, float)
+KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_grad_gaussian_f64, double)
+KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_grad_absexp_f64, double)
+
 // bf16 MFMA path (kmvp_mfma.hpp): largest shapes instantiated
 constexpr int MFMA_MAX_KS = 9;  // D <= 16*9 - 6 = 138
 constexpr int MFMA_MAX_NT = 4;  // E <= 128

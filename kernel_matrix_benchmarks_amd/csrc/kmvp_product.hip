@@ -759,6 +759,148 @@ int run_logsumexp_t(kmvp_ctx* c, int kernel, int sig) {
   return finish_lse(c, N, a.n_pad, E);
 }
 
+// ---- gradient of the log-sum-exp with respect to the targets (kmvp_lowd_lse_grad.hpp) ------------------------------------
+// lowd_lse_grad_kernel leaves, per (segment, column c, target), D + 1 sums at the scale 2^-k and ONE exponent k (+inf: no
+// live source), all fp64: part[s][k NC + c][i] for sum k (0: the denominator Z, 1 + d: the numerator V[d]) and
+// part[s][(D + 1) NC + c][i].  With q = (column, target) as ONE index of NC * n_pad (sharded: NC * N) entries the sums are
+// [D + 1][q] and the exponents [q]: lse_reduce_kernel's arithmetic and finish_lse's exchange with D + 1 sums per exponent.
+hipError_t launch_lowd_lse_grad(int kernel, int D, int E, int sig, const LowdArgs<float>& args, dim3 grid, hipStream_t s,
+                                const char** name) {
+  switch (kernel) {
+    case K_GAUSSIAN: return launch_lowd_lse_grad_gaussian_f32(D, E, sig, args, grid, s, name);
+    case K_ABSEXP: return launch_lowd_lse_grad_absexp_f32(D, E, sig, args, grid, s, name);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t launch_lowd_lse_grad(int kernel, int D, int E, int sig, const LowdArgs<double>& args, dim3 grid, hipStream_t s,
+                                const char** name) {
+  switch (kernel) {
+    case K_GAUSSIAN: return launch_lowd_lse_grad_gaussian_f64(D, E, sig, args, grid, s, name);
+    case K_ABSEXP: return launch_lowd_lse_grad_absexp_f64(D, E, sig, args, grid, s, name);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The segment merge: K_q = min_s k[s][q],   sums[t][q] = sum_s part[s][t][q] 2^(K_q - k[s][q]) for the NS = D + 1 sums t
+// that share the exponent (index order; every factor <= 1 and exact).  One thread per (t, q).
+__global__ void lse_grad_reduce_kernel(const double* __restrict__ part, double* __restrict__ sums, double* __restrict__ kmin,
+                                       int64_t count /* NC * n_pad */, int NS, int segments) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)NS * count) return;
+  const int64_t q = idx % count;
+  const int64_t stride = (int64_t)(NS + 1) * count;  // one segment
+  const double* kexp = part + (int64_t)NS * count + q;
+  double K = INFINITY;
+  for (int s = 0; s < segments; ++s) K = fmin(K, kexp[s * stride]);
+  double v = 0.0;
+  for (int s = 0; s < segments; ++s) {
+    const double ks = kexp[s * stride];
+    if (ks < INFINITY) v += ldexp(part[s * stride + idx], (int)fmax(K - ks, -100000.0));
+  }
+  sums[idx] = v;
+  if (idx < count) kmin[q] = K;
+}
+
+// out[i][e D + d] = constant V[d] / Z with Z = sums[0][e][i], V[d] = sums[1 + d][e][i]: the common scale cancels.
+// K = +inf (no live term anywhere): NaN in all D components -- exactly the entries where the log-sum-exp is -inf.
+__global__ void finish_lse_grad_kernel(const double* __restrict__ sums, const double* __restrict__ kshift,
+                                       double* __restrict__ out, int64_t n, int64_t n_pad, int NC, int D, double constant) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n * NC) return;
+  const int64_t i = q / NC, e = q % NC;
+  const int64_t count = (int64_t)NC * n_pad;
+  const bool none = !(kshift[e * n_pad + i] < 1.0e300);
+  const double z = sums[e * n_pad + i];
+  for (int d = 0; d < D; ++d)
+    out[q * D + d] = none ? __builtin_nan("") : constant * sums[(int64_t)(1 + d) * count + e * n_pad + i] / z;
+}
+
+// Tail of the gradient: c->sums [D + 1][NC][n_pad] and c->kshift [NC][n_pad].  Sharded as finish_lse: the canonical
+// unpadded layouts, all-reduce(MIN) of the NC * N exponents, this rank's (D + 1) NC N sums moved to the common scale
+// (rescale_shifted_kernel with (column, target) as its target index), ONE all-reduce(SUM) of them.
+int finish_lse_grad(kmvp_ctx* c, int kernel, int64_t N, int64_t n_pad, int NC, int D) {
+  int rc;
+  const int NS = D + 1;
+  const double* sums = (const double*)c->sums.p;
+  const double* kshift = (const double*)c->kshift.p;
+  if (c->exchanges()) {
+    const int64_t cnt = (int64_t)NC * N;
+    const size_t bytes = (size_t)std::max<int64_t>(cnt, 1) * sizeof(double);
+    if ((rc = ensure(c, c->xchg, NS * bytes))) return rc;
+    if ((rc = ensure(c, c->xchgk, 2 * bytes))) return rc;  // the rank's own exponents, then the common ones
+    double* klocal = (double*)c->xchgk.p;
+    double* kglobal = klocal + std::max<int64_t>(cnt, 1);
+    hipLaunchKernelGGL(unpad_kernel, dim3(blocks_for(NS * cnt)), dim3(256), 0, c->stream, sums, (double*)c->xchg.p, N, n_pad,
+                       (int64_t)NS * NC);
+    hipLaunchKernelGGL(unpad_kernel, dim3(blocks_for(cnt)), dim3(256), 0, c->stream, kshift, klocal, N, n_pad, (int64_t)NC);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(kglobal, klocal, (size_t)cnt * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, mark(c, 3));
+    if ((rc = exchange_f64(c, kglobal, cnt, KMVP_OP_MIN))) return rc;
+    hipLaunchKernelGGL(rescale_shifted_kernel, dim3(blocks_for(NS * cnt)), dim3(256), 0, c->stream, (double*)c->xchg.p,
+                       (const double*)klocal, (const double*)kglobal, cnt, cnt, NS);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = exchange_f64(c, (double*)c->xchg.p, NS * cnt, KMVP_OP_SUM))) return rc;
+    HIP_TRY(c, mark(c, 4));
+    sums = (const double*)c->xchg.p;
+    kshift = kglobal;
+    n_pad = N;
+  }
+  if ((rc = ensure(c, c->out, (size_t)std::max<int64_t>(N, 1) * NC * D * sizeof(double)))) return rc;
+  const double constant = kernel == K_GAUSSIAN ? -2.0 : -1.0;  // g = -2 (x - y), -(x - y) / r
+  hipLaunchKernelGGL(finish_lse_grad_kernel, dim3(blocks_for(std::max<int64_t>(N * NC, 1))), dim3(256), 0, c->stream, sums,
+                     kshift, (double*)c->out.p, N, n_pad, NC, D, constant);
+  HIP_TRY(c, hipGetLastError());
+  return complete(c, N, NC * D);
+}
+
+template <typename real>
+int run_logsumexp_grad_t(kmvp_ctx* c, int kernel, int sig) {
+  const int D = c->D;
+  const int E = sig == SIG_DENSITY ? 1 : c->E;  // = NC, the columns of the log-sum-exp
+  const int NS = D + 1;
+  const int64_t N = c->N, M = c->M;
+  const real* x_raw = (const real*)(c->same_points ? c->y_raw.p : c->x_raw.p);
+  int rc;
+  const int EB = sig == SIG_DENSITY ? 0 : E;
+  const int R = (D + EB + 3) / 4 * 4;
+  LowdArgs<real> a = lowd_geometry<real>(c, 1, R, E * (D + 2));
+
+  HIP_TRY(c, mark(c, 0));
+  // the product's layouts under the product's key (as run_logsumexp_t): whichever runs first on these points and this signal packs
+  const PackKey key = {LAYOUT_LOWD, kernel, 1};
+  if (points_stale(c, key)) {
+    if ((rc = ensure(c, c->xs, (size_t)D * a.n_pad * sizeof(real)))) return rc;
+    hipLaunchKernelGGL((pack_targets_kernel<real>), dim3(blocks_for(a.n_pad)), dim3(256), 0, c->stream, x_raw,
+                       (real*)c->xs.p, N, a.n_pad, D, (real)1);
+  }
+  if (signal_stale(c, key, sig)) {
+    if ((rc = ensure(c, c->rec, (size_t)(a.m_pad + LOWD_BATCH) * R * sizeof(real)))) return rc;
+    hipLaunchKernelGGL((pack_sources_kernel<real>), dim3(blocks_for(a.m_pad + LOWD_BATCH)), dim3(256), 0, c->stream,
+                       (const real*)c->y_raw.p, (const real*)c->b_raw.p, (real*)c->rec.p, M, a.m_pad + LOWD_BATCH, D, EB,
+                       R, (real)1);
+  }
+  HIP_TRY(c, hipGetLastError());
+  record_packed(c, key, sig);
+
+  const int64_t count = (int64_t)E * a.n_pad;
+  if ((rc = ensure(c, c->part, (size_t)a.segments * (NS + 1) * count * sizeof(double)))) return rc;
+  if ((rc = ensure(c, c->sums, (size_t)NS * count * sizeof(double)))) return rc;
+  if ((rc = ensure(c, c->kshift, (size_t)count * sizeof(double)))) return rc;
+  a.xs = (const real*)c->xs.p;
+  a.rec = (const real*)c->rec.p;
+  a.part = (double*)c->part.p;
+  const int64_t nblocks = (int64_t)a.tile_blocks * a.segments;
+  if (nblocks > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
+  HIP_TRY(c, mark(c, 0));
+  HIP_TRY(c, launch_lowd_lse_grad(kernel, D, E, sig, a, dim3((unsigned)nblocks), c->stream, &c->last_kernel_name));
+  HIP_TRY(c, mark(c, 1));
+  hipLaunchKernelGGL(lse_grad_reduce_kernel, dim3(blocks_for(NS * count)), dim3(256), 0, c->stream, (const double*)c->part.p,
+                     (double*)c->sums.p, (double*)c->kshift.p, count, NS, a.segments);
+  HIP_TRY(c, hipGetLastError());
+  return finish_lse_grad(c, kernel, N, a.n_pad, E, D);
+}
+
 // Low D, many signal columns (D <= LOWD_MAX_D, E > LOWD_MAX_E): the specialised pair loop run
 // once per block of LOWD_MAX_E columns (the kernel values are recomputed per block: E = 16 costs
 // four passes of 14 issue slots per pair, against a generic kernel that is 4-5x slower).  The
@@ -2203,6 +2345,62 @@ int run_logsumexp(kmvp_ctx* c, int kernel) {
   }
   const int sig = c->density ? SIG_DENSITY : SIG_PRODUCT;
   return c->dtype == KMVP_F64 ? run_logsumexp_t<double>(c, kernel, sig) : run_logsumexp_t<float>(c, kernel, sig);
+}
+
+// kmvp_<kernel>_logsumexp_grad: G[i, e, :] = grad_{x_i} L[i, e], a softmax-weighted sum of g(x_i, y_j), left as (N, E D) in
+// c->out.  Shards merge as (D + 1 sums, exponent) tuples (finish_lse_grad); an empty slice owes the other ranks the same two
+// collectives with no live term.  Without any live term the softmax does not exist: NaN.
+int run_logsumexp_grad(kmvp_ctx* c, int kernel) {
+  if (!c) return KMVP_E_INVALID;
+  c->note.clear();
+  if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
+  if (!c->have_signal) return fail(c, KMVP_E_INVALID, "kmvp_set_signal has not been called");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->M < c->m_total && !(c->exchanges() && c->world > 1) && !c->opt_partial)
+    return fail(c, KMVP_E_INVALID,
+                "the sources are a shard (M < M_total) but no multi-rank communicator is attached: call kmvp_comm_init, "
+                "or set option partial_shard = 1 to get this shard's own gradient of the log-sum-exp on purpose");
+  if (c->dtype == KMVP_BF16)
+    return fail(c, KMVP_E_UNSUPPORTED, "log-sum-exp gradient: built for float32 and float64 contexts, not for bfloat16");
+  const int E = c->density ? 1 : c->E;
+  const int D = c->D;
+  if (D > LOWD_MAX_D)
+    return fail(c, KMVP_E_UNSUPPORTED, "log-sum-exp gradient: D = " + std::to_string(D) + " is beyond the kernels' D <= " +
+                                           std::to_string(LOWD_MAX_D));
+  if (E > LOWD_MAX_E)
+    return fail(c, KMVP_E_UNSUPPORTED, "log-sum-exp gradient: E = " + std::to_string(E) + " columns are beyond the kernels' E <= " +
+                                           std::to_string(LOWD_MAX_E) + " (columns are independent: run it per block of columns)");
+  if (c->opt_fast >= 1)
+    return fail(c, KMVP_E_UNSUPPORTED, "log-sum-exp gradient: fast_sqdists = " + std::to_string(c->opt_fast) +
+                                           " asks for a matrix-core form that is not built for it (-1 or 0: the difference form)");
+  if (c->N == 0 || c->M == 0) {
+    int rc;
+    const int64_t cnt = (int64_t)E * c->N;
+    c->last_kernel_name = "none";
+    if (c->N > 0 && c->exchanges() && c->world > 1) {
+      if ((rc = ensure(c, c->sums, (size_t)(D + 1) * cnt * sizeof(double)))) return rc;
+      if ((rc = ensure(c, c->kshift, (size_t)cnt * sizeof(double)))) return rc;
+      HIP_TRY(c, mark(c, 0));
+      HIP_TRY(c, hipMemsetAsync(c->sums.p, 0, (size_t)(D + 1) * cnt * sizeof(double), c->stream));
+      hipLaunchKernelGGL(fill_kernel, dim3(blocks_for(cnt)), dim3(256), 0, c->stream, (double*)c->kshift.p, cnt, (double)INFINITY);
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, mark(c, 1));
+      return finish_lse_grad(c, kernel, c->N, c->N, E, D);
+    }
+    if ((rc = ensure(c, c->out, (size_t)std::max<int64_t>(cnt * D, 1) * sizeof(double)))) return rc;
+    if (c->N > 0) {  // no source: no softmax
+      hipLaunchKernelGGL(fill_kernel, dim3(blocks_for(cnt * D)), dim3(256), 0, c->stream, (double*)c->out.p, cnt * D,
+                         (double)NAN);
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    c->out_n = c->N;
+    c->out_e = E * D;
+    c->last_kernel_ms = c->last_total_ms = 0.f;
+    return KMVP_OK;
+  }
+  const int sig = c->density ? SIG_DENSITY : SIG_PRODUCT;
+  return c->dtype == KMVP_F64 ? run_logsumexp_grad_t<double>(c, kernel, sig) : run_logsumexp_grad_t<float>(c, kernel, sig);
 }
 
 }  // namespace kmvp
