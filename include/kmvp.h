@@ -343,6 +343,9 @@ int kmvp_comm_init_host(kmvp_ctx* ctx, kmvp_host_allreduce_fn fn, void* user, in
 /*   "cellmm_shape"     MFMA shape of the float32 cell form: -1 = by size (default: 16x16x32 from 5e5 targets and 1e5 sources
  *                      on with eight target tiles per wave, else 32x32x16), 0 = 32x32x16 (cellmm_kernel), 1 = 16x16x32
  *                      (cellmm16_kernel)
+ *   "cell_fused"       cellmm16_kernel's two lists of target tiles (whole groups per cell; the cells' leftover tiles): -1 =
+ *                      automatic (default) and 1 = ONE launch, the leftover list's workgroups behind the others, where both
+ *                      lists fit one grid; 0 = always two launches.  The sums are the same bit for bit either way
  *   "mfma_variant"     bf16 path, software-pipelined kernel: -1 = by kernel (default: exp(-r) 4, others 0), 0 = plain,
  *                      1 = denominators on the matrix pipe (one more accumulator tile per target tile), 4 = loop rotated by one
  *                      transcendental stage, 5 = both (csrc/kmvp_mfma.hpp, mfma_pipe_kernel VAR) */

@@ -76,9 +76,9 @@ struct CellmmArgs {
   const float* tmeta;        // target tiles [n_slots / 32][4]: c_x, c_y, c_z, cell key (bit 30: empty tile)
   const unsigned char* img;  // source stages [m_stages][CMM_STAGE_BYTES]
   const float* scale;        // [0] sigma_b, [1] 1 / (sigma_b * 2^6)
-  double* part;              // partial sums of THIS launch's tiles [segments][n_slots]
-  int64_t n_slots;           // slots (tiles x 32) of this launch
-  int64_t tile_base;         // first target tile of this launch (0: the list of whole groups; behind it: the leftover tiles)
+  double* part;              // partial sums of THIS list's tiles [segments][n_slots]
+  int64_t n_slots;           // slots (tiles x 32) of this list
+  int64_t tile_base;         // first target tile of this list (0: the list of whole groups; behind it: the leftover tiles)
   int64_t m_stages;
   int64_t seg_stages;
   int segments;
@@ -385,19 +385,19 @@ __device__ __forceinline__ float cellmm16_sources_sum(float v) {
 #define CMM16_NOFOLD 0  // 1: timing only, wrong sums -- the fold and U compiled out, their inputs kept live (what the fold costs)
 #endif
 
+// The pair loop of one workgroup: `bid` is its index within the launch (list) that `a` describes, `lds` the workgroup's two
+// stage buffers.
 template <int TT>
-__global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(TT >= 8 ? 2 : 1)))
-cellmm16_kernel(const CellmmArgs a) {
+__device__ __forceinline__ void cellmm16_body(const CellmmArgs& a, int bid, unsigned char (*lds)[CMM_STAGE_BYTES]) {
   static_assert(!CMM_BF16, "f16 operands only");
   constexpr int SB = CMM_STAGE_BYTES;
   constexpr int PIECES = SB / (16 * BLOCK_THREADS);
   constexpr float LOG2E = 1.4426950408889634f;
   constexpr int HT = 2 * TT;          // half tiles of 16 targets
   constexpr int NG = (HT + 3) / 4;    // fold groups of four half tiles (TT = 1: one, its rows 2 and 3 padded with zeros)
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2][SB];
 
   int tb, seg;
-  block_to_work((int)blockIdx.x, a.segments, a.tile_blocks, tb, seg);
+  block_to_work(bid, a.segments, a.tile_blocks, tb, seg);
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int cc = lane & 15;
@@ -568,7 +568,31 @@ cellmm16_kernel(const CellmmArgs a) {
       a.part[(int64_t)seg * a.n_slots + (tile0 + 2 * g + (kg >> 1) - a.tile_base) * CELL_TILE + 16 * h + cc] = outd[g] * inv;
 }
 
+// One launch for both target lists (TT > CELL_REST_TT).  The leftover list's workgroups are short and few: a launch of
+// their own starts only when the main list's last round of workgroups has drained and then runs latency-bound on a
+// chip it cannot fill.  Here they are the LAST workgroups of the main list's grid (fused_cell_work, kmvp_plan.hpp), so
+// they are dispatched into the slots that last round leaves empty.  Workgroups below `main_grid` run the TT body on the
+// main list `a`; those behind run the CELL_REST_TT body on `rest`, with that list's own segments, stages and region of
+// the partial sums.  The branch is uniform per workgroup, each body keeps its one site of accumulating MFMAs and its own
+// accumulators, and both share the two stage buffers.  main_grid == gridDim.x: the main list alone (`rest` is not read).
+template <int TT>
+__global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(TT >= 8 ? 2 : 1)))
+cellmm16_kernel(const CellmmArgs a, const CellmmArgs rest, const int main_grid) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2][CMM_STAGE_BYTES];
+  if constexpr (TT > CELL_REST_TT) {
+    const FusedCellWork w = fused_cell_work((int64_t)blockIdx.x, (int64_t)main_grid);
+    if (w.list) {
+      cellmm16_body<CELL_REST_TT>(rest, (int)w.local, lds);
+      return;
+    }
+  }
+  cellmm16_body<TT>(a, (int)blockIdx.x, lds);
+}
+
 // shape: 0 = cellmm_kernel (32x32x16), 1 = cellmm16_kernel (16x16x32)
 hipError_t launch_cellmm_gaussian(int TT, int shape, const CellmmArgs& args, dim3 grid, hipStream_t stream, const char** kernel_name);
+// cellmm16_kernel<TT> (TT > CELL_REST_TT) over both lists in one grid of main_grid + rest_grid workgroups
+hipError_t launch_cellmm16_fused(int TT, const CellmmArgs& main, const CellmmArgs& rest, int64_t main_grid, int64_t rest_grid,
+                                 hipStream_t stream, const char** kernel_name);
 
 }  // namespace kmvp

@@ -11,7 +11,7 @@ namespace kmvp {
 
 constexpr int WAVES_PER_BLOCK = 4;
 constexpr int CELL_TILE = 32;                     // points per tile of the float32 cell lists
-constexpr int CELL_REST_TT = 2;                   // tiles per wavefront of the cell kernels' second launch (the REST list)
+constexpr int CELL_REST_TT = 2;                   // tiles per wavefront of the cell kernels' REST list (the cells' leftover tiles)
 constexpr int STAGED_TILE = 32;                   // targets per tile of the staged matrix-core paths (FAST_TILE)
 constexpr int64_t SMALL_PROBLEM_TARGETS = 32768;  // below: one target tile per wave, one stage per segment
 constexpr int SEG_SPLIT_FROM = 16;                // segments from which the reductions split a sum over SEG_SPLIT lanes
@@ -164,8 +164,8 @@ inline TileList cell_tiles(const unsigned* keys, int64_t n, int tile = CELL_TILE
 // tiles used to be padded to a multiple of TT with empty tiles -- at the headline shape (cells of 1000 +- 32 points: 32
 // tiles, or 33-34 for a fifth of them) 5.6 % of all tile pairs were such padding, and the kernel is bound by the matrix
 // pipe.  Now a cell's tiles are split: whole groups of TT go to the MAIN list; a remainder of at most TT/2 tiles goes to
-// the REST list in groups of two (a larger remainder is still padded to a whole group: the second launch with two tiles
-// per wavefront is ~1.6x less efficient per tile).
+// the REST list in groups of two (a larger remainder is still padded to a whole group: workgroups with two tiles
+// per wavefront are ~1.6x less efficient per tile).
 struct CellTiles {
   int64_t main_live, main_empty, rest_live, rest_empty;
 };
@@ -202,10 +202,11 @@ inline TileList cell_tiles_split(const unsigned* keys, int64_t n, int TT, int64_
   return main;
 }
 
-// The two launches of the float32 cell kernels over the lists of cell_tiles_split(): r = 0 the MAIN list (groups of tt
+// The two grids of the float32 cell kernels over the lists of cell_tiles_split(): r = 0 the MAIN list (groups of tt
 // tiles per wavefront), r = 1 the REST list (the cells' leftover tiles, two per wavefront -- few workgroups, latency-bound
-// each, so its own, finer split of the sources).  Each launch has its own segments and its own region
-// [segment][cols][slots] of the partial sums.
+// each, so its own, finer split of the sources).  Each grid has its own segments and its own region
+// [segment][cols][slots] of the partial sums.  cell_kernel and cellmm_kernel run them as two launches, one after the
+// other; cellmm16_kernel as ONE launch, the REST grid behind the MAIN grid (fused_cell_grid below).
 struct CellSplit {
   int64_t m_stages, n_slots;  // source stages; target slots of both lists
   int64_t blocks[2], slots[2], seg_stages[2];
@@ -241,6 +242,44 @@ inline CellSplit cell_split(int64_t N, int64_t m_tiles, int64_t n_main, int64_t 
     s.segments[1] = (int)((s.m_stages + s.seg_stages[1] - 1) / s.seg_stages[1]);
   }
   return s;
+}
+
+// ---- both lists in one launch (cellmm16_kernel) ------------------------------------------------------------------------
+
+// A second launch for the REST list starts only when the MAIN list's last round of workgroups has drained, and the chip
+// stands partly idle through that tail (headline shape: 8000 workgroups in rounds of 512, the last one 320; then 1664 short
+// workgroups, 0.65 ms for 1.3 % of the work).  In one grid the REST list's workgroups come LAST in index order and so are
+// dispatched into the slots the last MAIN round leaves empty.  Nothing else changes: every workgroup does what it did in
+// its own launch, on the same list, segments and region of the partial sums, so the sums are the same bit for bit.
+//
+// workgroup `bid` of the fused grid -> list (0 MAIN, 1 REST) and the workgroup's index in that list's own grid.  With
+// main_grid a multiple of 8 (it is whenever the MAIN list has a multiple of 8 segments), (bid - main_grid) & 7 == bid & 7:
+// the REST workgroups that share an XCD in the fused grid are those that shared one in their own launch, and the XCD
+// affinity of block_to_work() holds for them.
+// (constexpr: the kernel calls the very function the host tests hold to its properties)
+struct FusedCellWork {
+  int list;
+  int64_t local;
+};
+constexpr FusedCellWork fused_cell_work(int64_t bid, int64_t main_grid) {
+  return bid < main_grid ? FusedCellWork{0, bid} : FusedCellWork{1, bid - main_grid};
+}
+
+// The fused grid of a split `s` with tt tiles per wavefront in the MAIN list.  opt_fused: the "cell_fused" option, -1 =
+// automatic and 1 = one launch where it applies, 0 = always two launches.  It applies when there is a REST list (which
+// needs tt > CELL_REST_TT: split_cell_tiles) and the two grids together are a grid a launch takes; a MAIN list that is
+// empty while the REST list is not is a fused grid with main_grid = 0.  fused == false: the two grids are two launches.
+struct FusedCellGrid {
+  bool fused;
+  int64_t main_grid, rest_grid, total;
+};
+inline FusedCellGrid fused_cell_grid(const CellSplit& s, int tt, int opt_fused) {
+  FusedCellGrid g;
+  g.main_grid = s.grid(0);
+  g.rest_grid = s.grid(1);
+  g.total = g.main_grid + g.rest_grid;
+  g.fused = opt_fused != 0 && tt > CELL_REST_TT && s.blocks[1] > 0 && g.total <= MAX_GRID;
+  return g;
 }
 
 }  // namespace kmvp

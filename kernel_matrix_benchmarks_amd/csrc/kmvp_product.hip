@@ -1499,8 +1499,8 @@ double cell_padding(const kmvp_ctx* c) {  // (empty tiles included)
   return std::max(t, s);
 }
 
-// The context's side of a CellSplit (kmvp_plan.hpp): the plan of the two launches of the float32 cell kernels for the
-// current lists, a launch's region of c->part and its share of the kernel's arguments.
+// The context's side of a CellSplit (kmvp_plan.hpp): the plan of the two grids (MAIN and REST list) of the float32 cell
+// kernels for the current lists, a grid's region of c->part and its share of the kernel's arguments.
 // Per path: the stage of its source image, and for the main launch the shortest segment on big problems, the L2 budget
 // of a segment and the target number of workgroups.
 CellSplit cell_plan(const kmvp_ctx* c, int stage_tiles, SegmentRule main) {
@@ -1658,6 +1658,8 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
   // counts is how full the TARGET cells are, not the pair count: one of eight ranks' share of config 2 (1e6 targets x 125 000
   // sources) gains 3 % as well (3.72 -> 3.60 ms, tools/c2_shard.py --shape)
   const int shape = c->opt_cellmm_shape >= 0 ? c->opt_cellmm_shape : ((TT >= 8 && c->N >= 500000 && c->M >= 100000) ? 1 : 0);
+  FusedCellGrid fg = fused_cell_grid(s, TT, c->opt_cell_fused);
+  if (shape != 1) fg.fused = false;  // cellmm_kernel keeps its two launches
   CellmmArgs a;
   a.xd = (const float*)c->xs.p;
   a.tmeta = (const float*)c->cell_tmeta.p;
@@ -1680,12 +1682,21 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
       HIP_TRY(c, hipGetLastError());
       if (NE == 1) HIP_TRY(c, mark(c, 0));
     }
+    // cellmm16_kernel takes both lists in ONE launch, the REST list's workgroups behind the MAIN list's (fused_cell_grid,
+    // kmvp_plan.hpp); otherwise the MAIN list, then the REST list, a launch each
     hipError_t le = hipSuccess;
-    for (int r = 0; r < 2 && le == hipSuccess; ++r)
-      if (s.blocks[r] > 0) {
-        cell_args(c, s, 1, r, a);
-        le = launch_cellmm_gaussian(cell_tt(c, r), shape, a, dim3((unsigned)s.grid(r)), c->stream, &c->last_kernel_name);
-      }
+    if (fg.fused) {
+      CellmmArgs ar = a;
+      cell_args(c, s, 1, 0, a);
+      cell_args(c, s, 1, 1, ar);
+      le = launch_cellmm16_fused(TT, a, ar, fg.main_grid, fg.rest_grid, c->stream, &c->last_kernel_name);
+    } else {
+      for (int r = 0; r < 2 && le == hipSuccess; ++r)
+        if (s.blocks[r] > 0) {
+          cell_args(c, s, 1, r, a);
+          le = launch_cellmm_gaussian(cell_tt(c, r), shape, a, dim3((unsigned)s.grid(r)), c->stream, &c->last_kernel_name);
+        }
+    }
     if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "fast_tiles must be 1, 2, 4 or 8");
     HIP_TRY(c, le);
     if (NE == 1) HIP_TRY(c, mark(c, 1));
