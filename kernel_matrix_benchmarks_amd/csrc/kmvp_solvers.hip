@@ -370,6 +370,13 @@ static int run_bursts(kmvp_ctx* c, const Krylov& k, int maxit, double rtol, int&
   return KMVP_OK;
 }
 
+// wv = the worst of wv and one more column's relative residual v.  A NaN column makes the whole verdict NaN whichever
+// column it is (std::max would drop it, and a plain !(v <= wv) lets the NEXT column overwrite it: with a NaN in one
+// right-hand side of several the solve then ran on the others and was reported as converged).
+static inline void fold_worst(double& wv, double v) {
+  if (!std::isnan(wv) && !(v <= wv)) wv = v;
+}
+
 // Copies the solution out.  The verdict is on the TRUE residual (include/kmvp.h), with 1.5x slack for
 // the rounding between it and the recurrence the iteration stops on; a non-finite residual
 // (non-finite operator or right-hand side) is never a success.
@@ -419,7 +426,7 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
     double wv = 0.0;
     for (int e = 0; e < E; ++e) {
       const double v = anorm2[e] > 0 ? std::sqrt(r2[e] / anorm2[e]) : (anorm2[e] == 0 ? 0.0 : NAN);
-      if (!(v <= wv)) wv = v;  // a NaN column makes the whole verdict NaN (std::max would drop it)
+      fold_worst(wv, v);
     }
     return wv;
   };
@@ -489,6 +496,10 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
 // textbook recurrence on the host would do.
 enum : int { MS_BETA1 = 0, MS_BETA, MS_OLDB, MS_ALFA, MS_DBAR, MS_EPSLN, MS_CS, MS_SN, MS_PHIBAR, MS_DONE, MS_FIELDS };
 // layout: state[MS_FIELDS][E] | T0..T4 [5][3E] | stop | iterations
+// The stop word: 0 while iterating; MS_MET once an iteration met the tolerance -- set by its scalar step, which comes BEFORE
+// its x update, so that iteration's tail still runs (without it the host would read x of the iteration before, with the
+// count and the phibar of this one); MS_STOPPED from the next scalar step on, and then the tail is off too.
+constexpr double MS_MET = 2.0, MS_STOPPED = 1.0;
 __host__ __device__ inline size_t ms_triple(int E, int t) { return (size_t)MS_FIELDS * E + (size_t)t * 3 * E; }
 __host__ __device__ inline size_t ms_stop(int E) { return (size_t)MS_FIELDS * E + 15 * (size_t)E; }
 
@@ -523,14 +534,15 @@ __global__ void minres_diag_lanczos_kernel(double* __restrict__ y, const double*
   y[q] = yv;
 }
 
-// The three vector updates that close a MINRES iteration, in one launch (each was a ~4.5 us kernel of its own in a solve whose
+// The three vector updates that close a MINRES iteration (the stopping one included), in one launch (each was a ~4.5 us
+// kernel of its own in a solve whose
 // iteration is a chain of such kernels): w = T3 . (v, w1, w2);  x = T4 . (x, w);  v = T0 y  (the NEXT iteration's Lanczos vector;
 // v is read for w before it is overwritten, element by element).  Same expressions, same order as vec_lin3_dev_kernel.
 __global__ void minres_tail_kernel(double* __restrict__ w, double* __restrict__ v, const double* __restrict__ w1,
                                    const double* __restrict__ w2, double* __restrict__ x, const double* __restrict__ y,
                                    const double* __restrict__ T3, const double* __restrict__ T4, const double* __restrict__ T0,
                                    const double* __restrict__ stop, int64_t m, int E) {
-  if (*stop != 0.0) return;
+  if (*stop == MS_STOPPED) return;  // MS_MET: the tolerance was met in THIS iteration, whose x is the one to return
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= m * E) return;
   const int e = (int)(q % E);
@@ -553,7 +565,10 @@ __global__ void __launch_bounds__(CG_BLOCKS) minres_scalars_kernel(const double*
 #pragma clang fp contract(off)  // the rotation exactly as written (no fused multiply-adds)
   __shared__ double red[CG_BLOCKS];
   double* stop = st + ms_stop(E);
-  if (*stop != 0.0) return;
+  if (*stop != 0.0) {  // uniform: a thread that reads the word after thread 0 rewrote it sees non-zero as well
+    if (mode == 1 && threadIdx.x == 0 && *stop == MS_MET) *stop = MS_STOPPED;  // the stopping iteration's tail has run
+    return;
+  }
   bool not_met = false;
   double* T0 = st + ms_triple(E, 0);
   double* T1 = st + ms_triple(E, 1);
@@ -611,7 +626,7 @@ __global__ void __launch_bounds__(CG_BLOCKS) minres_scalars_kernel(const double*
   }
   if (mode == 2 && threadIdx.x == 0) {
     stop[1] += 1.0;
-    if (!not_met) *stop = 1.0;
+    if (!not_met) *stop = MS_MET;
   }
 }
 
@@ -662,7 +677,7 @@ int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol
     for (int e = 0; e < E; ++e) {
       if (beta1[e] == 0.0) continue;  // zero right-hand side: x = 0
       const double v = state[(size_t)MS_PHIBAR * E + e] / beta1[e];
-      if (!(v <= wv)) wv = v;  // NaN propagates
+      fold_worst(wv, v);
     }
     return wv;
   };
@@ -711,7 +726,7 @@ int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol
   for (int e = 0; e < E; ++e) {
     if (beta1[e] == 0.0) continue;
     const double v = std::sqrt(dots[e]) / beta1[e];
-    if (!(v <= true_rel)) true_rel = v;  // NaN propagates
+    fold_worst(true_rel, v);
   }
   return solver_end(c, "MINRES", x, k, out_b, it, true_rel, rtol, iters, resid);
 }
