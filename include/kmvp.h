@@ -267,6 +267,46 @@ int kmvp_matern52_cg_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int
 int kmvp_invdist_minres_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int maxit,
                               double* out_b, int* iters, double* resid);
 
+/* Sinkhorn iteration of entropic optimal transport (an extension, the solver on top of kmvp_<kernel>_logsumexp as the
+ * Krylov solvers are on top of the product): the iteration stays on the device, three doubles (stop word, iteration
+ * count, error) cross to the host per iteration.  Targets x (N,D) and sources y (M,D) are the clouds given to kmvp_set_points (x_or_null == NULL:
+ * the same cloud on both sides); kmvp_set_signal is not needed and not consulted.  Marginals a (N) and b (M) come as
+ * log-weights; NULL means uniform (-log N, -log M).  The cost is |x - y|^2 (gaussian) or |x - y| (absexp); the
+ * temperature eps is the caller's scaling of the points, as for kmvp_<kernel>_logsumexp, and the potentials are the
+ * dimensionless u = f / eps, v = g / eps.  With l the kernel's logit:
+ *     T2(u)_j = -log sum_i exp( l(x_i, y_j) + u_i + log_a_i )        T1(v)_i = -log sum_j exp( l(x_i, y_j) + v_j + log_b_j )
+ *   k = 1, 2, ...:   v_k = T2(u_{k-1});   ut = T1(v_k);   err_k = sum_i a_i | exp(u_{k-1,i} - ut_i) - 1 |
+ *                    err_k <= tol: stop with (u_{k-1}, v_k), *iters = k, *err = err_k;   otherwise u_k = ut
+ * from u_0 = the caller's u (N doubles, read on entry: zeros, or a warm start -- an eps-scaling schedule is the caller's
+ * loop over warm starts).  The plan is pi_ij = a_i b_j exp(u_i + v_j + l_ij); err_k is the L1 violation of the row marginal
+ * of the plan of (u_{k-1}, v_k), whose column marginal is exact by construction.
+ *   u (N, in: u_0, out), v (M, out), *iters, *err: ALWAYS the plan the reported error describes -- also when maxit is
+ *   reached: KMVP_E_NOT_CONVERGED with all four written (u_{maxit-1}, v_maxit, maxit, err_maxit), as the solvers.
+ * Conventions
+ *  - the first k with err_k <= tol is the one returned: the stopping test and the commit u_k = ut are made on the device
+ *    in every iteration, nothing depends on when the host looks.
+ *  - log_a_i = -inf (log_b_j = -inf): a point of mass 0.  It contributes 0 to err and to every sum; its own potential
+ *    is still returned (finite: the c-transform of the other side's potential).
+ *  - a potential that becomes non-finite (a row without a live term, a NaN coordinate, a log-weight of +inf or NaN)
+ *    stops the solve: KMVP_E_NOT_CONVERGED with the outputs written.
+ *  - the masses of a and b are not compared here (the caller's business: the Python wrapper checks them).
+ *  - potentials and log-weights are float64 on the device for every working precision; they are rounded to the
+ *    context's precision only in the signal slot of the source records (potential + log-weight), which is all the pair
+ *    loop reads of them.
+ *  - bitwise reproducible run to run (u, v, iters, err): fixed summation order, no atomics.
+ * Per iteration: lowd_lse_kernel twice (kmvp_last_kernel_name), each with its segment merge and a finish kernel that
+ * forms the new potential and rewrites the signal slot of the OTHER direction's records; both packed layouts (target
+ * image of x with records of y, target image of y with records of x) are built once per kmvp_set_points in buffers of
+ * the solver's own, so a product, gradient or log-sum-exp on the same context before or after a solve is untouched.
+ * kmvp_last_kernel_ms and kmvp_last_total_ms both cover the whole solve.  Honours "segments" and "chunk".
+ * float32 and float64 contexts, D <= 8, one column of weights.  KMVP_E_UNSUPPORTED with a message for bfloat16 contexts,
+ * D > 8, an explicit "fast_sqdists" of 1 .. 4, an attached communicator and a source slice (M < M_total): sharded
+ * Sinkhorn is not built.  KMVP_E_INVALID for call-order errors, an empty cloud, tol < 0, maxit < 1 or a NULL output. */
+int kmvp_gaussian_sinkhorn(kmvp_ctx* ctx, const double* log_a_or_null, const double* log_b_or_null, double tol, int maxit,
+                           double* u, double* v, int* iters, double* err);
+int kmvp_absexp_sinkhorn(kmvp_ctx* ctx, const double* log_a_or_null, const double* log_b_or_null, double tol, int maxit,
+                         double* u, double* v, int* iters, double* err);
+
 /* Regularised systems (an extension: no reference method stands behind it -- the reference's lstsq solves the bare
  * K b = a; this is the `alpha` / nugget / noise term of kernel ridge regression, Kriging and Gaussian processes).
  * A = K + ridge I + diag(d) for the solvers that follow on this ctx.  d: n doubles (n = number of points of the

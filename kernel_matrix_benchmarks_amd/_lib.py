@@ -61,6 +61,10 @@ SYMBOLS = [
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_invdist_minres_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                              _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
+    ("kmvp_gaussian_sinkhorn", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p,
+                                          _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
+    ("kmvp_absexp_sinkhorn", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p,
+                                        _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_set_solver_diagonal", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_double]),
     ("kmvp_comm_get_unique_id", _c.c_int, [_c.c_void_p]),
     ("kmvp_comm_init", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int]),
@@ -262,6 +266,38 @@ class Context:
         if rc not in (0, 6):
             self._check(rc)
         return out, iters.value, resid.value, rc == 0
+
+    def sinkhorn(self, kernel, log_a, log_b, tol, maxit, u0=None):
+        """Sinkhorn iteration on the clouds of set_points (include/kmvp.h kmvp_<kernel>_sinkhorn): log_a (N) / log_b (M)
+        float64 log-weights or None (uniform), u0 (N) the starting potential or None (zeros).  Returns
+        (u, v, iterations, marginal error, converged); raises on every status but OK and NOT_CONVERGED."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_sinkhorn,
+            "absolute-exponential": self._lib.kmvp_absexp_sinkhorn,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no Sinkhorn iteration for kernel {kernel}")
+
+        def vector(a, n, what):
+            # the library reads n doubles from the pointer: a shorter array must never reach it
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (n,):
+                raise ValueError(f"{what} has shape {a.shape}, expected ({n},)")
+            return a
+
+        N, M = getattr(self, "N", 0), getattr(self, "M", 0)
+        log_a, log_b = vector(log_a, N, "log_a"), vector(log_b, M, "log_b")
+        u = np.zeros(N, dtype=np.float64) if u0 is None else vector(u0, N, "u0").copy()
+        v = np.zeros(M, dtype=np.float64)
+        iters = ctypes.c_int(0)
+        err = ctypes.c_double(0.0)
+        rc = entry(self._ctx, None if log_a is None else log_a.ctypes.data, None if log_b is None else log_b.ctypes.data,
+                   float(tol), int(maxit), u.ctypes.data, v.ctypes.data, ctypes.byref(iters), ctypes.byref(err))
+        if rc not in (0, 6):
+            self._check(rc)
+        return u, v, iters.value, err.value, rc == 0
 
     def set_solver_diagonal(self, d_or_none, ridge=0.0):
         """A = K + ridge I + diag(d) for the solves that follow (include/kmvp.h kmvp_set_solver_diagonal); d: one float64

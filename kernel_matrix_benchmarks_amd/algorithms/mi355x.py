@@ -1,4 +1,5 @@
-"""MI355X plugins: the on-the-fly kernel product and the CG solver built on it.
+"""MI355X plugins: the on-the-fly kernel product and the CG solver built on it (and, beyond the reference's plugin
+roles, ``MI355XSinkhorn``: entropic optimal transport on the product's log-sum-exp reduction).
 
 Drop-in counterparts of the reference's ``BruteForceProductBLAS``
 (bruteforce.py:61-153) and ``BruteForceSolverLAPACK`` (bruteforce.py:156-207):
@@ -667,6 +668,160 @@ class MI355XSolver(BaseSolver):
         if getattr(self, "_ctx32", None) is not None:
             self._ctx32.close()
             self._ctx32 = None
+
+    def __del__(self):
+        try:
+            self.done()
+        except Exception:
+            pass
+
+
+SINKHORN_KERNELS = ("gaussian", "absolute-exponential")  # the log-sum-exp's kernels: cost |x - y|^2 and |x - y|
+SINKHORN_MASS_RTOL = 1e-6
+
+
+class MI355XSinkhorn:
+    """Entropic optimal transport between two weighted clouds on one MI355X: the Sinkhorn iteration in the log domain,
+    resident on the device (include/kmvp.h kmvp_<kernel>_sinkhorn; the pair loop is lowd_lse_kernel).  An extension:
+    the reference's plugin API has no such role, so the class is not registered in algos.yaml.
+
+        minimise  <pi, C> + eps KL(pi | a x b)   over plans pi with marginals a (targets x) and b (sources y)
+        C = |x - y|^2 (kernel="gaussian")  or  |x - y| (kernel="absolute-exponential")
+
+    Same call order as MI355XSolver: prepare_data, fit, query, then get_potentials / dual_value / barycentric_map /
+    get_additional, done.  The temperature is applied by scaling the points (by 1 / sqrt(eps) or 1 / eps); the library
+    works on the dimensionless potentials u = f / eps, v = g / eps.  ``options``: device, segments, chunk, fast_sqdists
+    (only None / False run: the difference form)."""
+
+    def __init__(self, *, kernel, dimension, eps, precision=np.float32, tol=1e-6, maxit=1000, device=0, segments=0,
+                 chunk=0, fast_sqdists=None):
+        if kernel not in SINKHORN_KERNELS:
+            raise NotImplementedError(f"MI355XSinkhorn doesn't support kernel {kernel}.")
+        if not (np.isfinite(eps) and eps > 0):
+            raise ValueError(f"eps must be a positive number, not {eps!r}")
+        self.kernel, self.dimension, self.eps = kernel, int(dimension), float(eps)
+        self.precision = precision
+        self._dtype_code, self._host_dtype = _lib.dtype_code(precision)
+        self.tol, self.maxit = float(tol), int(maxit)
+        self.device = device
+        self.fast_sqdists = fast_sqdists
+        self._options = dict(segments=segments, chunk=chunk)
+        # the points are multiplied by this before they are cast to the working precision
+        self.scale = 1.0 / np.sqrt(self.eps) if kernel == "gaussian" else 1.0 / self.eps
+        self._ctx = None
+        self.u = self.v = None
+        self.iterations, self.marginal_error, self.converged = 0, float("nan"), False
+        self.name = f"MI355XSinkhorn({_precision_name(precision)}, eps={self.eps:g})"
+
+    @staticmethod
+    def _log_weights(w, n, what):
+        if w is None:
+            return np.full(n, 1.0 / n), None  # (the library's uniform default: log_w = NULL)
+        w = np.asarray(w, dtype=np.float64).reshape(-1)
+        if w.shape != (n,):
+            raise ValueError(f"{what} has {w.size} entries for {n} points")
+        if not np.all(w >= 0):  # (NaN fails this as well)
+            raise ValueError(f"{what} must be non-negative")
+        with np.errstate(divide="ignore"):
+            return w, np.log(w)  # a weight of 0 is a point of mass 0: log weight -inf
+
+    # -- untimed -------------------------------------------------------------------
+    def prepare_data(self, *, source_points, target_points, same_points=False, source_weights=None, target_weights=None):
+        self.same_points = bool(same_points)
+        if source_points is None or (target_points is None and not self.same_points):
+            raise ValueError("source_points and target_points are both needed (target_points may be None only with "
+                             "same_points=True)")
+        y = np.ascontiguousarray(np.asarray(source_points, dtype=np.float64) * self.scale, dtype=self._host_dtype)
+        if y.ndim != 2 or y.shape[1] != self.dimension:
+            raise ValueError(f"source_points has shape {y.shape}, expected (M, {self.dimension})")
+        self.M, self.D = y.shape
+        if self.same_points:
+            x = None
+            self.N = self.M
+        else:
+            x = np.ascontiguousarray(np.asarray(target_points, dtype=np.float64) * self.scale, dtype=self._host_dtype)
+            if x.ndim != 2 or x.shape[1] != self.D:
+                raise ValueError(f"target_points has shape {x.shape}, expected (N, {self.D})")
+            self.N = x.shape[0]
+        self.b, self._log_b = self._log_weights(source_weights, self.M, "source_weights")
+        self.a, self._log_a = self._log_weights(target_weights, self.N, "target_weights")
+        ma, mb = float(np.sum(self.a)), float(np.sum(self.b))
+        if not abs(ma - mb) <= SINKHORN_MASS_RTOL * max(ma, mb):
+            raise ValueError(f"the total masses differ: target_weights sum to {ma!r}, source_weights to {mb!r}")
+        self._y, self._x = y, (y if x is None else x)  # the scaled points as the device holds them
+        if self._ctx is None:
+            self._ctx = _lib.Context(self.device)
+            for key, value in self._options.items():
+                if value:
+                    self._ctx.set_option(key, value)
+            if self.fast_sqdists is not None:
+                code = {"centred": 2, "cells": 3, "cells-valu": 4}.get(self.fast_sqdists, int(bool(self.fast_sqdists)))
+                self._ctx.set_option("fast_sqdists", code)
+        self._ctx.set_points(y, x, self._dtype_code)
+        self.u = self.v = None
+
+    # -- timed ---------------------------------------------------------------------
+    def fit(self):
+        """Nothing to build ahead of the first solve: it packs both directions' layouts itself, once per prepare_data."""
+
+    def query(self, warm_start=None):
+        """Runs the iteration from f = warm_start (N values in the caller's units, e.g. get_potentials()[0] of a solve
+        at a larger eps) or from zero.  Synchronous.  Not converged (maxit reached, or a non-finite potential) is a
+        result, reported by get_additional()["converged"]; every other failure raises."""
+        u0 = None if warm_start is None else np.asarray(warm_start, dtype=np.float64).reshape(-1) / self.eps
+        self.u, self.v, self.iterations, self.marginal_error, self.converged = self._ctx.sinkhorn(
+            self.kernel, self._log_a, self._log_b, self.tol, self.maxit, u0)
+
+    def set_query_arguments(self, tol=None, maxit=None):
+        if tol is not None:
+            self.tol = float(tol)
+        if maxit is not None:
+            self.maxit = int(maxit)
+
+    # -- results -------------------------------------------------------------------
+    def _need_solution(self, method):
+        if self.u is None:
+            raise RuntimeError(f"MI355XSinkhorn.{method}: no solution yet -- call query() after prepare_data() first")
+
+    def get_potentials(self):
+        """(f, g) = eps (u, v): f on the N targets, g on the M sources; the plan is
+        pi_ij = a_i b_j exp((f_i + g_j - C_ij) / eps)."""
+        self._need_solution("get_potentials")
+        return self.eps * self.u, self.eps * self.v
+
+    def dual_value(self):
+        """<a, f> + <b, g>: the dual objective at the returned potentials (the plan's mass term cancels when its
+        marginals are met)."""
+        f, g = self.get_potentials()
+        return float(np.dot(self.a, f) + np.dot(self.b, g))
+
+    def barycentric_map(self):
+        """(N, D): sum_j pi_ij y_j / sum_j pi_ij in the caller's coordinates -- where the plan sends x_i on average.
+        Gaussian only: G = grad_x L = -2 (x - barycentre) of the log-sum-exp with the signal v + log b
+        (kmvp_gaussian_logsumexp_grad on the same context)."""
+        if self.kernel != "gaussian":
+            raise NotImplementedError("MI355XSinkhorn.barycentric_map is built for kernel='gaussian' only.")
+        self._need_solution("barycentric_map")
+        log_b = self._log_b if self._log_b is not None else np.full(self.M, -np.log(self.M))
+        self._ctx.set_signal(np.ascontiguousarray((self.v + log_b).reshape(-1, 1), dtype=self._host_dtype))
+        self._ctx.run_lse_grad("gaussian")
+        grad = self._ctx.get_result(self.N, self.D)
+        return np.ascontiguousarray((np.asarray(self._x, dtype=np.float64) + 0.5 * grad) / self.scale)
+
+    def get_memory_usage(self):
+        return 0.0 if self._ctx is None else self._ctx.device_bytes / 1024
+
+    def get_additional(self):
+        extra = {"iterations": self.iterations, "marginal_error": self.marginal_error, "converged": bool(self.converged)}
+        if self._ctx is not None:
+            extra.update(device_kernel_ms=self._ctx.last_kernel_ms, device_total_ms=self._ctx.last_total_ms,
+                         device_kernel=self._ctx.last_kernel_name, device_bytes=self._ctx.device_bytes)
+        return extra
+
+    def done(self):
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None
 
     def __del__(self):
         try:

@@ -90,6 +90,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
                     &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     release(*b);
   for (int i = 0; i < 5; ++i)
@@ -221,6 +222,15 @@ int kmvp_matern52_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int m
 int kmvp_invdist_minres_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
                               int* iters, double* resid) {
   return minres_solve(c, K_INVDIST, a, E, rtol, maxit, out_b, iters, resid);
+}
+
+int kmvp_gaussian_sinkhorn(kmvp_ctx* c, const double* log_a, const double* log_b, double tol, int maxit, double* u, double* v,
+                           int* iters, double* err) {
+  return sinkhorn_solve(c, K_GAUSSIAN, log_a, log_b, tol, maxit, u, v, iters, err);
+}
+int kmvp_absexp_sinkhorn(kmvp_ctx* c, const double* log_a, const double* log_b, double tol, int maxit, double* u, double* v,
+                         int* iters, double* err) {
+  return sinkhorn_solve(c, K_ABSEXP, log_a, log_b, tol, maxit, u, v, iters, err);
 }
 
 int kmvp_set_solver_diagonal(kmvp_ctx* c, const double* d, int64_t n, double ridge) {
@@ -369,6 +379,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
                           &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     t += b->cap;
   return (int64_t)t;

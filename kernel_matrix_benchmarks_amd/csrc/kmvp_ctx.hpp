@@ -3,6 +3,7 @@
 //   kmvp_api.hip      the extern "C" surface of include/kmvp.h
 //   kmvp_product.hip  layouts, launch geometry, the pair-loop paths and the policy that picks one
 //   kmvp_solvers.hip  conjugate gradients and MINRES on the product
+//   kmvp_sinkhorn.hip the Sinkhorn iteration of entropic optimal transport on the log-sum-exp
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -129,6 +130,10 @@ struct kmvp_ctx {
   DevBuf kflag;                 // exp(<x,y>): set when a row's exponent reached the shift's clamp (check_shift_range_kernel)
   DevBuf scratch;               // CG vectors / dot products
   DevBuf sdiag;                 // solvers: the effective diagonal ridge + d_i, N doubles (kmvp_set_solver_diagonal)
+  // Sinkhorn (kmvp_sinkhorn.hip): layouts of its own for both directions -- target image of x with records of y, target
+  // image of y with records of x (the record's signal slot carries potential + log-weight) -- and the fp64 state
+  DevBuf sk_xs_x, sk_rec_y, sk_xs_y, sk_rec_x, sk_state;
+  uint64_t sk_points_ver = 0;   // points version the four layouts were packed from (0: none)
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
   int packed_layout = -1;  // LAYOUT_* of the path that owns xs / rec right now
@@ -206,5 +211,9 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
              int* iters, double* resid);
 int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit,
                  double* out_b, int* iters, double* resid);
+
+// kmvp_sinkhorn.hip: kmvp_<kernel>_sinkhorn, the device-resident Sinkhorn iteration on lowd_lse_kernel
+int sinkhorn_solve(kmvp_ctx* c, int kernel, const double* log_a, const double* log_b, double tol, int maxit, double* u,
+                   double* v, int* iters, double* err);
 
 }  // namespace kmvp

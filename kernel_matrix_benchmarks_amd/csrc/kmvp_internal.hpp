@@ -72,6 +72,74 @@ KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_absexp_f32, float)
 KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_gaussian_f64, double)
 KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_absexp_f64, double)
 
+// What the log-sum-exp (kmvp_product.hip run_logsumexp_t) and the Sinkhorn iteration on top of it (kmvp_sinkhorn.hip) share
+// on the host side: the launch switch, the launch geometry and the segment merge.
+inline hipError_t launch_lowd_lse(int kernel, int D, int E, int sig, const LowdArgs<float>& args, dim3 grid, hipStream_t s,
+                                  const char** name) {
+  switch (kernel) {
+    case K_GAUSSIAN: return launch_lowd_lse_gaussian_f32(D, E, sig, args, grid, s, name);
+    case K_ABSEXP: return launch_lowd_lse_absexp_f32(D, E, sig, args, grid, s, name);
+    default: return hipErrorInvalidValue;
+  }
+}
+inline hipError_t launch_lowd_lse(int kernel, int D, int E, int sig, const LowdArgs<double>& args, dim3 grid, hipStream_t s,
+                                  const char** name) {
+  switch (kernel) {
+    case K_GAUSSIAN: return launch_lowd_lse_gaussian_f64(D, E, sig, args, grid, s, name);
+    case K_ABSEXP: return launch_lowd_lse_absexp_f64(D, E, sig, args, grid, s, name);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// Geometry of the specialised difference-form kernels (kmvp_lowd.hpp) for N targets and M sources: tiles of 64 T targets
+// per wave, source records of R reals in batches, segments of whole batches, `cols` columns of partial sums per segment.
+// Everything but the buffers.  opt_segments / opt_chunk: the context's "segments" and "chunk" options.
+constexpr int64_t LOWD_BATCH = 8;  // two ping-pong batches of 4 records
+template <typename real>
+LowdArgs<real> lowd_geometry(int64_t N, int64_t M, int opt_segments, int opt_chunk, int64_t j_offset, int64_t m_total, int T,
+                             int R, int cols) {
+  const int64_t tile = 64 * (int64_t)T * WAVES_PER_BLOCK;
+  LowdArgs<real> a;
+  a.xs = nullptr;
+  a.rec = nullptr;
+  a.part = nullptr;
+  a.n = N;
+  a.n_pad = round_up(N > 1 ? N : 1, tile);
+  a.tile_blocks = (int)(a.n_pad / tile);
+  a.m_pad = round_up(M > 1 ? M : 1, LOWD_BATCH);
+  // few targets: short segments, so that the launch still covers the chip (n = 2000, fp64: 121 -> 9 us)
+  const bool small = small_problem(N);
+  SegmentRule rule((int64_t)R * sizeof(real), cols);
+  rule.min_seg = small ? 32 : 1024;
+  rule.small = small;
+  const int segments = choose_segments(opt_segments, a.n_pad / tile, a.m_pad, a.n_pad, rule);
+  a.seg_len = round_up((a.m_pad + segments - 1) / segments, LOWD_BATCH);
+  a.segments = (int)((a.m_pad + a.seg_len - 1) / a.seg_len);
+  a.chunk = (int)round_up(opt_chunk > 8 ? opt_chunk : 8, LOWD_BATCH);
+  a.j_offset = j_offset;
+  a.m_total = m_total;
+  return a;
+}
+
+// The segment merge of lowd_lse_kernel's (sum, exponent) pairs, reduce_shifted_kernel's arithmetic with fp64 exponents per
+// (column, target) q < count:
+//   K_q = min_s k[s][q],   sums[q] = sum_s part[s][q] 2^(K_q - k[s][q])   (index order; every factor <= 1 and exact)
+// (static: a kernel cannot be inline; each of the two units that launch it carries its own copy, the others none)
+static __global__ void lse_reduce_kernel(const double* __restrict__ part, double* __restrict__ sums, double* __restrict__ kmin,
+                                         int64_t count /* NC * n_pad */, int segments) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= count) return;
+  double K = INFINITY;
+  for (int s = 0; s < segments; ++s) K = fmin(K, part[((int64_t)2 * s + 1) * count + q]);
+  double v = 0.0;
+  for (int s = 0; s < segments; ++s) {
+    const double ks = part[((int64_t)2 * s + 1) * count + q];
+    if (ks < INFINITY) v += ldexp(part[(int64_t)2 * s * count + q], (int)fmax(K - ks, -100000.0));
+  }
+  sums[q] = v;
+  kmin[q] = K;
+}
+
 // Gradient of the log-sum-exp with respect to the targets (kmvp_lowd_lse_grad.hpp; kmvp_lowd_lse_grad_inst.hip, one unit
 // per kernel x precision): the same shapes.  args.part: [segments][(D + 2) NC][n_pad] -- row k NC + c holds sum k of
 // column c (k = 0: the denominator, k = 1 + d: component d of the numerator), rows (D + 1) NC + c the exponents.

@@ -424,29 +424,10 @@ int reduce_and_finish(kmvp_ctx* c, int segments, int NE, int64_t N, int64_t n_pa
   return complete(c, N, E);
 }
 
-// Geometry of the specialised difference-form kernels (kmvp_lowd.hpp): tiles of 64 T targets per wave, source records of
-// R reals in batches, segments of whole batches, `cols` columns of partial sums per segment.  Everything but the buffers.
-constexpr int64_t LOWD_BATCH = 8;  // two ping-pong batches of 4 records
+// Geometry of the specialised difference-form kernels for the context's own clouds and options (kmvp_internal.hpp).
 template <typename real>
 LowdArgs<real> lowd_geometry(const kmvp_ctx* c, int T, int R, int cols) {
-  const int64_t tile = 64 * (int64_t)T * WAVES_PER_BLOCK;
-  LowdArgs<real> a;
-  a.n = c->N;
-  a.n_pad = round_up(std::max<int64_t>(c->N, 1), tile);
-  a.tile_blocks = (int)(a.n_pad / tile);
-  a.m_pad = round_up(std::max<int64_t>(c->M, 1), LOWD_BATCH);
-  // few targets: short segments, so that the launch still covers the chip (n = 2000, fp64: 121 -> 9 us)
-  const bool small = small_problem(c->N);
-  SegmentRule rule((int64_t)R * sizeof(real), cols);
-  rule.min_seg = small ? 32 : 1024;
-  rule.small = small;
-  const int segments = choose_segments(c->opt_segments, a.n_pad / tile, a.m_pad, a.n_pad, rule);
-  a.seg_len = round_up((a.m_pad + segments - 1) / segments, LOWD_BATCH);
-  a.segments = (int)((a.m_pad + a.seg_len - 1) / a.seg_len);
-  a.chunk = (int)round_up(std::max(c->opt_chunk, 8), LOWD_BATCH);
-  a.j_offset = c->j_offset;
-  a.m_total = c->m_total;
-  return a;
+  return kmvp::lowd_geometry<real>(c->N, c->M, c->opt_segments, c->opt_chunk, c->j_offset, c->m_total, T, R, cols);
 }
 
 // The whole product: everything query() times.  `sig` as in kmvp_lowd.hpp.
@@ -633,39 +614,7 @@ int run_gradient_t(kmvp_ctx* c, int kernel, int sig) {
 // lowd_lse_kernel leaves, per (segment, column, target), a sum at the scale 2^-k and its exponent k (+inf: no live source),
 // both fp64: part[s][c][i] and part[s][NC + c][i].  Every column has its own exponents, so the tail below treats
 // (column, target) as ONE index of NC * n_pad (sharded: NC * N) entries and is then exp(<x,y>)'s, step by step.
-hipError_t launch_lowd_lse(int kernel, int D, int E, int sig, const LowdArgs<float>& args, dim3 grid, hipStream_t s,
-                           const char** name) {
-  switch (kernel) {
-    case K_GAUSSIAN: return launch_lowd_lse_gaussian_f32(D, E, sig, args, grid, s, name);
-    case K_ABSEXP: return launch_lowd_lse_absexp_f32(D, E, sig, args, grid, s, name);
-    default: return hipErrorInvalidValue;
-  }
-}
-hipError_t launch_lowd_lse(int kernel, int D, int E, int sig, const LowdArgs<double>& args, dim3 grid, hipStream_t s,
-                           const char** name) {
-  switch (kernel) {
-    case K_GAUSSIAN: return launch_lowd_lse_gaussian_f64(D, E, sig, args, grid, s, name);
-    case K_ABSEXP: return launch_lowd_lse_absexp_f64(D, E, sig, args, grid, s, name);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-// The segment merge, reduce_shifted_kernel's arithmetic with fp64 exponents per (column, target) q < count:
-//   K_q = min_s k[s][q],   sums[q] = sum_s part[s][q] 2^(K_q - k[s][q])   (index order; every factor <= 1 and exact)
-__global__ void lse_reduce_kernel(const double* __restrict__ part, double* __restrict__ sums, double* __restrict__ kmin,
-                                  int64_t count /* NC * n_pad */, int segments) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= count) return;
-  double K = INFINITY;
-  for (int s = 0; s < segments; ++s) K = fmin(K, part[((int64_t)2 * s + 1) * count + q]);
-  double v = 0.0;
-  for (int s = 0; s < segments; ++s) {
-    const double ks = part[((int64_t)2 * s + 1) * count + q];
-    if (ks < INFINITY) v += ldexp(part[(int64_t)2 * s * count + q], (int)fmax(K - ks, -100000.0));
-  }
-  sums[q] = v;
-  kmin[q] = K;
-}
+// The launch switch and the segment merge (lse_reduce_kernel) are in kmvp_internal.hpp: the Sinkhorn iteration shares them.
 
 // out[i * NC + e] = (log2(sums[e][i]) - K[e][i]) ln 2;  K = +inf (no live term anywhere): exactly -inf
 __global__ void finish_lse_kernel(const double* __restrict__ sums, const double* __restrict__ kshift, double* __restrict__ out,
