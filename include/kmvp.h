@@ -386,6 +386,10 @@ int kmvp_comm_init_host(kmvp_ctx* ctx, kmvp_host_allreduce_fn fn, void* user, in
  *   "cell_fused"       cellmm16_kernel's two lists of target tiles (whole groups per cell; the cells' leftover tiles): -1 =
  *                      automatic (default) and 1 = ONE launch, the leftover list's workgroups behind the others, where both
  *                      lists fit one grid; 0 = always two launches.  The sums are the same bit for bit either way
+ *   "cell_shared_build" cellmm16_kernel's workgroups whose four wavefronts own target tiles of ONE cell: -1 = automatic
+ *                      (default) and 1 = such a workgroup builds every source operand once and shares it through LDS,
+ *                      wherever the kernel holds that body (eight target tiles per wavefront); 0 = never, every wavefront
+ *                      builds its own.  The sums are the same bit for bit either way
  *   "mfma_variant"     bf16 path, software-pipelined kernel: -1 = by kernel (default: exp(-r) 4, others 0), 0 = plain,
  *                      1 = denominators on the matrix pipe (one more accumulator tile per target tile), 4 = loop rotated by one
  *                      transcendental stage, 5 = both (csrc/kmvp_mfma.hpp, mfma_pipe_kernel VAR) */

@@ -353,6 +353,9 @@ int kmvp_set_option(kmvp_ctx* c, const char* key, int64_t value) {
   } else if (k == "cell_fused") {
     if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "cell_fused must be -1 (automatic), 0 (two launches) or 1 (one launch where it applies)");
     c->opt_cell_fused = (int)value;
+  } else if (k == "cell_shared_build") {
+    if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "cell_shared_build must be -1 (automatic), 0 (never) or 1 (wherever a workgroup is one-cell)");
+    c->opt_cell_shared_build = (int)value;
   } else if (k == "mfma_variant") {
     if (value != -1 && value != 0 && value != 1 && value != 4 && value != 5)
       return fail(c, KMVP_E_INVALID, "mfma_variant must be -1 (by kernel), 0, 1, 4 or 5");

@@ -43,6 +43,9 @@
 // the operand build and the per-tile bookkeeping removed from this kernel's loop (timing-only experiment)
 // the same launch takes 25.4 ms against 26.0-26.9 ms complete: the VALU work is hidden, what remains is
 // the MFMA stream itself (1.30 PFLOP/s, 0.52 of the nominal 2.5, 0.83 of what random data sustains).
+// That was measured on cellmm_kernel (32x32x16) and holds for it alone.  On the 16x16x32 shape below the operand
+// build is NOT hidden: with three of four builds compiled out (CMM16_BUILD_PROBE) cellmm16_kernel<8> runs 5-6 %
+// shorter, which is why its one-cell workgroups build each operand once (cellmm16_body<TT, true>).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -83,6 +86,7 @@ struct CellmmArgs {
   int64_t seg_stages;
   int segments;
   int tile_blocks;
+  int shared_build;          // cellmm16_kernel: != 0 = one-cell workgroups of the main list build each source operand once (cellmm16_body)
 };
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -381,20 +385,97 @@ __device__ __forceinline__ float cellmm16_sources_sum(float v) {
          __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 47));
 }
 
+// A operand of one source row for slot half h, and the row's weight.  `ef` = (f_x, f_y, f_z, g) and `bq` = b sigma_b are
+// the row's record of the stage image, d1 = log2 e (c_T - c_S) of the target and the source cell.  Out: `ya`, the eight
+// f16 slots psi_k(e_j) W_j b_j of the header comment's table, and `wexp` = W_j = 2^(g + f.d1); the weight itself is the
+// product wexp * bq, which callers sum with cellmm16_weight_sum().
+// The lane half's five monomial factors come from three selects (v_cndmask) and four products, no exec-masked branch:
+// h = 0: x, y, x x, y y | y;  h = 1: z, x z, z z, x y | y z  (the products with 1 are exact).
+// The two contractions the compiler used to find here on its own are written out (fmaf), so that the operand's bits do
+// not depend on what surrounds the call: the mid parts a_k wb - c_k are ONE rounding each (v_fma_mix_f32).
+__device__ __forceinline__ void cellmm16_operand(const f32x4 ef, float bq, float d1x, float d1y, float d1z, int h, f16x8& ya,
+                                                 float& wexp) {
+  const float m0 = h ? ef[2] : ef[0];
+  const float m1 = h ? ef[0] : ef[1];
+  const float m2 = h ? ef[2] : 1.f;
+  const f32x4 a14 = f32x4{m0, m1 * m2, m0 * m0, m1 * ef[1]};
+  const float a5 = ef[1] * m2;
+  const float arg = fmaf(ef[0], d1x, fmaf(ef[1], d1y, fmaf(ef[2], d1z, ef[3])));
+  wexp = kexp2(arg);
+  const float wb = wexp * bq;
+  const float u1 = a14[0] * wb, u2 = a14[1] * wb;
+  const f16x2 R0 = cellmm_pk(u1, u2);
+  const float c1 = (float)R0[0], c2 = (float)R0[1];
+  const f16x2 R1 = cellmm_pk(fmaf(a14[0], wb, -c1), fmaf(a14[1], wb, -c2));
+  const f16x2 R3 = cellmm_pk(a14[2] * wb, a14[3] * wb);
+  const f16x2 R2 = cellmm_pk(c1, a5 * wb);
+  i32x4 yw;
+  yw[0] = __builtin_bit_cast(int, R0);
+  yw[1] = __builtin_bit_cast(int, R1);
+  yw[2] = __builtin_bit_cast(int, R2);
+  yw[3] = __builtin_bit_cast(int, R3);
+  ya = __builtin_bit_cast(f16x8, yw);
+}
+// S0 += W_j b_j, compensated (Kahan) as in cellmm_kernel.  The product wexp * bq enters the sum through ONE rounding,
+// fmaf(bq, wexp, -S0c): a lane that sums a weight somebody else built needs both factors, not their rounded product.
+__device__ __forceinline__ void cellmm16_weight_sum(float bq, float wexp, float& S0, float& S0c) {
+  const float yk = fmaf(bq, wexp, -S0c);
+  const float tk = S0 + yk;
+  S0c = (tk - S0) - yk;
+  S0 = tk;
+}
+
 #ifndef CMM16_NOFOLD
 #define CMM16_NOFOLD 0  // 1: timing only, wrong sums -- the fold and U compiled out, their inputs kept live (what the fold costs)
 #endif
+#ifndef CMM16_BUILD_PROBE
+#define CMM16_BUILD_PROBE 0  // 1: timing only, wrong sums -- wave w builds the operand of every fourth tile only ((q & 3) == w) and
+                             // reuses it for the three tiles between, their records still read: what three of four builds cost
+#endif
 
-// The pair loop of one workgroup: `bid` is its index within the launch (list) that `a` describes, `lds` the workgroup's two
-// stage buffers.
-template <int TT>
-__device__ __forceinline__ void cellmm16_body(const CellmmArgs& a, int bid, unsigned char (*lds)[CMM_STAGE_BYTES]) {
+// LDS of one cellmm16_kernel workgroup.  A workgroup runs ONE body, so the two images share one array:
+//   staged (SHARED = false):  the two stage buffers, raw records, 2 x CMM_STAGE_BYTES
+//   shared (SHARED = true):   abuf[2][12 tiles][64 lanes] finished A operands (16 bytes per lane, as the MFMA reads them), then
+//                             wbuf[2][12 tiles][32 rows] (b sigma_b, W_j) -- both factors of the weight: cellmm16_weight_sum
+constexpr int CMM16_ABUF_BYTES = CMM_STAGE_TILES * 64 * 16;
+constexpr int CMM16_WBUF_OFF = 2 * CMM16_ABUF_BYTES;
+constexpr int CMM16_WBUF_BYTES = CMM_STAGE_TILES * CELL_TILE * 8;
+constexpr int CMM16_SHARED_LDS_BYTES = CMM16_WBUF_OFF + 2 * CMM16_WBUF_BYTES;  // 30 KB
+constexpr int CMM16_SHARED_OWN = CMM_STAGE_TILES / WAVES_PER_BLOCK;            // tiles of a stage each wavefront builds
+static_assert(CMM_STAGE_TILES % WAVES_PER_BLOCK == 0 && CMM_STAGE_TILES <= 64, "a stage's tiles: equal shares, one header lane each");
+// the kernels that hold the shared-build body: more than CELL_REST_TT tiles per wavefront (TT <= 2 runs 6-8 wavefronts per
+// SIMD, which the larger image would cut)
+constexpr bool cellmm16_has_shared(int TT) { return TT >= 8; }
+constexpr int cellmm16_lds_bytes(int TT) { return cellmm16_has_shared(TT) ? CMM16_SHARED_LDS_BYTES : 2 * CMM_STAGE_BYTES; }
+
+// The pair loop of one workgroup: `bid` is its index within the launch (list) that `a` describes, `lds` the workgroup's
+// LDS (cellmm16_lds_bytes).
+//
+// SHARED = false: every wavefront builds the A operand of every source tile itself, from the raw stage in LDS.
+//
+// SHARED = true, for a workgroup whose four wavefronts own tiles of ONE target cell (cellmm16_kernel decides): the operand
+// of a source tile depends on the target side through D1 = log2 e (c_T - c_S) alone, so the four would build the same
+// kilobyte four times.  Here wavefront w builds tiles 3 w .. 3 w + 2 of a stage, once, and all four read them:
+//   * raw rows (ef, bq of row rs) of the wavefront's own three tiles come straight from the image in global memory into
+//     registers, requested for stage s + 2 once stage s + 1's operands are built from them; the stage headers (centre,
+//     key) likewise, lane q holding tile q's, for stages s (consumed), s + 1 (built) and s + 2 (in flight);
+//   * while stage s is consumed from abuf[buf], stage s + 1 is built into abuf[buf ^ 1], which was last read before the
+//     previous barrier -- the discipline of `commit` above; one barrier per stage as before, and every wavefront of the
+//     workgroup passes the same barriers: the stage loop's bounds depend on the segment alone, the tile loop's early exit
+//     (pad tiles) leaves only the tile loop, and no barrier sits inside either;
+//   * a consumer's tile is one ds_read_b128 (its lane's operand), one ds_read_b64 (its row's weight factors), the weight
+//     sum and the MFMAs.  Every lane sums the same weights in the same order through the same fmaf and feeds the MFMAs the
+//     same operand bits as in the staged body: the sums are the same bit for bit.
+template <int TT, bool SHARED>
+__device__ __forceinline__ void cellmm16_body(const CellmmArgs& a, int bid, unsigned char* lds) {
   static_assert(!CMM_BF16, "f16 operands only");
+  static_assert(!SHARED || cellmm16_has_shared(TT), "no shared-build body at this tile count");
   constexpr int SB = CMM_STAGE_BYTES;
   constexpr int PIECES = SB / (16 * BLOCK_THREADS);
   constexpr float LOG2E = 1.4426950408889634f;
   constexpr int HT = 2 * TT;          // half tiles of 16 targets
   constexpr int NG = (HT + 3) / 4;    // fold groups of four half tiles (TT = 1: one, its rows 2 and 3 padded with zeros)
+  constexpr int OWN = CMM16_SHARED_OWN;
 
   int tb, seg;
   block_to_work(bid, a.segments, a.tile_blocks, tb, seg);
@@ -442,7 +523,8 @@ __device__ __forceinline__ void cellmm16_body(const CellmmArgs& a, int bid, unsi
   int64_t s_end = s_begin + a.seg_stages;
   if (s_end > a.m_stages) s_end = a.m_stages;
 
-  f32x4 pre[PIECES];
+  // ---- staged body: stage s + 1 travels through registers, as in cellmm_kernel
+  f32x4 pre[SHARED ? 1 : PIECES];
   auto fetch = [&](int64_t s) {
     const unsigned char* src = a.img + s * SB;
 #pragma unroll
@@ -452,17 +534,67 @@ __device__ __forceinline__ void cellmm16_body(const CellmmArgs& a, int bid, unsi
   auto commit = [&](int buf) {
 #pragma unroll
     for (int p = 0; p < PIECES; ++p)
-      *reinterpret_cast<f32x4*>(&lds[buf][(p * BLOCK_THREADS + (int)threadIdx.x) * 16]) = pre[p];
+      *reinterpret_cast<f32x4*>(lds + buf * SB + (p * BLOCK_THREADS + (int)threadIdx.x) * 16) = pre[p];
   };
-  if (s_begin < s_end) {
-    fetch(s_begin);
-    commit(0);
+
+  // ---- shared body: raw rows of this wavefront's own tiles, and the headers of three stages (lane q: tile q)
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const int hl = lane < CMM_STAGE_TILES ? lane : 0;
+  f32x4 raw_ef[SHARED ? OWN : 1];
+  float raw_b[SHARED ? OWN : 1];
+  f32x4 hcur = {0.f, 0.f, 0.f, 0.f}, hnext = hcur, hfar = hcur;
+  auto load_hdr = [&](int64_t s) { return *reinterpret_cast<const f32x4*>(a.img + s * SB + CMM_HDR_OFF + hl * 16); };
+  auto load_raw = [&](int64_t s, int j) {
+    const unsigned char* src = a.img + s * SB;
+    const int row = (wave_u * OWN + j) * CELL_TILE + rs;
+    raw_ef[j] = *reinterpret_cast<const f32x4*>(src + CMM_E_OFF + row * 16);
+    raw_b[j] = *reinterpret_cast<const float*>(src + CMM_B_OFF + row * 4);
+  };
+  // own tile j of the stage whose header is `hd`, from the raw rows in registers into image `buf`; pad tiles are skipped
+  // (nobody reads them)
+  auto build_tile = [&](int buf, const f32x4 hd, int j) {
+    const int t = wave_u * OWN + j;
+    if (__builtin_amdgcn_readlane(__float_as_int(hd[3]), t) < 0) return;  // wave-uniform
+    float d1[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      d1[c] = (cT[c] - __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hd[c]), t))) * LOG2E;
+    f16x8 ya;
+    float wexp;
+    cellmm16_operand(raw_ef[j], raw_b[j], d1[0], d1[1], d1[2], h, ya, wexp);
+    *reinterpret_cast<f16x8*>(lds + buf * CMM16_ABUF_BYTES + (t * 64 + lane) * 16) = ya;
+    if (h == 0)
+      *reinterpret_cast<f32x2*>(lds + CMM16_WBUF_OFF + buf * CMM16_WBUF_BYTES + (t * CELL_TILE + rs) * 8) = f32x2{raw_b[j], wexp};
+  };
+
+  if constexpr (SHARED) {
+    if (s_begin < s_end) {
+      hcur = load_hdr(s_begin);
+#pragma unroll
+      for (int j = 0; j < OWN; ++j) load_raw(s_begin, j);
+#pragma unroll
+      for (int j = 0; j < OWN; ++j) build_tile(0, hcur, j);
+      if (s_begin + 1 < s_end) {
+        hnext = load_hdr(s_begin + 1);
+#pragma unroll
+        for (int j = 0; j < OWN; ++j) load_raw(s_begin + 1, j);
+      }
+    }
+  } else {
+    if (s_begin < s_end) {
+      fetch(s_begin);
+      commit(0);
+    }
   }
   __syncthreads();
 
   int key_s = -2;
   float S0 = 0.f, S0c = 0.f;
   float D1[3] = {0.f, 0.f, 0.f};
+#if CMM16_BUILD_PROBE
+  f16x8 ya_probe = {};      // the last operand and weight this wave built, reused until its next turn
+  float wexp_probe = 0.f;
+#endif
 
   auto fold = [&]() {  // as in cellmm_kernel, transposed (cellmm16_fold4)
 #if CMM16_NOFOLD
@@ -503,55 +635,83 @@ __device__ __forceinline__ void cellmm16_body(const CellmmArgs& a, int bid, unsi
 
   for (int64_t s = s_begin; s < s_end; ++s) {
     const int buf = (int)((s - s_begin) & 1);
-    if (s + 1 < s_end) fetch(s + 1);
-    const unsigned char* base = &lds[buf][0];
-    const unsigned char* p_ef = base + CMM_E_OFF + rs * 16;
-    const unsigned char* p_b = base + CMM_B_OFF + rs * 4;
-    const f32x4* hdr = reinterpret_cast<const f32x4*>(base + CMM_HDR_OFF);
-    // the stage's cell keys, lane q holding tile q's: a tile's key is then one v_readlane, and the reads of its e and b
-    // no longer queue behind a header read and its wait
-    const int keys = lane < CMM_STAGE_TILES ? __float_as_int(hdr[lane < CMM_STAGE_TILES ? lane : 0][3]) : -1;
-#pragma unroll 1
-    for (int q = 0; q < CMM_STAGE_TILES; ++q) {
-      const int ks = __builtin_amdgcn_readlane(keys, q);
-      if (ks < 0) break;                         // pad tiles (key -1) only trail the last source tile (wave-uniform)
-      if (ks != key_s) new_cell(hdr[q], ks);     // wave-uniform, once per ~30 tiles
-      // ---- A = psi_k(e_j) W_j(T) b_j for source row rs, slot half h (as cellmm_kernel)
-      const f32x4 ef = *reinterpret_cast<const f32x4*>(p_ef);
-      const float bq = *reinterpret_cast<const float*>(p_b);
-      p_ef += CELL_TILE * 16;
-      p_b += CELL_TILE * 4;
-      // the lane half's five monomial factors from three selects (v_cndmask) and four products, no exec-masked branch:
-      // h = 0: x, y, x x, y y | y;  h = 1: z, x z, z z, x y | y z  (the products with 1 are exact)
-      const float m0 = h ? ef[2] : ef[0];
-      const float m1 = h ? ef[0] : ef[1];
-      const float m2 = h ? ef[2] : 1.f;
-      const f32x4 a14 = f32x4{m0, m1 * m2, m0 * m0, m1 * ef[1]};
-      const float a5 = ef[1] * m2;
-      const float arg = fmaf(ef[0], D1[0], fmaf(ef[1], D1[1], fmaf(ef[2], D1[2], ef[3])));
-      const float wb = kexp2(arg) * bq;
-      {
-        const float yk = wb - S0c;
-        const float tk = S0 + yk;
-        S0c = (tk - S0) - yk;
-        S0 = tk;
-      }
-      const float u1 = a14[0] * wb, u2 = a14[1] * wb;
-      const f16x2 R0 = cellmm_pk(u1, u2);
-      const float c1 = (float)R0[0], c2 = (float)R0[1];
-      const f16x2 R1 = cellmm_pk(u1 - c1, u2 - c2);
-      const f16x2 R3 = cellmm_pk(a14[2] * wb, a14[3] * wb);
-      const f16x2 R2 = cellmm_pk(c1, a5 * wb);
-      i32x4 yw;
-      yw[0] = __builtin_bit_cast(int, R0);
-      yw[1] = __builtin_bit_cast(int, R1);
-      yw[2] = __builtin_bit_cast(int, R2);
-      yw[3] = __builtin_bit_cast(int, R3);
-      const f16x8 ya = __builtin_bit_cast(f16x8, yw);
+    if constexpr (SHARED) {
+      // The builds wait for their raw rows here, not in the tile loop, and the rows were requested a stage ago.  The
+      // requests for stage s + 2 follow the LAST build: the wait counter is in order, and a request in front of a build
+      // would make that build wait for it (a full trip to memory, every stage).
+      if (s + 1 < s_end) {
 #pragma unroll
-      for (int u = 0; u < HT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ya, xb[u], acc[u], 0, 0, 0);
+        for (int j = 0; j < OWN; ++j) build_tile(buf ^ 1, hnext, j);
+      }
+      if (s + 2 < s_end) {
+        hfar = load_hdr(s + 2);
+#pragma unroll
+        for (int j = 0; j < OWN; ++j) load_raw(s + 2, j);
+      }
+      const unsigned char* p_ya = lds + buf * CMM16_ABUF_BYTES + lane * 16;
+      const unsigned char* p_w = lds + CMM16_WBUF_OFF + buf * CMM16_WBUF_BYTES + rs * 8;
+      const int keys = lane < CMM_STAGE_TILES ? __float_as_int(hcur[3]) : -1;
+#pragma unroll 1
+      for (int q = 0; q < CMM_STAGE_TILES; ++q) {
+        const int ks = __builtin_amdgcn_readlane(keys, q);
+        if (ks < 0) break;  // pad tiles (key -1) only trail the last source tile (wave-uniform)
+        if (ks != key_s) {  // wave-uniform, once per ~30 tiles
+          f32x4 cs;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) cs[c] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hcur[c]), q));
+          cs[3] = 0.f;
+          new_cell(cs, ks);
+        }
+        const f16x8 ya = *reinterpret_cast<const f16x8*>(p_ya);
+        const f32x2 w = *reinterpret_cast<const f32x2*>(p_w);
+        p_ya += 64 * 16;
+        p_w += CELL_TILE * 8;
+        cellmm16_weight_sum(w[0], w[1], S0, S0c);
+#pragma unroll
+        for (int u = 0; u < HT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ya, xb[u], acc[u], 0, 0, 0);
+      }
+      hcur = hnext;
+      hnext = hfar;
+    } else {
+      if (s + 1 < s_end) fetch(s + 1);
+      const unsigned char* base = lds + buf * SB;
+      const unsigned char* p_ef = base + CMM_E_OFF + rs * 16;
+      const unsigned char* p_b = base + CMM_B_OFF + rs * 4;
+      const f32x4* hdr = reinterpret_cast<const f32x4*>(base + CMM_HDR_OFF);
+      // the stage's cell keys, lane q holding tile q's: a tile's key is then one v_readlane, and the reads of its e and b
+      // no longer queue behind a header read and its wait
+      const int keys = lane < CMM_STAGE_TILES ? __float_as_int(hdr[hl][3]) : -1;
+#pragma unroll 1
+      for (int q = 0; q < CMM_STAGE_TILES; ++q) {
+        const int ks = __builtin_amdgcn_readlane(keys, q);
+        if (ks < 0) break;                         // pad tiles (key -1) only trail the last source tile (wave-uniform)
+        if (ks != key_s) new_cell(hdr[q], ks);     // wave-uniform, once per ~30 tiles
+        // ---- A = psi_k(e_j) W_j(T) b_j for source row rs, slot half h (cellmm16_operand)
+        const f32x4 ef = *reinterpret_cast<const f32x4*>(p_ef);
+        const float bq = *reinterpret_cast<const float*>(p_b);
+        p_ef += CELL_TILE * 16;
+        p_b += CELL_TILE * 4;
+#if CMM16_BUILD_PROBE
+        if ((q & 3) == wave_u) {
+          cellmm16_operand(ef, bq, D1[0], D1[1], D1[2], h, ya_probe, wexp_probe);
+        } else {
+          asm volatile("" ::"v"(ef[0]), "v"(ef[1]), "v"(ef[2]), "v"(ef[3]));
+        }
+        asm volatile("" ::"v"(bq), "v"(S0));
+        const f16x8 ya = ya_probe;
+        const float wexp = wexp_probe;
+#else
+        f16x8 ya;
+        float wexp;
+        cellmm16_operand(ef, bq, D1[0], D1[1], D1[2], h, ya, wexp);
+#endif
+        cellmm16_weight_sum(bq, wexp, S0, S0c);
+        // ONE site of accumulating MFMAs per body and no branch around it (cellmm_kernel)
+#pragma unroll
+        for (int u = 0; u < HT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ya, xb[u], acc[u], 0, 0, 0);
+      }
+      if (s + 1 < s_end) commit(buf ^ 1);
     }
-    if (s + 1 < s_end) commit(buf ^ 1);
     __syncthreads();
   }
   if (key_s >= 0) fold();
@@ -568,25 +728,48 @@ __device__ __forceinline__ void cellmm16_body(const CellmmArgs& a, int bid, unsi
       a.part[(int64_t)seg * a.n_slots + (tile0 + 2 * g + (kg >> 1) - a.tile_base) * CELL_TILE + 16 * h + cc] = outd[g] * inv;
 }
 
+// Is workgroup `bid` of list `a` a ONE-CELL workgroup: do its four wavefronts' first tiles carry the same cell centre, bit
+// for bit?  The centre is all a source operand takes from the target side.  Every wavefront reads the four records itself:
+// no LDS exchange, no barrier, and the answer is the same in all of them.
+template <int TT>
+__device__ __forceinline__ bool cellmm16_one_cell(const CellmmArgs& a, int bid) {
+  int tb, seg;
+  block_to_work(bid, a.segments, a.tile_blocks, tb, seg);
+  const int* m = reinterpret_cast<const int*>(a.tmeta) + (a.tile_base + (int64_t)tb * WAVES_PER_BLOCK * TT) * 4;
+  int differ = 0;
+#pragma unroll
+  for (int w = 1; w < WAVES_PER_BLOCK; ++w)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) differ |= m[(int64_t)w * TT * 4 + c] ^ m[c];
+  return __builtin_amdgcn_readfirstlane(differ) == 0;
+}
+
 // One launch for both target lists (TT > CELL_REST_TT).  The leftover list's workgroups are short and few: a launch of
 // their own starts only when the main list's last round of workgroups has drained and then runs latency-bound on a
 // chip it cannot fill.  Here they are the LAST workgroups of the main list's grid (fused_cell_work, kmvp_plan.hpp), so
 // they are dispatched into the slots that last round leaves empty.  Workgroups below `main_grid` run the TT body on the
 // main list `a`; those behind run the CELL_REST_TT body on `rest`, with that list's own segments, stages and region of
 // the partial sums.  The branch is uniform per workgroup, each body keeps its one site of accumulating MFMAs and its own
-// accumulators, and both share the two stage buffers.  main_grid == gridDim.x: the main list alone (`rest` is not read).
+// accumulators, and all share the one LDS array.  main_grid == gridDim.x: the main list alone (`rest` is not read).
+// a.shared_build != 0: the main list's one-cell workgroups (cellmm16_one_cell) run the shared-build body.
 template <int TT>
 __global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(TT >= 8 ? 2 : 1)))
 cellmm16_kernel(const CellmmArgs a, const CellmmArgs rest, const int main_grid) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2][CMM_STAGE_BYTES];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[cellmm16_lds_bytes(TT)];
   if constexpr (TT > CELL_REST_TT) {
     const FusedCellWork w = fused_cell_work((int64_t)blockIdx.x, (int64_t)main_grid);
     if (w.list) {
-      cellmm16_body<CELL_REST_TT>(rest, (int)w.local, lds);
+      cellmm16_body<CELL_REST_TT, false>(rest, (int)w.local, lds);
       return;
     }
   }
-  cellmm16_body<TT>(a, (int)blockIdx.x, lds);
+  if constexpr (cellmm16_has_shared(TT)) {
+    if (a.shared_build && cellmm16_one_cell<TT>(a, (int)blockIdx.x)) {
+      cellmm16_body<TT, true>(a, (int)blockIdx.x, lds);
+      return;
+    }
+  }
+  cellmm16_body<TT, false>(a, (int)blockIdx.x, lds);
 }
 
 // shape: 0 = cellmm_kernel (32x32x16), 1 = cellmm16_kernel (16x16x32)

@@ -148,6 +148,7 @@ struct kmvp_ctx {
   int opt_feed = -1, opt_T = 0, opt_segments = 0, opt_chunk = 512;
   int opt_fast = -1, opt_fast_tiles = 0;  // fast_sqdists: -1 auto, 0 never, 1 always, 2 always the centred form, 3 always the cell form
   int opt_cellmm_shape = -1;              // cellmm_kernel's MFMA shape: 0 = 32x32x16, 1 = 16x16x32 (cellmm16_kernel), -1 = by size
+  int opt_cell_shared_build = -1;         // cellmm16_kernel's one-cell workgroups build each source operand once: -1 / 1 = where the kernel holds that body (cell_shared_build), 0 = never
   int opt_cell_fused = -1;                // cellmm16_kernel's two tile lists: -1 / 1 = one launch where it applies (fused_cell_grid), 0 = two launches
   int opt_mfma_variant = -1;              // bf16 path: VAR of mfma_pipe_kernel (kmvp_mfma.hpp); -1 = by kernel
   int opt_same_global = 0;                // the targets ARE the (unsharded) sources although x was passed explicitly

@@ -282,4 +282,30 @@ inline FusedCellGrid fused_cell_grid(const CellSplit& s, int tt, int opt_fused) 
   return g;
 }
 
+// ---- one-cell workgroups (cellmm16_kernel's shared operand build) -------------------------------------------------------
+
+constexpr int CELL_SHARED_TT = 8;  // tiles per wavefront from which cellmm16_kernel holds the shared-build body
+
+// Does a MAIN launch with tt tiles per wavefront ask its one-cell workgroups for the shared build?  opt: the
+// "cell_shared_build" option, -1 = automatic and 1 = wherever the kernel holds that body, 0 = never.  At four tiles per
+// wavefront the second body would cost the kernel its fourth wavefront per SIMD (118 -> 142 registers) for every workgroup,
+// shared or not, so it is not instantiated there.
+constexpr bool cell_shared_build(int tt, int opt) { return opt != 0 && tt >= CELL_SHARED_TT; }
+
+// One-cell workgroups of a MAIN list: a workgroup is WAVES_PER_BLOCK wavefronts of tt tiles each, and one-cell when the
+// first tiles of its wavefronts carry the same cell key (a wavefront's tiles are of one cell by construction).  The kernel
+// compares the tiles' stored centres instead (cellmm16_one_cell); on one grid a key and a centre name the same cell.
+// `keys`: the keys of the list's n_main tiles (a multiple of tt * WAVES_PER_BLOCK).  Returns the number of one-cell
+// workgroups; the others are n_main / (tt * WAVES_PER_BLOCK) minus that.
+inline int64_t count_one_cell_blocks(const unsigned* keys, int64_t n_main, int tt) {
+  const int64_t per_block = (int64_t)tt * WAVES_PER_BLOCK;
+  int64_t one = 0;
+  for (int64_t t = 0; t + per_block <= n_main; t += per_block) {
+    bool same = true;
+    for (int w = 1; w < WAVES_PER_BLOCK; ++w) same = same && keys[t + (int64_t)w * tt] == keys[t];
+    one += same ? 1 : 0;
+  }
+  return one;
+}
+
 }  // namespace kmvp

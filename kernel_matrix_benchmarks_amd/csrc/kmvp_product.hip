@@ -1615,6 +1615,7 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
   a.img = (const unsigned char*)c->rec.p;
   a.scale = scale;
   a.m_stages = m_stages;
+  a.shared_build = cell_shared_build(TT, c->opt_cell_shared_build) ? 1 : 0;  // the kernel decides per workgroup (cellmm16_one_cell)
   if (NE == 1 && !sig_stale) HIP_TRY(c, mark(c, 0));  // resident signal: the timed region is the pair loop alone
   for (int col = 0; col < NE; ++col) {
     if (sig_stale) {  // the signal part of the image: max |b| -> sigma_b -> b sigma_b in tile order
