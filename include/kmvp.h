@@ -267,6 +267,49 @@ int kmvp_matern52_cg_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int
 int kmvp_invdist_minres_solve(kmvp_ctx* ctx, const void* a, int E, double rtol, int maxit,
                               double* out_b, int* iters, double* resid);
 
+/* Stochastic Lanczos quadrature (an extension: the other half of a Gaussian-process training objective,
+ *     log p(a) = -1/2 a' A^-1 a - 1/2 log det A - n/2 log 2 pi,    A = K + ridge I + diag(d) as kmvp_set_solver_diagonal set it,
+ * without the N x N matrix).  Conjugate gradients on A x_e = z_e for P probe columns z (N,P) in the ctx dtype, from
+ * x = 0, keeping the step lengths alpha_k, beta_k of every iteration: they are the Lanczos tridiagonal of (A, z_e), and
+ * with theta_i, tau_i its eigenvalues and the first components of its eigenvectors (csrc/kmvp_quadrature.hpp)
+ *     logquad[e] = |z_e|^2 sum_i tau_i^2 log(theta_i)  ~  z_e' log(A) z_e        invquad[e] = z_e' x_e  ~  z_e' A^-1 z_e.
+ * The estimator is the caller's: with Rademacher (+-1) columns z, (1/P) sum_e logquad[e] estimates log det A and
+ * (1/P) sum_e invquad[e] estimates tr A^-1; their statistical error (sample standard deviation / sqrt(P)) is the
+ * caller's too.  The library draws nothing: the same z give the same bits.  The quadrature's own error is of the order
+ * of rtol^2 relative to |z_e|^2 sum tau^2 |log theta| (measured: <= 1.5 rtol^2 on the systems of
+ * tests/lanczos_reference.py), far below the statistical one for any rtol <= 1e-2.
+ *   Every column is on its own clock: it FREEZES after the first iteration with sqrt(rs / |z_e|^2) <= rtol on the
+ *   RECURRENCE residual rs (there is no residual replacement and no final true residual: a restart would break the
+ *   three-term recurrence the coefficients stand for), and takes no further update -- unlike kmvp_<kernel>_cg_solve,
+ *   whose converged columns go on iterating until all have converged.  A column whose recurrence breaks down
+ *   (p' A p == 0 or rs <= 0) freezes one step earlier; a zero column never starts; NaN never freezes a column.  The
+ *   iteration ends once every column is frozen, or after maxit iterations.
+ *   steps[e]: the iterations column e took (0 for a zero column: logquad = invquad = 0, x = 0).
+ *   x (N,P) float64 or NULL: the iterates, each column as it was when it froze.
+ *   alpha, beta (maxit,P) float64 or NULL: row k - 1 holds iteration k; rows >= steps[e] of column e are unspecified.
+ * Returns KMVP_OK when every non-zero column froze on the tolerance with a finite logquad; otherwise
+ * KMVP_E_NOT_CONVERGED with everything written (logquad is NaN where a theta_i <= 0 or a coefficient is not finite: the
+ * operator was not positive definite in working precision).  KMVP_E_INVALID / KMVP_E_UNSUPPORTED as for the CG entries
+ * (targets != sources, a diagonal of the wrong length, ridge + d_i < 0, P < 1, maxit < 0, rtol <= 0, a NULL z, logquad,
+ * invquad or steps; a bfloat16 context is KMVP_E_UNSUPPORTED).  There is no inverse-distance entry: that matrix is
+ * indefinite and log is not defined on its spectrum.
+ * Device-resident like the solvers (one look of the host every 8 iterations, the burst replayed as a graph in long
+ * runs, the operator sharded and the vectors replicated with a communicator: every rank returns bitwise the same
+ * values); fixed summation order, no atomics: bitwise reproducible run to run.  The context is left as after a solve (no
+ * signal).  kmvp_last_kernel_ms and kmvp_last_total_ms both cover the whole call. */
+int kmvp_gaussian_lanczos_quadrature(kmvp_ctx* ctx, const void* z, int P, double rtol, int maxit, double* logquad,
+                                     double* invquad, int* steps, double* x_or_null, double* alpha_or_null,
+                                     double* beta_or_null);
+int kmvp_absexp_lanczos_quadrature(kmvp_ctx* ctx, const void* z, int P, double rtol, int maxit, double* logquad,
+                                   double* invquad, int* steps, double* x_or_null, double* alpha_or_null,
+                                   double* beta_or_null);
+int kmvp_matern32_lanczos_quadrature(kmvp_ctx* ctx, const void* z, int P, double rtol, int maxit, double* logquad,
+                                     double* invquad, int* steps, double* x_or_null, double* alpha_or_null,
+                                     double* beta_or_null);
+int kmvp_matern52_lanczos_quadrature(kmvp_ctx* ctx, const void* z, int P, double rtol, int maxit, double* logquad,
+                                     double* invquad, int* steps, double* x_or_null, double* alpha_or_null,
+                                     double* beta_or_null);
+
 /* Sinkhorn iteration of entropic optimal transport (an extension, the solver on top of kmvp_<kernel>_logsumexp as the
  * Krylov solvers are on top of the product): the iteration stays on the device, three doubles (stop word, iteration
  * count, error) cross to the host per iteration.  Targets x (N,D) and sources y (M,D) are the clouds given to kmvp_set_points (x_or_null == NULL:

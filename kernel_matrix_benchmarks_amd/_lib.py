@@ -61,6 +61,10 @@ SYMBOLS = [
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_invdist_minres_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                              _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
+    ("kmvp_gaussian_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
+    ("kmvp_absexp_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
+    ("kmvp_matern32_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
+    ("kmvp_matern52_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
     ("kmvp_gaussian_sinkhorn", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p,
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_absexp_sinkhorn", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p,
@@ -266,6 +270,40 @@ class Context:
         if rc not in (0, 6):
             self._check(rc)
         return out, iters.value, resid.value, rc == 0
+
+    def lanczos_quadrature(self, kernel, z, rtol, maxit, want_x=False, want_coefficients=False):
+        """Stochastic Lanczos quadrature on the probe columns z (N, P) in the context's dtype (include/kmvp.h
+        kmvp_<kernel>_lanczos_quadrature).  Returns a dict: logquad, invquad (P float64), steps (P int), converged, and x
+        (N, P) / alpha, beta (maxit, P) when asked for; raises on every status but OK and NOT_CONVERGED."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_lanczos_quadrature,
+            "absolute-exponential": self._lib.kmvp_absexp_lanczos_quadrature,
+            "matern-3/2": self._lib.kmvp_matern32_lanczos_quadrature,
+            "matern-5/2": self._lib.kmvp_matern52_lanczos_quadrature,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no Lanczos quadrature for kernel {kernel}")
+        if z.ndim != 2 or z.shape[0] != getattr(self, "N", z.shape[0]) or not z.flags.c_contiguous:
+            # the library reads N * P elements from the pointer: a shorter array must never reach it
+            raise ValueError(f"the probes have shape {z.shape}, expected a contiguous ({getattr(self, 'N', '?')}, P) array")
+        N, P = z.shape
+        maxit = int(maxit)
+        logquad, invquad = np.empty(P, dtype=np.float64), np.empty(P, dtype=np.float64)
+        steps = np.empty(P, dtype=np.intc)
+        x = np.empty((N, P), dtype=np.float64) if want_x else None
+        alpha = np.empty((max(maxit, 0), P), dtype=np.float64) if want_coefficients else None
+        beta = np.empty((max(maxit, 0), P), dtype=np.float64) if want_coefficients else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = entry(self._ctx, z.ctypes.data, P, float(rtol), maxit, logquad.ctypes.data, invquad.ctypes.data,
+                   steps.ctypes.data, ptr(x), ptr(alpha), ptr(beta))
+        if rc not in (0, 6):
+            self._check(rc)
+        out = {"logquad": logquad, "invquad": invquad, "steps": steps.astype(np.int64), "converged": rc == 0}
+        if want_x:
+            out["x"] = x
+        if want_coefficients:
+            out["alpha"], out["beta"] = alpha, beta
+        return out
 
     def sinkhorn(self, kernel, log_a, log_b, tol, maxit, u0=None):
         """Sinkhorn iteration on the clouds of set_points (include/kmvp.h kmvp_<kernel>_sinkhorn): log_a (N) / log_b (M)

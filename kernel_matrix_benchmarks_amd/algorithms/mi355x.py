@@ -23,6 +23,8 @@ Differences a user should know about
    solves the regularised system (K + ridge I) b = a instead, which is well posed
    and is tested against a dense solve on the solution vector.
 """
+import collections
+
 import numpy as np
 
 from kernel_matrix_benchmarks_amd import _lib
@@ -399,6 +401,11 @@ class MI355XProduct(BaseProduct):
             pass
 
 
+# What MI355XSolver.log_determinant returns: the estimates with their standard errors (sample standard deviation over
+# the probes / sqrt(probes)), the iterations every probe column took, and whether every column met the tolerance.
+LogDeterminant = collections.namedtuple("LogDeterminant", "value stderr trace_inverse trace_inverse_stderr steps converged")
+
+
 class MI355XSolver(BaseSolver):
     """Solves K b = a with the HIP product as the operator: conjugate gradients for the positive
     definite Gaussian / exp(-r) / Matern matrices, MINRES for the symmetric indefinite inverse-distance
@@ -638,6 +645,50 @@ class MI355XSolver(BaseSolver):
                 self.stop_reason = "tolerance"
         self.res, self.residual = x, rel
         self.converged = bool(np.isfinite(rel) and rel <= 1.5 * self.rtol)
+
+    def log_determinant(self, probes=32, seed=0, rtol=None, maxit=None):
+        """log det A and tr A^-1 of A = K + ridge (the matrix query() solves with), without the matrix: stochastic Lanczos
+        quadrature on ``probes`` Rademacher columns (include/kmvp.h kmvp_<kernel>_lanczos_quadrature), after
+        prepare_data().  ``value`` is the mean of the per-probe z' log(A) z and ``stderr`` their sample standard
+        deviation / sqrt(probes) -- the statistical error, which more probes reduce and a tighter ``rtol`` (default: the
+        solver's) does not; ``trace_inverse`` likewise from z' A^-1 z.  The probes depend on (M, probes, seed) alone, so
+        every rank of a sharded solver draws the same ones and returns the same bits."""
+        what = (f"kernel {self.kernel}" if self.method != "cg" or self._dot else "refine" if self.refine else
+                "normalize_rows" if self.normalize_rows else None)
+        if what:
+            raise NotImplementedError(f"MI355XSolver.log_determinant doesn't support {what}.")
+        if self._ctx is None:
+            raise RuntimeError("log_determinant() needs prepare_data() first")
+        probes = int(probes)
+        if probes < 2:
+            raise ValueError("log_determinant needs at least 2 probes (the standard error is a sample deviation)")
+        z = np.where(np.random.RandomState(seed).rand(self.M, probes) < 0.5, -1.0, 1.0)
+        self._apply_diagonal()
+        out = self._ctx.lanczos_quadrature(self._device_kernel_fn, np.ascontiguousarray(z, dtype=self._host_dtype),
+                                           self.rtol if rtol is None else rtol, self.maxit if maxit is None else maxit)
+        root = np.sqrt(probes)
+        return LogDeterminant(value=float(np.mean(out["logquad"])), stderr=float(np.std(out["logquad"], ddof=1) / root),
+                              trace_inverse=float(np.mean(out["invquad"])),
+                              trace_inverse_stderr=float(np.std(out["invquad"], ddof=1) / root),
+                              steps=out["steps"], converged=bool(out["converged"]))
+
+    def log_marginal_likelihood(self, probes=32, seed=0):
+        """log p(a) of a zero-mean Gaussian process with covariance A = K + ridge, summed over the E columns of the last
+        query()'s target_signal a (b = A^-1 a is its result):
+            -1/2 sum_e a_e' b_e  -  E/2 log det A  -  E M / 2 log 2 pi
+        with log det A from log_determinant(probes, seed).  Returns (value, stderr); the standard error is the
+        log-determinant's share, E/2 times its own (the quadratic term is exact to the solve's rtol)."""
+        if getattr(self, "res", None) is None or getattr(self, "_a", None) is None:
+            raise RuntimeError("log_marginal_likelihood() needs prepare_query() and query() first")
+        if not self.converged:
+            raise RuntimeError(f"log_marginal_likelihood(): the last solve did not converge (relative residual {self.residual:g})")
+        logdet = self.log_determinant(probes=probes, seed=seed)
+        if not logdet.converged:
+            raise RuntimeError("log_marginal_likelihood(): the Lanczos quadrature did not converge")
+        a = np.asarray(self._a, dtype=np.float64)
+        E = a.shape[1]
+        value = -0.5 * float(np.sum(a * self.res)) - 0.5 * E * logdet.value - 0.5 * E * self.M * np.log(2.0 * np.pi)
+        return value, 0.5 * E * logdet.stderr
 
     def get_memory_usage(self):
         return 0.0 if self._ctx is None else self._ctx.device_bytes / 1024

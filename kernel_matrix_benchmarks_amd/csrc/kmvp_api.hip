@@ -224,6 +224,23 @@ int kmvp_invdist_minres_solve(kmvp_ctx* c, const void* a, int E, double rtol, in
   return minres_solve(c, K_INVDIST, a, E, rtol, maxit, out_b, iters, resid);
 }
 
+int kmvp_gaussian_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double rtol, int maxit, double* logquad,
+                                     double* invquad, int* steps, double* x, double* alpha, double* beta) {
+  return cg_lanczos(c, K_GAUSSIAN, z, P, rtol, maxit, logquad, invquad, steps, x, alpha, beta);
+}
+int kmvp_absexp_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double rtol, int maxit, double* logquad,
+                                   double* invquad, int* steps, double* x, double* alpha, double* beta) {
+  return cg_lanczos(c, K_ABSEXP, z, P, rtol, maxit, logquad, invquad, steps, x, alpha, beta);
+}
+int kmvp_matern32_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double rtol, int maxit, double* logquad,
+                                     double* invquad, int* steps, double* x, double* alpha, double* beta) {
+  return cg_lanczos(c, K_MATERN32, z, P, rtol, maxit, logquad, invquad, steps, x, alpha, beta);
+}
+int kmvp_matern52_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double rtol, int maxit, double* logquad,
+                                     double* invquad, int* steps, double* x, double* alpha, double* beta) {
+  return cg_lanczos(c, K_MATERN52, z, P, rtol, maxit, logquad, invquad, steps, x, alpha, beta);
+}
+
 int kmvp_gaussian_sinkhorn(kmvp_ctx* c, const double* log_a, const double* log_b, double tol, int maxit, double* u, double* v,
                            int* iters, double* err) {
   return sinkhorn_solve(c, K_GAUSSIAN, log_a, log_b, tol, maxit, u, v, iters, err);

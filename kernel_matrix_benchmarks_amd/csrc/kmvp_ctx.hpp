@@ -2,7 +2,7 @@
 // functions the translation units call across each other.
 //   kmvp_api.hip      the extern "C" surface of include/kmvp.h
 //   kmvp_product.hip  layouts, launch geometry, the pair-loop paths and the policy that picks one
-//   kmvp_solvers.hip  conjugate gradients and MINRES on the product
+//   kmvp_solvers.hip  conjugate gradients, MINRES and the Lanczos quadrature on the product
 //   kmvp_sinkhorn.hip the Sinkhorn iteration of entropic optimal transport on the log-sum-exp
 #pragma once
 #include <dlfcn.h>
@@ -212,6 +212,8 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
              int* iters, double* resid);
 int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit,
                  double* out_b, int* iters, double* resid);
+int cg_lanczos(kmvp_ctx* c, int kernel, const void* z_host, int P, double rtol, int maxit, double* logquad, double* invquad,
+               int* steps, double* x_out, double* alpha_out, double* beta_out);
 
 // kmvp_sinkhorn.hip: kmvp_<kernel>_sinkhorn, the device-resident Sinkhorn iteration on lowd_lse_kernel
 int sinkhorn_solve(kmvp_ctx* c, int kernel, const double* log_a, const double* log_b, double tol, int maxit, double* u,

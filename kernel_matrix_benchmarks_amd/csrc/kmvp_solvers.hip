@@ -4,9 +4,12 @@
 // parity is judged on the residual.
 // With kmvp_set_solver_diagonal the operator of both is A = K + ridge I + diag(d): the product is untouched, the
 // diagonal term is added to K v by the first kernel that consumes it (the *_diag_* variants below).
+// cg_lanczos is conjugate gradients once more, for its coefficients rather than its iterate: every column on its own
+// clock, the step lengths of every iteration kept, and the Gauss quadrature of log on them (kmvp_quadrature.hpp).
 #include <cstdlib>
 
 #include "kmvp_ctx.hpp"
+#include "kmvp_quadrature.hpp"
 
 namespace kmvp {
 
@@ -185,7 +188,8 @@ __global__ void cg_update_p_kernel(double* __restrict__ p, const double* __restr
 // host side shared by both solvers
 
 // One solve's scratch block: `nvec` Krylov vectors of N x E doubles, the dot products' partial sums, then
-// the device-resident iteration's state, with its stop word at `stop` and the iteration count after it.
+// the device-resident iteration's state, with its stop word at `stop` and the iteration count after it, then `extra`
+// doubles of the solver's own (cg_lanczos: the coefficient history).
 struct Krylov {
   int64_t m = 0;  // length of the Krylov vectors: all points
   int E = 0;
@@ -197,7 +201,7 @@ struct Krylov {
 
 // The checks both solvers make, the device, and the scratch layout.
 static int solver_begin(kmvp_ctx* c, const void* a_host, int E, double rtol, int maxit, const double* out_b, int nvec,
-                        size_t stop, Krylov& k) {
+                        size_t stop, Krylov& k, size_t extra = 0) {
   if (!c) return KMVP_E_INVALID;
   if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
   if (int rc = solver_shape(c)) return rc;
@@ -210,7 +214,7 @@ static int solver_begin(kmvp_ctx* c, const void* a_host, int E, double rtol, int
   k.E = E;
   k.n = (size_t)k.m * E;
   k.stop = stop;
-  if (int rc = ensure(c, c->scratch, sizeof(double) * (nvec * k.n + (size_t)CG_BLOCKS * E + stop + 2))) return rc;
+  if (int rc = ensure(c, c->scratch, sizeof(double) * (nvec * k.n + (size_t)CG_BLOCKS * E + stop + 2 + extra))) return rc;
   k.vecs = (double*)c->scratch.p;
   k.partial = k.vec(nvec);
   k.state = k.partial + (size_t)CG_BLOCKS * E;
@@ -484,6 +488,187 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
     rel = true_rel;
   }
   return solver_end(c, "conjugate gradients", x, k, out_b, it, true_rel, rtol, iters, resid);
+}
+
+
+// ------------------------------------------------------------------------------------
+// conjugate gradients for its coefficients: stochastic Lanczos quadrature (include/kmvp.h kmvp_<kernel>_lanczos_quadrature)
+
+// State per column e: see LZ_* ; then the stop word and the iteration count.  LZ_FROZEN says why a column takes no
+// further update: on the tolerance, by a breakdown of the recurrence (pAp == 0 or rs_old <= 0), or as a zero column.
+enum : int { LZ_RS = 0, LZ_ALPHA, LZ_BETA, LZ_Z2, LZ_FROZEN, LZ_STEPS, LZ_FIELDS };
+constexpr double LZ_LIVE = 0.0, LZ_TOLERANCE = 1.0, LZ_BREAKDOWN = 2.0, LZ_ZERO = 3.0;
+
+// cg_scalars_kernel with every column on its own clock.  One block; same guards on alpha and beta.  Iteration k = count + 1:
+// mode 1 (after p . Ap): alpha, written to row `count` of the history; a column whose guard fires freezes here, with
+//   steps = k - 1 and no row.
+// mode 2 (after r . r): beta into row `count`, rs_old = rs_new, steps = k, and the column freezes once
+//   sqrt(rs_new / |z|^2) <= rtol (NaN: never).  Then count + 1, and the stop word is set in the first iteration that
+//   leaves every column frozen.
+// The row is the DEVICE's count, so a replayed burst graph writes the rows of the iterations it replays.
+__global__ void __launch_bounds__(CG_BLOCKS) lanczos_scalars_kernel(const double* __restrict__ partial,
+                                                                   double* __restrict__ st, int P, int mode, double rtol,
+                                                                   double* __restrict__ hist_alpha,
+                                                                   double* __restrict__ hist_beta, int maxit) {
+  __shared__ double red[CG_BLOCKS];
+  double* stop = st + (size_t)LZ_FIELDS * P;
+  if (*stop != 0.0) return;  // uniform: every thread reads the same word
+  const int64_t row = (int64_t)stop[1];
+  bool live = false;
+  for (int e = 0; e < P; ++e) {
+    const double v = block_sum_partials(partial, P, e, red);
+    if (threadIdx.x != 0) continue;
+    auto S = [&](int f) -> double& { return st[(size_t)f * P + e]; };
+    if (S(LZ_FROZEN) != LZ_LIVE || row >= maxit) continue;
+    const double rs_old = S(LZ_RS);
+    if (mode == 1) {
+      const double alpha = (v != 0.0 && rs_old > 0.0) ? rs_old / v : 0.0;
+      S(LZ_ALPHA) = alpha;
+      if (v == 0.0 || rs_old <= 0.0)
+        S(LZ_FROZEN) = LZ_BREAKDOWN;
+      else
+        hist_alpha[row * P + e] = alpha;
+    } else {
+      const double beta = rs_old > 0.0 ? v / rs_old : 0.0;
+      S(LZ_BETA) = beta;
+      S(LZ_RS) = v;
+      S(LZ_STEPS) = (double)(row + 1);
+      hist_beta[row * P + e] = beta;
+      if (sqrt(v / S(LZ_Z2)) <= rtol)
+        S(LZ_FROZEN) = LZ_TOLERANCE;
+      else
+        live = true;
+    }
+  }
+  if (mode == 2 && threadIdx.x == 0) {
+    stop[1] += 1.0;
+    if (!live) *stop = 1.0;
+  }
+}
+
+// x += alpha p ; r -= alpha Ap in the columns that are live.  A frozen column is skipped, not multiplied by 0: whatever
+// its p and Ap have become, its x and r stay.
+__global__ void lanczos_update_xr_kernel(double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
+                                         const double* __restrict__ Ap, const double* __restrict__ st, int64_t m, int P) {
+  if (st[(size_t)LZ_FIELDS * P] != 0.0) return;  // stopped
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= m * P) return;
+  const int e = (int)(q % P);
+  if (st[(size_t)LZ_FROZEN * P + e] != LZ_LIVE) return;
+  const double a = st[(size_t)LZ_ALPHA * P + e];
+  x[q] = x[q] + a * p[q];
+  r[q] = r[q] + (-a) * Ap[q];
+}
+
+// p = r + beta p in the columns that are live
+__global__ void lanczos_update_p_kernel(double* __restrict__ p, const double* __restrict__ r,
+                                        const double* __restrict__ st, int64_t m, int P) {
+  if (st[(size_t)LZ_FIELDS * P] != 0.0) return;  // stopped
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= m * P) return;
+  const int e = (int)(q % P);
+  if (st[(size_t)LZ_FROZEN * P + e] != LZ_LIVE) return;
+  p[q] = r[q] + st[(size_t)LZ_BETA * P + e] * p[q];
+}
+
+// The recurrence of cg_solve from x = 0, r = p = z, without its residual replacement (a restart would break the three-term
+// recurrence the coefficients stand for): the verdict is on the RECURRENCE residual.  Converged columns do not go on
+// iterating as they do in cg_solve: their later coefficients would be rounding noise.
+int cg_lanczos(kmvp_ctx* c, int kernel, const void* z_host, int P, double rtol, int maxit, double* logquad, double* invquad,
+               int* steps, double* x_out, double* alpha_out, double* beta_out) {
+  if (c && (!logquad || !invquad || !steps)) return fail(c, KMVP_E_INVALID, "bad solver arguments");
+  if (c && c->dtype == KMVP_BF16 && c->have_points)
+    return fail(c, KMVP_E_UNSUPPORTED, "the Lanczos quadrature needs a float32 or float64 context");
+  Krylov k;  // x, r, p, z; state: LZ_FIELDS x P, stop, iterations; then alpha and beta of every iteration, (maxit, P) each
+  const size_t rows = (size_t)std::max(maxit, 0) * (size_t)std::max(P, 0);
+  if (int rc = solver_begin(c, z_host, P, rtol, maxit, logquad, 4, (size_t)LZ_FIELDS * P, k, 2 * rows)) return rc;
+  if (c->diag_on && c->diag_min < 0.0)
+    return fail(c, KMVP_E_INVALID, "solver diagonal: conjugate gradients needs ridge + d_i >= 0 everywhere (smallest: " +
+                                       std::to_string(c->diag_min) + ")");
+  SolveGuard guard{c};
+  BurstGraph graph(c);
+  const bool with_diag = c->diag_on;
+  const Diag diag = solver_diag(c);
+  const int64_t m = k.m;
+  const size_t vec = k.n * sizeof(double);
+  double *x = k.vec(0), *r = k.vec(1), *p = k.vec(2), *z = k.vec(3), *st = k.state;
+  double *hist_alpha = st + k.stop + 2, *hist_beta = hist_alpha + rows;
+  HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
+
+  // z = r = p = the probes (widened to double), x = 0, history = 0
+  int rc = load_rhs(c, z_host, z, k);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(r, z, vec, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(p, z, vec, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(x, 0, vec, c->stream));
+  if (rows) HIP_TRY(c, hipMemsetAsync(hist_alpha, 0, sizeof(double) * 2 * rows, c->stream));
+  std::vector<double> z2, zx;
+  if ((rc = cg_dots(c, z, z, k, z2))) return rc;
+
+  std::vector<double> state(k.stop + 2, 0.0);
+  for (int e = 0; e < P; ++e) {
+    state[(size_t)LZ_RS * P + e] = z2[e];
+    state[(size_t)LZ_Z2 * P + e] = z2[e];
+    state[(size_t)LZ_FROZEN * P + e] = z2[e] == 0.0 ? LZ_ZERO : LZ_LIVE;
+  }
+  HIP_TRY(c, hipMemcpyAsync(st, state.data(), sizeof(double) * state.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const unsigned vblocks = blocks_for(m * P);
+  auto body = [&](int burst) -> int {
+    for (int i = 0; i < burst; ++i) {
+      if (int rcb = cg_apply(c, kernel, p, k)) return rcb;
+      double* Ap = (double*)c->out.p;
+      if (with_diag)  // Ap = K p + diag p, and p . Ap
+        hipLaunchKernelGGL(cg_diag_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, p, Ap, diag, m, P, k.partial);
+      else
+        hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, p, Ap, m, P, k.partial);
+      hipLaunchKernelGGL(lanczos_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, st, P, 1, rtol, hist_alpha,
+                         hist_beta, maxit);
+      hipLaunchKernelGGL(lanczos_update_xr_kernel, dim3(vblocks), dim3(256), 0, c->stream, x, r, p, Ap, st, m, P);
+      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, r, r, m, P, k.partial);
+      hipLaunchKernelGGL(lanczos_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, st, P, 2, rtol, hist_alpha,
+                         hist_beta, maxit);
+      hipLaunchKernelGGL(lanczos_update_p_kernel, dim3(vblocks), dim3(256), 0, c->stream, p, r, st, m, P);
+    }
+    return KMVP_OK;
+  };
+  // run_bursts goes on while "rel" > rtol: infinite while a column is live
+  auto rel_of = [&] {
+    for (int e = 0; e < P; ++e)
+      if (state[(size_t)LZ_FROZEN * P + e] == LZ_LIVE) return (double)INFINITY;
+    return 0.0;
+  };
+  int it = 0;
+  double rel = rel_of();
+  if ((rc = run_bursts(c, k, maxit, rtol, it, rel, state, body, rel_of, &graph))) return rc;
+
+  // z . x per column, then the history, the final state and the iterates in one pass over the stream
+  if ((rc = cg_dots(c, z, x, k, zx))) return rc;
+  std::vector<double> hist(2 * rows);
+  HIP_TRY(c, hipMemcpyAsync(state.data(), st, sizeof(double) * state.size(), hipMemcpyDeviceToHost, c->stream));
+  if (rows) HIP_TRY(c, hipMemcpyAsync(hist.data(), hist_alpha, sizeof(double) * 2 * rows, hipMemcpyDeviceToHost, c->stream));
+  if (x_out) HIP_TRY(c, hipMemcpyAsync(x_out, x, vec, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
+  c->last_kernel_ms = c->last_total_ms;  // both cover the whole call (include/kmvp.h)
+
+  bool ok = true;
+  for (int e = 0; e < P; ++e) {
+    const double frozen = state[(size_t)LZ_FROZEN * P + e];
+    steps[e] = (int)state[(size_t)LZ_STEPS * P + e];
+    logquad[e] = z2[e] * lanczos_quadrature_log(hist.data() + e, hist.data() + rows + e, steps[e], P);
+    invquad[e] = zx[e];
+    if (frozen != LZ_ZERO && !(frozen == LZ_TOLERANCE && std::isfinite(logquad[e]))) ok = false;
+  }
+  if (alpha_out && rows) memcpy(alpha_out, hist.data(), sizeof(double) * rows);
+  if (beta_out && rows) memcpy(beta_out, hist.data() + rows, sizeof(double) * rows);
+  if (!ok) {
+    c->err = "Lanczos quadrature: a column did not reach the requested tolerance on the recurrence residual, or its "
+             "quadrature is not finite (operator not positive definite, non-finite operator or probe)";
+    return KMVP_E_NOT_CONVERGED;
+  }
+  return KMVP_OK;
 }
 
 
