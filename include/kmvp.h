@@ -171,6 +171,33 @@ int kmvp_invdist_grad(kmvp_ctx* ctx);
 int kmvp_matern32_grad(kmvp_ctx* ctx);
 int kmvp_matern52_grad(kmvp_ctx* ctx);
 
+/* Derivative of the product in the logarithm of a per-axis length scale (an extension: no reference method stands
+ * behind it -- the ARD length-scale gradient of a Gaussian-process likelihood, of a Kriging fit, of a bandwidth
+ * selection).  A length scale is the caller's scaling of the points, x / l and y / l with one l_d per axis; at l = 1,
+ * with w the weight of kmvp_<kernel>_grad above,
+ *     d k(x_i, y_j) / d log l_d = -w(s_ij) (x_{i,d} - y_{j,d})^2 =: h_d(x_i, y_j)        (summed over d: -s w)
+ *     H[i, e, d] = sum_j h_d(x_i, y_j) b[j, e]
+ *   kmvp_gaussian_dscale   h_d = 2 k D_d^2                       D_d = x_{i,d} - y_{j,d}
+ *   kmvp_absexp_dscale     h_d = k D_d^2 / r.  A coincident pair contributes exactly 0: the true limit D_d^2 / r -> 0,
+ *                          not a convention.  (float32: s below the smallest normal number counts as 0, as above.)
+ *   kmvp_matern32_dscale   h_d = 3 e^-t D_d^2,  t = sqrt(3) r
+ *   kmvp_matern52_dscale   h_d = (5/3) (1 + t) e^-t D_d^2,  t = sqrt(5) r
+ * There is no inverse-distance entry: that kernel is not a covariance, and its derivative is the kernel itself.
+ * A pair whose squared distance overflows the working precision contributes exactly 0 as long as x - y itself is
+ * finite.  A NaN target coordinate makes that row of H NaN (the Gaussian: every component; the others: at least the
+ * components of the NaN axes) and no other row.  Density estimation (b == NULL) means b = 1, E = 1.  Row normalisation
+ * is not differentiated.
+ * Synchronous like the products; the result is read with kmvp_get_result as (N, E D) float64 row-major, d fastest.
+ * float32 and float64 contexts, D <= 8, E <= 4 (lowd_dscale_kernel, difference form on the product's own packed
+ * layouts: as accurate far from the origin as near it); KMVP_E_UNSUPPORTED beyond that and for bfloat16 contexts.
+ * Honours "segments", "chunk" and "partial_shard"; linear in the sources, so with a communicator attached the (N, E D)
+ * sums of all ranks are all-reduced like a product's.  Results are bitwise reproducible run to run (fixed summation
+ * order, no atomics). */
+int kmvp_gaussian_dscale(kmvp_ctx* ctx);
+int kmvp_absexp_dscale(kmvp_ctx* ctx);
+int kmvp_matern32_dscale(kmvp_ctx* ctx);
+int kmvp_matern52_dscale(kmvp_ctx* ctx);
+
 /* Log-sum-exp reduction of the Gaussian and exp(-r) kernels (an extension: no reference method stands behind it -- the
  * half-iteration of entropic optimal transport (Sinkhorn), log-densities far from the data, the log-partition of a
  * kernel-attention row).  For targets x (N,D), sources y (M,D) and log-weights c (M,E):

@@ -46,6 +46,10 @@ SYMBOLS = [
     ("kmvp_invdist_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_matern32_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_matern52_grad", _c.c_int, [_c.c_void_p]),
+    ("kmvp_gaussian_dscale", _c.c_int, [_c.c_void_p]),
+    ("kmvp_absexp_dscale", _c.c_int, [_c.c_void_p]),
+    ("kmvp_matern32_dscale", _c.c_int, [_c.c_void_p]),
+    ("kmvp_matern52_dscale", _c.c_int, [_c.c_void_p]),
     ("kmvp_gaussian_logsumexp", _c.c_int, [_c.c_void_p]),
     ("kmvp_absexp_logsumexp", _c.c_int, [_c.c_void_p]),
     ("kmvp_gaussian_logsumexp_grad", _c.c_int, [_c.c_void_p]),
@@ -219,6 +223,19 @@ class Context:
         }.get(kernel)
         if entry is None:
             raise NotImplementedError(f"no gradient for kernel {kernel}")
+        self._check(entry(self._ctx))
+
+    def run_dscale(self, kernel):
+        """Derivative in the logarithm of a per-axis length scale (include/kmvp.h kmvp_<kernel>_dscale); read it with
+        get_result(N, E * D)."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_dscale,
+            "absolute-exponential": self._lib.kmvp_absexp_dscale,
+            "matern-3/2": self._lib.kmvp_matern32_dscale,
+            "matern-5/2": self._lib.kmvp_matern52_dscale,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no length-scale derivative for kernel {kernel}")
         self._check(entry(self._ctx))
 
     def run_lse(self, kernel):

@@ -55,6 +55,8 @@ MATERN_KERNELS = ("matern-3/2", "matern-5/2")
 #    (EXPDOT_IDENTITY_SPREAD), NotImplementedError beyond it -- never a silent zero weight.
 SQRT_HALF = 0.7071067811865476
 GRADIENT_MAX_D, GRADIENT_MAX_E = 8, 4  # lowd_grad_kernel's instantiations (csrc/kmvp_internal.hpp LOWD_MAX_D, LOWD_MAX_E)
+# lowd_dscale_kernel: the derivative in the per-axis length scales, at the gradient's shapes; no 1/r (not a covariance)
+SCALE_DERIVATIVE_KERNELS = ("gaussian", "absolute-exponential", "matern-3/2", "matern-5/2")
 # lowd_lse_kernel: the log-sum-exp reduction is built for these kernels, at the gradient's shapes
 LOGSUMEXP_KERNELS = ("gaussian", "absolute-exponential")
 LOGSUMEXP_MAX_D, LOGSUMEXP_MAX_E = 8, 4
@@ -301,6 +303,38 @@ class MI355XProduct(BaseProduct):
         """(N, E, D) float64, C-contiguous: the result of the last query_gradient()."""
         return np.ascontiguousarray(self._ctx.get_result(self.N, self.E * self.D).reshape(self.N, self.E, self.D))
 
+    def query_scale_derivative(self):
+        """H[i, e, d] = d/d log l_d of sum_j k(x_i / l, y_j / l) b[j, e] at l = 1, one length scale per axis (include/kmvp.h
+        kmvp_<kernel>_dscale): -w (x_{i,d} - y_{j,d})^2 with the gradient's weight w.  The length scales are the caller's
+        scaling of the points; H.sum(axis=2) is the derivative in one isotropic length scale.  The timed part, like
+        query().  Synchronous."""
+        self._check_scale_derivative_supported()
+        self._ctx.run_dscale(self.kernel)
+        self.res = None
+
+    def _check_scale_derivative_supported(self):
+        """What lowd_dscale_kernel is not built for, refused before the library is called -- the kernel, the precision and
+        the normalisation before prepare_data() too."""
+        what = None
+        if self.kernel not in SCALE_DERIVATIVE_KERNELS:
+            what = f"kernel={self.kernel!r} (gaussian, absolute-exponential, matern-3/2 and matern-5/2 only)"
+        elif self.normalize_rows:
+            what = "normalize_rows=True (the derivative of a ratio of sums is not built)"
+        elif self._dtype_code == _lib.KMVP_BF16:
+            what = "precision='bfloat16' (float16, float32 and float64 only)"
+        if what is None and self._ctx is None:
+            raise RuntimeError("query_scale_derivative() needs prepare_data() and prepare_query() first")
+        if what is None and self.D > GRADIENT_MAX_D:
+            what = f"D = {self.D} > {GRADIENT_MAX_D}"
+        elif what is None and self.E > GRADIENT_MAX_E:
+            what = f"E = {self.E} > {GRADIENT_MAX_E} signal columns (pass them in blocks of {GRADIENT_MAX_E})"
+        if what is not None:
+            raise NotImplementedError(f"MI355XProduct.query_scale_derivative doesn't support {what}.")
+
+    def get_scale_derivative(self):
+        """(N, E, D) float64, C-contiguous: the result of the last query_scale_derivative()."""
+        return np.ascontiguousarray(self._ctx.get_result(self.N, self.E * self.D).reshape(self.N, self.E, self.D))
+
     def query_logsumexp(self):
         """L[i, e] = log sum_j exp(l(x_i, y_j) + c[j, e]), l = -|x - y|^2 (gaussian) or -|x - y| (absolute-exponential),
         with the array given to prepare_query(source_signal=c) read as LOG-weights (density estimation: c = 0; c = -inf:
@@ -404,6 +438,49 @@ class MI355XProduct(BaseProduct):
 # What MI355XSolver.log_determinant returns: the estimates with their standard errors (sample standard deviation over
 # the probes / sqrt(probes)), the iterations every probe column took, and whether every column met the tolerance.
 LogDeterminant = collections.namedtuple("LogDeterminant", "value stderr trace_inverse trace_inverse_stderr steps converged")
+# What MI355XSolver.log_marginal_likelihood_gradient returns: the objective, its derivatives in the logarithm of the D
+# per-axis length scales and in a uniform shift of the diagonal, each with the standard error of its trace estimate.
+MarginalLikelihoodGradient = collections.namedtuple(
+    "MarginalLikelihoodGradient",
+    "value value_stderr d_log_lengthscale d_log_lengthscale_stderr d_ridge d_ridge_stderr converged")
+
+
+def _rademacher_probes(M, probes, seed):
+    """The +-1 probe columns of the trace estimates: a function of (M, probes, seed) alone, so every rank of a sharded
+    solver draws the same ones."""
+    return np.where(np.random.RandomState(seed).rand(M, probes) < 0.5, -1.0, 1.0)
+
+
+def _log_likelihood(a, b, logdet, M):
+    """-1/2 sum_e a_e' b_e - E/2 log det A - E M / 2 log 2 pi with b = A^-1 a (M, E)."""
+    E = a.shape[1]
+    return -0.5 * float(np.sum(a * b)) - 0.5 * E * logdet - 0.5 * E * M * np.log(2.0 * np.pi)
+
+
+def assemble_likelihood_gradient(a, alpha, x, h_z, h_alpha, logquad, invquad, converged=True):
+    """The host side of MI355XSolver.log_marginal_likelihood_gradient, in float64 and without a device: from the data a
+    (M, E), alpha = A^-1 a (M, E), the probes' solves x_p = A^-1 z_p (M, P), the products h_z[:, p, d] = (d_d A) z_p
+    (M, P, D) and h_alpha[:, e, d] = (d_d A) alpha_e (M, E, D) with d_d A = dA / d log l_d, and the per-probe quadratures
+    logquad_p = z_p' log(A) z_p, invquad_p = z_p' A^-1 z_p (P):
+        tr(A^-1 d_d A) ~ 1/P sum_p x_p' (d_d A) z_p              quad_d = sum_e alpha_e' (d_d A) alpha_e
+        dL/d log l_d  = 1/2 quad_d - E/2 tr(A^-1 d_d A)           dL/d ridge = 1/2 sum_e alpha_e' alpha_e - E/2 tr A^-1
+    Standard errors: E/2 x the sample standard deviation of the per-probe terms / sqrt(P)."""
+    a, alpha, x = (np.asarray(v, dtype=np.float64) for v in (a, alpha, x))
+    h_z, h_alpha = np.asarray(h_z, dtype=np.float64), np.asarray(h_alpha, dtype=np.float64)
+    logquad, invquad = np.asarray(logquad, dtype=np.float64), np.asarray(invquad, dtype=np.float64)
+    M, E = a.shape
+    P = x.shape[1]
+    root = np.sqrt(P)
+    terms = np.einsum("mp,mpd->pd", x, h_z)           # x_p' (d_d A) z_p
+    quad = np.einsum("me,med->d", alpha, h_alpha)     # sum_e alpha_e' (d_d A) alpha_e
+    return MarginalLikelihoodGradient(
+        value=_log_likelihood(a, alpha, float(np.mean(logquad)), M),
+        value_stderr=0.5 * E * float(np.std(logquad, ddof=1) / root),
+        d_log_lengthscale=0.5 * quad - 0.5 * E * np.mean(terms, axis=0),
+        d_log_lengthscale_stderr=0.5 * E * np.std(terms, axis=0, ddof=1) / root,
+        d_ridge=0.5 * float(np.sum(alpha * alpha)) - 0.5 * E * float(np.mean(invquad)),
+        d_ridge_stderr=0.5 * E * float(np.std(invquad, ddof=1) / root),
+        converged=bool(converged))
 
 
 class MI355XSolver(BaseSolver):
@@ -662,7 +739,7 @@ class MI355XSolver(BaseSolver):
         probes = int(probes)
         if probes < 2:
             raise ValueError("log_determinant needs at least 2 probes (the standard error is a sample deviation)")
-        z = np.where(np.random.RandomState(seed).rand(self.M, probes) < 0.5, -1.0, 1.0)
+        z = _rademacher_probes(self.M, probes, seed)
         self._apply_diagonal()
         out = self._ctx.lanczos_quadrature(self._device_kernel_fn, np.ascontiguousarray(z, dtype=self._host_dtype),
                                            self.rtol if rtol is None else rtol, self.maxit if maxit is None else maxit)
@@ -686,9 +763,58 @@ class MI355XSolver(BaseSolver):
         if not logdet.converged:
             raise RuntimeError("log_marginal_likelihood(): the Lanczos quadrature did not converge")
         a = np.asarray(self._a, dtype=np.float64)
-        E = a.shape[1]
-        value = -0.5 * float(np.sum(a * self.res)) - 0.5 * E * logdet.value - 0.5 * E * self.M * np.log(2.0 * np.pi)
-        return value, 0.5 * E * logdet.stderr
+        return _log_likelihood(a, self.res, logdet.value, self.M), 0.5 * a.shape[1] * logdet.stderr
+
+    def log_marginal_likelihood_gradient(self, probes=32, seed=0):
+        """log_marginal_likelihood(probes, seed) with its gradient in the hyperparameters, after query(): a namedtuple
+        (value, value_stderr, d_log_lengthscale (D,), d_log_lengthscale_stderr (D,), d_ridge, d_ridge_stderr, converged).
+        ``d_log_lengthscale[d]`` is dL / d log l_d for the covariance k(x / l, y / l) at l = 1: the length scales are the
+        caller's scaling of the points, one per axis (ARD); the derivative in ONE isotropic length scale is
+        ``d_log_lengthscale.sum()``.  ``d_ridge`` is the derivative in a uniform shift of the diagonal, also when
+        ``ridge`` is one value per point.  With alpha = A^-1 a the last query()'s result:
+            dL/d log l_d = 1/2 sum_e alpha_e' (d_d A) alpha_e - E/2 tr(A^-1 d_d A)
+            dL/d ridge   = 1/2 sum_e alpha_e' alpha_e         - E/2 tr A^-1
+        The traces are estimated on the Rademacher probes z_p of log_determinant(probes, seed), from ONE Lanczos
+        quadrature that also returns x_p = A^-1 z_p: tr(A^-1 d_d A) ~ mean_p x_p' (d_d A) z_p, and (d_d A) [z | alpha]
+        from kmvp_<kernel>_dscale in blocks of four columns.  ``value`` is log_marginal_likelihood(probes, seed)'s, bit for
+        bit; the standard errors are the trace estimates' share (E/2 x sample deviation / sqrt(probes)), the quadratic
+        terms are exact to the solve's rtol.  Every rank of a sharded solver returns the same bits."""
+        pieces = self._likelihood_gradient_pieces(probes, seed)
+        return assemble_likelihood_gradient(self._a, self.res, **pieces)
+
+    def _likelihood_gradient_pieces(self, probes, seed):
+        """The device's share of log_marginal_likelihood_gradient(): what assemble_likelihood_gradient() takes beside a and
+        alpha, as a dict."""
+        what = (f"kernel {self.kernel}" if self.method != "cg" or self._dot else "refine" if self.refine else
+                "normalize_rows" if self.normalize_rows else None)
+        if what:
+            raise NotImplementedError(f"MI355XSolver.log_marginal_likelihood_gradient doesn't support {what}.")
+        if getattr(self, "res", None) is None or getattr(self, "_a", None) is None:
+            raise RuntimeError("log_marginal_likelihood_gradient() needs prepare_query() and query() first")
+        if self.D > GRADIENT_MAX_D:
+            raise NotImplementedError(f"MI355XSolver.log_marginal_likelihood_gradient doesn't support D = {self.D} > {GRADIENT_MAX_D}.")
+        if not self.converged:
+            raise RuntimeError("log_marginal_likelihood_gradient(): the last solve did not converge "
+                               f"(relative residual {self.residual:g})")
+        probes = int(probes)
+        if probes < 2:
+            raise ValueError("log_marginal_likelihood_gradient needs at least 2 probes (the standard error is a sample deviation)")
+        z = np.ascontiguousarray(_rademacher_probes(self.M, probes, seed), dtype=self._host_dtype)  # +-1: exact
+        self._apply_diagonal()
+        out = self._ctx.lanczos_quadrature(self._device_kernel_fn, z, self.rtol, self.maxit, want_x=True)
+        if not out["converged"]:
+            raise RuntimeError("log_marginal_likelihood_gradient(): the Lanczos quadrature did not converge")
+        # (d_d A) [z_1 .. z_P, alpha_1 .. alpha_E]: the operator's own context, a rank's signal its slice of the replicated
+        # columns (as the solver's operator), summed over the ranks by the product's all-reduce
+        cols = np.concatenate([z, np.asarray(self.res, dtype=self._host_dtype)], axis=1)
+        lo, hi = self._shard
+        h = np.empty((self.M, cols.shape[1], self.D), dtype=np.float64)
+        for c0 in range(0, cols.shape[1], GRADIENT_MAX_E):
+            block = np.ascontiguousarray(cols[lo:hi, c0:c0 + GRADIENT_MAX_E])
+            self._ctx.set_signal(block)
+            self._ctx.run_dscale(self._device_kernel_fn)
+            h[:, c0:c0 + block.shape[1], :] = self._ctx.get_result(self.M, block.shape[1] * self.D).reshape(self.M, -1, self.D)
+        return dict(x=out["x"], h_z=h[:, :probes], h_alpha=h[:, probes:], logquad=out["logquad"], invquad=out["invquad"])
 
     def get_memory_usage(self):
         return 0.0 if self._ctx is None else self._ctx.device_bytes / 1024

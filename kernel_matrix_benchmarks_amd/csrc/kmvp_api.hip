@@ -184,6 +184,10 @@ int kmvp_absexp_grad(kmvp_ctx* c) { return run_gradient(c, K_ABSEXP); }
 int kmvp_invdist_grad(kmvp_ctx* c) { return run_gradient(c, K_INVDIST); }
 int kmvp_matern32_grad(kmvp_ctx* c) { return run_gradient(c, K_MATERN32); }
 int kmvp_matern52_grad(kmvp_ctx* c) { return run_gradient(c, K_MATERN52); }
+int kmvp_gaussian_dscale(kmvp_ctx* c) { return run_dscale(c, K_GAUSSIAN); }
+int kmvp_absexp_dscale(kmvp_ctx* c) { return run_dscale(c, K_ABSEXP); }
+int kmvp_matern32_dscale(kmvp_ctx* c) { return run_dscale(c, K_MATERN32); }
+int kmvp_matern52_dscale(kmvp_ctx* c) { return run_dscale(c, K_MATERN52); }
 int kmvp_gaussian_logsumexp(kmvp_ctx* c) { return run_logsumexp(c, K_GAUSSIAN); }
 int kmvp_absexp_logsumexp(kmvp_ctx* c) { return run_logsumexp(c, K_ABSEXP); }
 int kmvp_gaussian_logsumexp_grad(kmvp_ctx* c) { return run_logsumexp_grad(c, K_GAUSSIAN); }

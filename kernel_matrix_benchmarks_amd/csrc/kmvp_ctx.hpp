@@ -204,6 +204,7 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise);
 int measure_clouds(kmvp_ctx* c, int dtype, int64_t M, int64_t N, int D);
 int prepare_points(kmvp_ctx* c, int kernel);  // kmvp_fit: whatever can be built from the points alone
 int run_gradient(kmvp_ctx* c, int kernel);    // kmvp_<kernel>_grad: (N, E D) into c->out, synchronous
+int run_dscale(kmvp_ctx* c, int kernel);      // kmvp_<kernel>_dscale: (N, E D) into c->out, synchronous
 int run_logsumexp(kmvp_ctx* c, int kernel);   // kmvp_<kernel>_logsumexp: (N, E) into c->out, synchronous
 int run_logsumexp_grad(kmvp_ctx* c, int kernel);  // kmvp_<kernel>_logsumexp_grad: (N, E D) into c->out, synchronous
 

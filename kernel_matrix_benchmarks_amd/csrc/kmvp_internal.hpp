@@ -61,6 +61,17 @@ KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_matern52_f32, float)
 KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_matern32_f64, double)
 KMVP_DECLARE_LOWD_GRAD(launch_lowd_grad_matern52_f64, double)
 
+// Derivative in the logarithm of a per-axis length scale (kmvp_lowd_dscale.hpp; kmvp_lowd_dscale_inst.hip): the
+// gradient's signature, shapes and partial sums; no 1/r.
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_dscale_gaussian_f32, float)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_dscale_absexp_f32, float)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_dscale_gaussian_f64, double)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_dscale_absexp_f64, double)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_dscale_matern32_f32, float)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_dscale_matern52_f32, float)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_dscale_matern32_f64, double)
+KMVP_DECLARE_LOWD_GRAD(launch_lowd_dscale_matern52_f64, double)
+
 // Log-sum-exp reduction (kmvp_lowd_lse.hpp; kmvp_lowd_lse_inst.hip, one unit per kernel x precision): the Gaussian and
 // exp(-r), D <= LOWD_MAX_D, E <= LOWD_MAX_E, sig SIG_PRODUCT or SIG_DENSITY; hipErrorInvalidValue otherwise.
 // args.part: [segments][2 NC][n_pad] -- NC columns of sums, then NC columns of exponents.

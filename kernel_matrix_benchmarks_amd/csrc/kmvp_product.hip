@@ -567,9 +567,32 @@ hipError_t launch_lowd_grad(int kernel, int D, int E, int sig, const LowdArgs<do
     default: return hipErrorInvalidValue;
   }
 }
+// Its sibling in the logarithm of a per-axis length scale (kmvp_lowd_dscale.hpp): lowd_dscale_kernel, the same arguments,
+// the same E D columns; no 1/r.
+hipError_t launch_lowd_dscale(int kernel, int D, int E, int sig, const LowdArgs<float>& args, dim3 grid, hipStream_t s,
+                              const char** name) {
+  switch (kernel) {
+    case K_GAUSSIAN: return launch_lowd_dscale_gaussian_f32(D, E, sig, args, grid, s, name);
+    case K_ABSEXP: return launch_lowd_dscale_absexp_f32(D, E, sig, args, grid, s, name);
+    case K_MATERN32: return launch_lowd_dscale_matern32_f32(D, E, sig, args, grid, s, name);
+    case K_MATERN52: return launch_lowd_dscale_matern52_f32(D, E, sig, args, grid, s, name);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t launch_lowd_dscale(int kernel, int D, int E, int sig, const LowdArgs<double>& args, dim3 grid, hipStream_t s,
+                              const char** name) {
+  switch (kernel) {
+    case K_GAUSSIAN: return launch_lowd_dscale_gaussian_f64(D, E, sig, args, grid, s, name);
+    case K_ABSEXP: return launch_lowd_dscale_absexp_f64(D, E, sig, args, grid, s, name);
+    case K_MATERN32: return launch_lowd_dscale_matern32_f64(D, E, sig, args, grid, s, name);
+    case K_MATERN52: return launch_lowd_dscale_matern52_f64(D, E, sig, args, grid, s, name);
+    default: return hipErrorInvalidValue;
+  }
+}
 
+// dscale: lowd_dscale_kernel in lowd_grad_kernel's place (run_dscale), everything else is shared
 template <typename real>
-int run_gradient_t(kmvp_ctx* c, int kernel, int sig) {
+int run_gradient_t(kmvp_ctx* c, int kernel, int sig, bool dscale) {
   const int D = c->D;
   const int E = sig == SIG_DENSITY ? 1 : c->E;
   const int NC = E * D;  // columns of the result: e D + d
@@ -581,7 +604,7 @@ int run_gradient_t(kmvp_ctx* c, int kernel, int sig) {
   LowdArgs<real> a = lowd_geometry<real>(c, 1, R, NC);
 
   HIP_TRY(c, mark(c, 0));
-  // the product's layouts under the product's key: whichever of the two runs first on these points and this signal packs
+  // the product's layouts under the product's key: whichever of them runs first on these points and this signal packs
   const PackKey key = {LAYOUT_LOWD, kernel, 1};
   if (points_stale(c, key)) {
     if ((rc = ensure(c, c->xs, (size_t)D * a.n_pad * sizeof(real)))) return rc;
@@ -604,7 +627,8 @@ int run_gradient_t(kmvp_ctx* c, int kernel, int sig) {
   const int64_t nblocks = (int64_t)a.tile_blocks * a.segments;
   if (nblocks > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
   HIP_TRY(c, mark(c, 0));
-  HIP_TRY(c, launch_lowd_grad(kernel, D, E, sig, a, dim3((unsigned)nblocks), c->stream, &c->last_kernel_name));
+  HIP_TRY(c, dscale ? launch_lowd_dscale(kernel, D, E, sig, a, dim3((unsigned)nblocks), c->stream, &c->last_kernel_name)
+                    : launch_lowd_grad(kernel, D, E, sig, a, dim3((unsigned)nblocks), c->stream, &c->last_kernel_name));
   HIP_TRY(c, mark(c, 1));
   return reduce_and_finish(c, a.segments, NC, N, a.n_pad, NC, SIG_PRODUCT);
 }
@@ -2208,7 +2232,9 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
 
 // kmvp_<kernel>_grad: G[i, e, :] = sum_j w(s_ij) (x_i - y_j) b[j, e], left as (N, E D) in c->out.  Linear in the sources,
 // so shards, the exchange and the empty cases go through the product's tail with E D plain columns.
-int run_gradient(kmvp_ctx* c, int kernel) {
+// kmvp_<kernel>_dscale: H[i, e, d] = sum_j -w(s_ij) (x_{i,d} - y_{j,d})^2 b[j, e], the same shape, the same tail, the same
+// refusals and empty cases: one driver, `what` names the entry point in its messages.
+static int run_target_columns(kmvp_ctx* c, int kernel, const std::string& what, bool dscale) {
   if (!c) return KMVP_E_INVALID;
   c->note.clear();
   if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
@@ -2219,13 +2245,13 @@ int run_gradient(kmvp_ctx* c, int kernel) {
                 "the sources are a shard (M < M_total) but no multi-rank communicator is attached: call kmvp_comm_init, "
                 "or set option partial_shard = 1 to get this shard's partial sums on purpose");
   if (c->dtype == KMVP_BF16)
-    return fail(c, KMVP_E_UNSUPPORTED, "gradient: built for float32 and float64 contexts, not for bfloat16");
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": built for float32 and float64 contexts, not for bfloat16");
   const int E = c->density ? 1 : c->E;
   if (c->D > LOWD_MAX_D)
-    return fail(c, KMVP_E_UNSUPPORTED, "gradient: D = " + std::to_string(c->D) + " is beyond the kernels' D <= " +
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": D = " + std::to_string(c->D) + " is beyond the kernels' D <= " +
                                            std::to_string(LOWD_MAX_D));
   if (E > LOWD_MAX_E)
-    return fail(c, KMVP_E_UNSUPPORTED, "gradient: E = " + std::to_string(E) + " signal columns are beyond the kernels' E <= " +
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": E = " + std::to_string(E) + " signal columns are beyond the kernels' E <= " +
                                            std::to_string(LOWD_MAX_E) + " (run it per block of columns)");
   const int64_t NC = (int64_t)E * c->D;
   if (c->N == 0 || c->M == 0) {
@@ -2251,8 +2277,10 @@ int run_gradient(kmvp_ctx* c, int kernel) {
     return KMVP_OK;
   }
   const int sig = c->density ? SIG_DENSITY : SIG_PRODUCT;
-  return c->dtype == KMVP_F64 ? run_gradient_t<double>(c, kernel, sig) : run_gradient_t<float>(c, kernel, sig);
+  return c->dtype == KMVP_F64 ? run_gradient_t<double>(c, kernel, sig, dscale) : run_gradient_t<float>(c, kernel, sig, dscale);
 }
+int run_gradient(kmvp_ctx* c, int kernel) { return run_target_columns(c, kernel, "gradient", false); }
+int run_dscale(kmvp_ctx* c, int kernel) { return run_target_columns(c, kernel, "length-scale derivative", true); }
 
 // kmvp_<kernel>_logsumexp: L[i, e] = log sum_j exp(l(x_i, y_j) + c[j, e]) with the signal read as log-weights, left as
 // (N, E) in c->out.  Not linear in the sources: shards merge as (sum, exponent) pairs (finish_lse), an empty slice owes
