@@ -267,6 +267,46 @@ int kmvp_absexp_logsumexp(kmvp_ctx* ctx);
 int kmvp_gaussian_logsumexp_grad(kmvp_ctx* ctx);
 int kmvp_absexp_logsumexp_grad(kmvp_ctx* ctx);
 
+/* Brute-force K nearest neighbours (an extension: no reference method stands behind it -- the third reduction over the
+ * sources next to the sum and the log-sum-exp, KeOps' argKmin, and the eps -> 0 limit of the log-sum-exp's soft-min: the
+ * assignment step of k-means and mean-shift, Chamfer and Hausdorff distances, the k-NN distance of an adaptive bandwidth or
+ * a median heuristic, neighbour sets of Vecchia / nearest-neighbour Gaussian processes, a k-NN graph).  For every target
+ * x_i the K sources with the smallest squared distance s = |x_i - y_j|^2, never forming the N x M matrix:
+ *     out_idx[i, k]    GLOBAL index of the k-th nearest source (j_offset + position in y), int64
+ *     out_sqdist[i, k] its squared distance, float64
+ * both caller-owned, (N, K) row-major, written during the call (synchronous).  Neighbours come nearest first; equal
+ * distances come in ascending index.  exclude_self != 0 leaves source j == i out of row i (same_points: a k-NN graph
+ * without loops).  It is exact and costs the pair loop nothing: K + 1 candidates are collected, and the one with j == i
+ * is dropped if it is there, the last one otherwise -- right also when more than K + 1 sources coincide with the target
+ * (the K + 1 candidates are then all at distance 0 with indices below i).  Hence K <= 16, and K <= 15 with exclude_self.
+ * Conventions
+ *  - s is the family's difference form in the working precision (one subtraction, one square, D - 1 fmas), and
+ *    out_sqdist is that very value -- the one the kernel compared -- widened to float64.
+ *  - fewer than K qualifying sources (M == 0 included): the trailing entries are idx = -1, sqdist = +inf.  N == 0
+ *    writes nothing and returns KMVP_OK.
+ *  - a source with a NaN coordinate and a pair whose squared distance is not finite in the working precision (float32:
+ *    it overflowed) never qualify: the family's rule that a pair at infinite distance contributes nothing.
+ *  - a NaN target coordinate gives that row idx = -1, sqdist = NaN in all K entries, and touches no other row.
+ *  - bitwise reproducible run to run, and independent of "segments".
+ *  - kmvp_set_signal is neither needed nor consulted, and kmvp_get_result is not involved.  A product, gradient or
+ *    log-sum-exp on the same context before and after the call returns the same bits as without it (the call goes through
+ *    the context's pack bookkeeping with the density layout of the difference form).
+ * float32 and float64 contexts, D <= 8 (lowd_knn_kernel: per-lane sorted lists of capacity 1, 4 or 16 in registers, the
+ * smallest that holds K [+ 1]; csrc/kmvp_lowd_knn.hpp, merge: csrc/kmvp_knn_merge.hpp).  KMVP_E_UNSUPPORTED with a message
+ * for bfloat16 contexts, D > 8, K > 16 (15 with exclude_self) and an explicit "fast_sqdists" of 1 .. 4.  KMVP_E_INVALID for
+ * K < 1, a NULL output with N > 0, no points set, and exclude_self when the targets are not the sources (with a source
+ * shard it is allowed when "same_points_global" is set and x is the full cloud).
+ * kmvp_last_kernel_name is "lowd_knn_kernel", kmvp_last_dispatch_note is "", kmvp_last_kernel_ms / kmvp_last_total_ms as
+ * for a product.  Honours "segments" (every segment starts from an empty list, which the lists of capacity 16 pay for:
+ * the automatic choice gives them only the segments two workgroups per CU ask for, none shorter than 4096 sources; the
+ * shorter lists take the product's rule), "chunk" (no meaning here: accepted, ignored) and
+ * "partial_shard": a slice returns its own K with global indices, and the caller merges shards by (sqdist, idx).
+ * With a communicator attached every rank places its [2 K'][N] candidates (K' = K, + 1 with exclude_self) into slot
+ * `rank` of a zero-filled [world][2 K'][N] buffer; ONE all-reduce(sum) -- adding zeros is exact -- hands every rank all
+ * lists, which it merges like segments: every rank returns the same bits, also a rank whose source slice is empty.  That
+ * buffer is world * 2 K' * N doubles on every rank. */
+int kmvp_nearest(kmvp_ctx* ctx, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);
+
 /* BaseProduct.get_result (base.py:107-116): (N,E) float64 row-major. */
 int kmvp_get_result(kmvp_ctx* ctx, double* out, int64_t out_len);
 

@@ -54,6 +54,7 @@ SYMBOLS = [
     ("kmvp_absexp_logsumexp", _c.c_int, [_c.c_void_p]),
     ("kmvp_gaussian_logsumexp_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_absexp_logsumexp_grad", _c.c_int, [_c.c_void_p]),
+    ("kmvp_nearest", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     ("kmvp_get_result", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("kmvp_gaussian_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
@@ -259,6 +260,17 @@ class Context:
         if entry is None:
             raise NotImplementedError(f"no log-sum-exp gradient for kernel {kernel}")
         self._check(entry(self._ctx))
+
+    def run_nearest(self, K, exclude_self=False):
+        """The K nearest sources of every target (include/kmvp.h kmvp_nearest): (idx int64 (N, K), sqdist float64 (N, K)),
+        nearest first, ties in ascending index, global indices; (-1, +inf) where fewer than K sources qualify."""
+        K = int(K)
+        N = int(getattr(self, "N", 0))
+        # the library writes N * K elements through each pointer: the arrays are sized here, from the points it was given
+        idx = np.empty((N, max(K, 0)), dtype=np.int64)
+        sqdist = np.empty((N, max(K, 0)), dtype=np.float64)
+        self._check(self._lib.kmvp_nearest(self._ctx, K, 1 if exclude_self else 0, idx.ctypes.data, sqdist.ctypes.data))
+        return idx, sqdist
 
     def get_result(self, N, E):
         out = np.empty((N, E), dtype=np.float64)

@@ -60,6 +60,8 @@ SCALE_DERIVATIVE_KERNELS = ("gaussian", "absolute-exponential", "matern-3/2", "m
 # lowd_lse_kernel: the log-sum-exp reduction is built for these kernels, at the gradient's shapes
 LOGSUMEXP_KERNELS = ("gaussian", "absolute-exponential")
 LOGSUMEXP_MAX_D, LOGSUMEXP_MAX_E = 8, 4
+# lowd_knn_kernel: K nearest neighbours, at the gradient's dimensions; K + 1 candidates are collected with exclude_self
+NEAREST_MAX_D, NEAREST_MAX_K = 8, 16
 EXPDOT_NATIVE_MAX_D = 64
 EXPDOT_NATIVE_MAX_D_BF16 = 141  # 16 * 9 k-steps - 3 operand columns (kmvp_mfma.hpp MFMA_DOT_AUG)
 # largest spread max_j |y_j|^2/2 - min_j |y_j|^2/2 the identity route accepts: the smallest weight is exp(-spread);
@@ -379,6 +381,39 @@ class MI355XProduct(BaseProduct):
     def get_logsumexp_gradient(self):
         """(N, E, D) float64, C-contiguous: the result of the last query_logsumexp_gradient()."""
         return np.ascontiguousarray(self._ctx.get_result(self.N, self.E * self.D).reshape(self.N, self.E, self.D))
+
+    def query_nearest(self, k, exclude_self=False):
+        """The k sources nearest to every target and their squared distances (include/kmvp.h kmvp_nearest): nearest first,
+        ties in ascending index, indices into source_points as given to prepare_data(); where fewer than k sources qualify
+        the tail is (-1, +inf).  exclude_self (same_points only) leaves point i out of its own row.  Needs prepare_data()
+        only: no signal is read, and the plugin's kernel function does not enter.  The timed part, like query().
+        Synchronous; a sharded plugin merges the ranks' candidates, and every rank gets the same result."""
+        k = int(k)
+        what = None
+        if self._dtype_code == _lib.KMVP_BF16:
+            what = "precision='bfloat16' (float16, float32 and float64 only)"
+        elif self._ctx is None:
+            raise RuntimeError("query_nearest() needs prepare_data() first")
+        elif self._dot and not self._dot_native:
+            what = "kernel='exp-dot' through the Gaussian identity (the context holds rescaled points)"
+        elif self.D > NEAREST_MAX_D:
+            what = f"D = {self.D} > {NEAREST_MAX_D}"
+        elif k + bool(exclude_self) > NEAREST_MAX_K:
+            what = f"k = {k} > {NEAREST_MAX_K - bool(exclude_self)}" + (" with exclude_self" if exclude_self else "")
+        elif self.fast_sqdists not in (None, False):
+            what = f"fast_sqdists={self.fast_sqdists!r} (the difference form only: None or False)"
+        elif self._order is not None:
+            what = ("a sharded float32 Gaussian plugin, whose sources were dealt to the ranks in cell order: ties would no "
+                    "longer resolve towards the smaller index of the caller's order (use another kernel= for the neighbour query)")
+        if what is not None:
+            raise NotImplementedError(f"MI355XProduct.query_nearest doesn't support {what}.")
+        if exclude_self and not self.same_points:
+            raise ValueError("exclude_self needs same_points=True")
+        self._nearest = self._ctx.run_nearest(k, exclude_self)
+
+    def get_nearest(self):
+        """(idx (N, k) int64, sqdist (N, k) float64), C-contiguous: the result of the last query_nearest()."""
+        return self._nearest
 
     # -- bookkeeping ---------------------------------------------------------------
     def set_query_arguments(self, **kwargs):

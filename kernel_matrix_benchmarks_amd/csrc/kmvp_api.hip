@@ -89,7 +89,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
-                    &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
+                    &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
                     &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     release(*b);
@@ -192,6 +192,9 @@ int kmvp_gaussian_logsumexp(kmvp_ctx* c) { return run_logsumexp(c, K_GAUSSIAN); 
 int kmvp_absexp_logsumexp(kmvp_ctx* c) { return run_logsumexp(c, K_ABSEXP); }
 int kmvp_gaussian_logsumexp_grad(kmvp_ctx* c) { return run_logsumexp_grad(c, K_GAUSSIAN); }
 int kmvp_absexp_logsumexp_grad(kmvp_ctx* c) { return run_logsumexp_grad(c, K_ABSEXP); }
+int kmvp_nearest(kmvp_ctx* c, int K, int exclude_self, int64_t* out_idx, double* out_sqdist) {
+  return run_nearest(c, K, exclude_self, out_idx, out_sqdist);
+}
 
 int kmvp_get_result(kmvp_ctx* c, double* out, int64_t out_len) {
   if (!c) return KMVP_E_INVALID;
@@ -402,7 +405,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   if (!c) return 0;
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
-                          &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
+                          &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
                     &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     t += b->cap;

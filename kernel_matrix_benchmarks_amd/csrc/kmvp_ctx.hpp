@@ -129,6 +129,7 @@ struct kmvp_ctx {
                                 // (log-sum-exp: kshift and xchgk per (column, target); xchgk holds the rank's own and the common ones)
   DevBuf kflag;                 // exp(<x,y>): set when a row's exponent reached the shift's clamp (check_shift_range_kernel)
   DevBuf scratch;               // CG vectors / dot products
+  DevBuf knn;                   // kmvp_nearest: (N, K) int64 indices, then (N, K) float64 squared distances
   DevBuf sdiag;                 // solvers: the effective diagonal ridge + d_i, N doubles (kmvp_set_solver_diagonal)
   // Sinkhorn (kmvp_sinkhorn.hip): layouts of its own for both directions -- target image of x with records of y, target
   // image of y with records of x (the record's signal slot carries potential + log-weight) -- and the fp64 state
@@ -207,6 +208,7 @@ int run_gradient(kmvp_ctx* c, int kernel);    // kmvp_<kernel>_grad: (N, E D) in
 int run_dscale(kmvp_ctx* c, int kernel);      // kmvp_<kernel>_dscale: (N, E D) into c->out, synchronous
 int run_logsumexp(kmvp_ctx* c, int kernel);   // kmvp_<kernel>_logsumexp: (N, E) into c->out, synchronous
 int run_logsumexp_grad(kmvp_ctx* c, int kernel);  // kmvp_<kernel>_logsumexp_grad: (N, E D) into c->out, synchronous
+int run_nearest(kmvp_ctx* c, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);  // kmvp_nearest: synchronous, into the caller's arrays
 
 // kmvp_solvers.hip
 int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit, double* out_b,

@@ -151,6 +151,38 @@ static __global__ void lse_reduce_kernel(const double* __restrict__ part, double
   kmin[q] = K;
 }
 
+// K nearest neighbours (kmvp_lowd_knn.hpp; kmvp_lowd_knn_inst.hip, one unit per precision): D <= LOWD_MAX_D, list capacity
+// KT = 1, 4 or 16; hipErrorInvalidValue otherwise.  args.part: [segments][2 KT][n_pad] -- KT rows of squared distances, then
+// KT rows of global source indices.
+hipError_t launch_lowd_knn_f32(int D, int KT, const LowdArgs<float>& args, dim3 grid, hipStream_t stream, const char** kernel_name);
+hipError_t launch_lowd_knn_f64(int D, int KT, const LowdArgs<double>& args, dim3 grid, hipStream_t stream, const char** kernel_name);
+inline hipError_t launch_lowd_knn(int D, int KT, const LowdArgs<float>& args, dim3 grid, hipStream_t s, const char** name) {
+  return launch_lowd_knn_f32(D, KT, args, grid, s, name);
+}
+inline hipError_t launch_lowd_knn(int D, int KT, const LowdArgs<double>& args, dim3 grid, hipStream_t s, const char** name) {
+  return launch_lowd_knn_f64(D, KT, args, grid, s, name);
+}
+// Smallest instantiated list capacity that holds `need` candidates (need <= 16).
+inline int knn_capacity(int need) { return need <= 1 ? 1 : need <= 4 ? 4 : 16; }
+// Source segments of a nearest-neighbour launch; 0: the product's own rule (choose_segments).  Every segment starts from
+// an empty list, and a wave enters the insertion code whenever any of its 64 lanes improves -- at KT = 16 almost every
+// batch of a segment's first ~4000 sources -- so a short segment costs far more here than in the product, whose segments
+// exist for L2 residency and for many rounds of workgroups.  Measured at N = M = 2e5, D = 3, float32 (LAB_NOTES.md
+// section 21): KT = 16 takes 23.5 / 24.5 / 27.6 / 30.5 / 40.8 / 54.8 ms with 1 / 2 / 3 / 4 / 8 / 16 segments, KT = 1 takes
+// 13.1 / 11.0 / 10.3 / 10.1 / 9.5 / 9.3 ms.  Hence: the short lists, whose insertion costs next to nothing, take the
+// product's rule; KT = 16 takes only as many segments as two workgroups per CU ask for (none where the target tiles alone
+// cover the device), none shorter than 4096 sources, within the product's bound on the partial-result buffer.
+// opt_segments > 0 (the "segments" option) holds.
+constexpr int64_t KNN_MIN_SEGMENT = 4096;
+inline int knn_segments(int opt_segments, int KT, int64_t tile_blocks, int64_t m_pad, int64_t n_pad) {
+  if (opt_segments > 0) return opt_segments;
+  if (KT <= 4) return 0;
+  const int64_t for_parallelism = (512 + tile_blocks - 1) / tile_blocks;
+  const int64_t cap_len = std::max<int64_t>(1, m_pad / KNN_MIN_SEGMENT);
+  const int64_t cap_mem = std::max<int64_t>(1, (int64_t)(4e9 / (2.0 * KT * n_pad * 8)));
+  return (int)std::max<int64_t>(1, std::min(for_parallelism, std::min(cap_len, cap_mem)));
+}
+
 // Gradient of the log-sum-exp with respect to the targets (kmvp_lowd_lse_grad.hpp; kmvp_lowd_lse_grad_inst.hip, one unit
 // per kernel x precision): the same shapes.  args.part: [segments][(D + 2) NC][n_pad] -- row k NC + c holds sum k of
 // column c (k = 0: the denominator, k = 1 + d: component d of the numerator), rows (D + 1) NC + c the exponents.

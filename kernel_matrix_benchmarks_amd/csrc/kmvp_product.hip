@@ -13,6 +13,7 @@
 #include "kmvp_fastmm_pack.hpp"
 #include "kmvp_cfastmm_pack.hpp"
 #include "kmvp_mfma_pack.hpp"
+#include "kmvp_knn_merge.hpp"
 
 namespace kmvp {
 namespace {
@@ -2390,6 +2391,160 @@ int run_logsumexp_grad(kmvp_ctx* c, int kernel) {
   }
   const int sig = c->density ? SIG_DENSITY : SIG_PRODUCT;
   return c->dtype == KMVP_F64 ? run_logsumexp_grad_t<double>(c, kernel, sig) : run_logsumexp_grad_t<float>(c, kernel, sig);
+}
+
+// ---- K nearest neighbours (kmvp_lowd_knn.hpp, kmvp_knn_merge.hpp) ------------------------------------------------------
+// lowd_knn_kernel leaves KT sorted candidates per (segment, target): part[s][2 KT][n_pad].  knn_merge_kernel folds S lists
+// of one target into Kc = K (+ 1 with exclude_self) candidates in the canonical unpadded layout [2 Kc][N] -- the segments
+// first, then, sharded, the ranks' lists after ONE all-reduce; knn_finish_kernel drops the own index and writes (N, K).
+static __global__ void knn_merge_kernel(const double* __restrict__ lists, double* __restrict__ cand, int64_t n, int64_t list_stride,
+                                        int64_t elem_stride, int S, int KT, int Kc) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  knn_merge(lists + i, list_stride, elem_stride, S, KT, Kc, cand + i, cand + (int64_t)Kc * n + i, n);
+}
+
+static __global__ void knn_fill_kernel(double* __restrict__ cand, int64_t n, int Kc) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= 2 * (int64_t)Kc * n) return;
+  cand[q] = q < (int64_t)Kc * n ? (double)INFINITY : -1.0;
+}
+
+// cand [2 Kc][n] (modified in place by the exclude-self drop) -> idx (n, K) int64, sqdist (n, K) float64
+static __global__ void knn_finish_kernel(double* __restrict__ cand, int64_t* __restrict__ idx, double* __restrict__ sqdist,
+                                         int64_t n, int K, int exclude_self) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int Kc = K + (exclude_self ? 1 : 0);
+  double* s = cand + i;
+  double* j = cand + (int64_t)Kc * n + i;
+  if (exclude_self) knn_drop_self(s, j, n, Kc, i);
+  for (int k = 0; k < K; ++k) {
+    sqdist[i * K + k] = s[(int64_t)k * n];
+    idx[i * K + k] = (int64_t)j[(int64_t)k * n];
+  }
+}
+
+template <typename real>
+static int run_nearest_t(kmvp_ctx* c, int Kc) {
+  const int D = c->D;
+  const int64_t N = c->N, M = c->M;
+  const real* x_raw = (const real*)(c->same_points ? c->y_raw.p : c->x_raw.p);
+  int rc;
+  const int KT = knn_capacity(Kc);
+  const int R = (D + 3) / 4 * 4;  // density layout: no signal columns
+  const int64_t tile = 64 * (int64_t)WAVES_PER_BLOCK;
+  const int64_t n_pad0 = round_up(std::max<int64_t>(N, 1), tile), m_pad0 = round_up(std::max<int64_t>(M, 1), LOWD_BATCH);
+  LowdArgs<real> a = kmvp::lowd_geometry<real>(N, M, knn_segments(c->opt_segments, KT, n_pad0 / tile, m_pad0, n_pad0),
+                                              c->opt_chunk, c->j_offset, c->m_total, 1, R, 2 * KT);
+  if (a.seg_len > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "nearest: a source segment of 2^31 records or more (raise \"segments\")");
+
+  // the product's layouts in the density form through the context's own bookkeeping (no kernel constant enters them):
+  // a product with a signal before or after repacks its records, as it does after a density product
+  const PackKey key = {LAYOUT_LOWD, K_GAUSSIAN, 1};
+  if (points_stale(c, key)) {
+    if ((rc = ensure(c, c->xs, (size_t)D * a.n_pad * sizeof(real)))) return rc;
+    hipLaunchKernelGGL((pack_targets_kernel<real>), dim3(blocks_for(a.n_pad)), dim3(256), 0, c->stream, x_raw,
+                       (real*)c->xs.p, N, a.n_pad, D, (real)1);
+  }
+  if (points_stale(c, key) || c->packed_sig != SIG_DENSITY) {
+    if ((rc = ensure(c, c->rec, (size_t)(a.m_pad + LOWD_BATCH) * R * sizeof(real)))) return rc;
+    hipLaunchKernelGGL((pack_sources_kernel<real>), dim3(blocks_for(a.m_pad + LOWD_BATCH)), dim3(256), 0, c->stream,
+                       (const real*)c->y_raw.p, (const real*)nullptr, (real*)c->rec.p, M, a.m_pad + LOWD_BATCH, D, 0, R, (real)1);
+  }
+  HIP_TRY(c, hipGetLastError());
+  record_packed(c, key, SIG_DENSITY);
+
+  if ((rc = ensure(c, c->part, (size_t)a.segments * 2 * KT * a.n_pad * sizeof(double)))) return rc;
+  a.xs = (const real*)c->xs.p;
+  a.rec = (const real*)c->rec.p;
+  a.part = (double*)c->part.p;
+  const int64_t nblocks = (int64_t)a.tile_blocks * a.segments;
+  if (nblocks > 0x7fffffff) return fail(c, KMVP_E_UNSUPPORTED, "launch grid too large");
+  HIP_TRY(c, mark(c, 0));
+  HIP_TRY(c, launch_lowd_knn(D, KT, a, dim3((unsigned)nblocks), c->stream, &c->last_kernel_name));
+  HIP_TRY(c, mark(c, 1));
+  hipLaunchKernelGGL(knn_merge_kernel, dim3(blocks_for(N)), dim3(256), 0, c->stream, (const double*)c->part.p, (double*)c->sums.p,
+                     N, (int64_t)2 * KT * a.n_pad, a.n_pad, a.segments, KT, Kc);
+  HIP_TRY(c, hipGetLastError());
+  return KMVP_OK;
+}
+
+// kmvp_nearest: the K smallest squared distances of every target and their global source indices, into the caller's
+// arrays.  Not a sum over the sources: shards merge as candidate lists (one all-reduce that adds zeros to every slot but
+// the rank's own); an empty slice owes the other ranks the same collective with an all-pad slot.
+int run_nearest(kmvp_ctx* c, int K, int exclude_self, int64_t* out_idx, double* out_sqdist) {
+  if (!c) return KMVP_E_INVALID;
+  c->note.clear();
+  if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
+  if (K < 1) return fail(c, KMVP_E_INVALID, "nearest: K must be >= 1");
+  if (exclude_self && !c->same_points && !c->opt_same_global)
+    return fail(c, KMVP_E_INVALID, "nearest: exclude_self needs the targets to be the sources (same_points, or option "
+                                   "same_points_global = 1 when the sources are a shard and x is the full cloud)");
+  if (c->N > 0 && (!out_idx || !out_sqdist)) return fail(c, KMVP_E_INVALID, "nearest: a NULL output");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->M < c->m_total && !(c->exchanges() && c->world > 1) && !c->opt_partial)
+    return fail(c, KMVP_E_INVALID,
+                "the sources are a shard (M < M_total) but no multi-rank communicator is attached: call kmvp_comm_init, "
+                "or set option partial_shard = 1 to get this shard's own neighbours on purpose");
+  if (c->dtype == KMVP_BF16)
+    return fail(c, KMVP_E_UNSUPPORTED, "nearest: built for float32 and float64 contexts, not for bfloat16");
+  if (c->D > LOWD_MAX_D)
+    return fail(c, KMVP_E_UNSUPPORTED, "nearest: D = " + std::to_string(c->D) + " is beyond the kernels' D <= " +
+                                           std::to_string(LOWD_MAX_D));
+  const int Kc = K + (exclude_self ? 1 : 0);  // candidates collected per target
+  if (K > KNN_MAX_K || Kc > KNN_MAX_K)
+    return fail(c, KMVP_E_UNSUPPORTED, "nearest: K = " + std::to_string(K) + (exclude_self ? " with exclude_self" : "") +
+                                           " is beyond the lists' K <= 16 (15 with exclude_self)");
+  if (c->opt_fast >= 1)
+    return fail(c, KMVP_E_UNSUPPORTED, "nearest: fast_sqdists = " + std::to_string(c->opt_fast) +
+                                           " asks for a matrix-core form that is not built for it (-1 or 0: the difference form)");
+  const int64_t N = c->N;
+  c->last_kernel_ms = c->last_total_ms = c->last_allreduce_ms = 0.f;
+  c->last_kernel_name = "none";
+  if (N == 0) return KMVP_OK;
+
+  int rc;
+  const int64_t cnt = (int64_t)2 * Kc * N;  // one rank's candidates, [2 Kc][N]
+  if ((rc = ensure(c, c->sums, (size_t)cnt * sizeof(double)))) return rc;
+  HIP_TRY(c, mark(c, 0));
+  if (c->M == 0) {  // no source here: every list is empty
+    HIP_TRY(c, mark(c, 0));
+    hipLaunchKernelGGL(knn_fill_kernel, dim3(blocks_for(cnt)), dim3(256), 0, c->stream, (double*)c->sums.p, N, Kc);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, mark(c, 1));
+  } else if ((rc = c->dtype == KMVP_F64 ? run_nearest_t<double>(c, Kc) : run_nearest_t<float>(c, Kc))) {
+    return rc;
+  }
+  double* cand = (double*)c->sums.p;
+  if (c->exchanges()) {  // also with world == 1, as the product's tail
+    const int world = c->world;
+    if ((rc = ensure(c, c->xchg, (size_t)(world + 1) * cnt * sizeof(double)))) return rc;
+    double* slots = (double*)c->xchg.p;  // [world][2 Kc][N], then the merged [2 Kc][N]
+    HIP_TRY(c, hipMemsetAsync(slots, 0, (size_t)world * cnt * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(slots + (int64_t)c->rank * cnt, cand, (size_t)cnt * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, mark(c, 3));
+    if ((rc = exchange_f64(c, slots, (int64_t)world * cnt, KMVP_OP_SUM))) return rc;  // adding zeros is exact, also for inf, NaN, -1
+    HIP_TRY(c, mark(c, 4));
+    cand = slots + (int64_t)world * cnt;
+    hipLaunchKernelGGL(knn_merge_kernel, dim3(blocks_for(N)), dim3(256), 0, c->stream, (const double*)slots, cand, N, cnt, N,
+                       world, Kc, Kc);
+    HIP_TRY(c, hipGetLastError());
+  }
+  const size_t nk = (size_t)N * K;
+  if ((rc = ensure(c, c->knn, nk * (sizeof(int64_t) + sizeof(double))))) return rc;
+  int64_t* d_idx = (int64_t*)c->knn.p;
+  double* d_sq = (double*)(d_idx + nk);
+  hipLaunchKernelGGL(knn_finish_kernel, dim3(blocks_for(N)), dim3(256), 0, c->stream, cand, d_idx, d_sq, N, K, exclude_self ? 1 : 0);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out_idx, d_idx, nk * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out_sqdist, d_sq, nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_kernel_ms, c->ev[0], c->ev[1]));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
+  if (c->exchanges()) HIP_TRY(c, hipEventElapsedTime(&c->last_allreduce_ms, c->ev[3], c->ev[4]));
+  return KMVP_OK;
 }
 
 }  // namespace kmvp
