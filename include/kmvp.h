@@ -307,6 +307,49 @@ int kmvp_absexp_logsumexp_grad(kmvp_ctx* ctx);
  * buffer is world * 2 K' * N doubles on every rank. */
 int kmvp_nearest(kmvp_ctx* ctx, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);
 
+/* Lloyd's k-means, resident on the device (an extension: the solver on top of the arg-K-min at K = 1, as the Krylov
+ * solvers are on top of the product and Sinkhorn on top of the log-sum-exp).  Kernel-independent, like kmvp_nearest.  The
+ * points are the TARGETS of the context -- x (N,D), or the cloud itself when x_or_null == NULL; the context's sources and
+ * kmvp_set_signal are neither needed nor consulted.  weights_or_null: N doubles >= 0, NULL = every weight 1.
+ * centroids: (C,D) float64 row-major, in: the caller's initial centroids c_0 (the library draws nothing), out: the final
+ * ones.  With w the weights and x the points in the working precision, widened exactly:
+ *   k = 1, 2, ...:  l_k(i)   = the nearest of c_{k-1} to x_i: exactly kmvp_nearest with K = 1 and the centroids, rounded to
+ *                              the working precision, as sources (difference form; ties go to the smaller centroid index)
+ *                   c_k[c]   = sum_{l_k(i) = c} w_i x_i / sum_{l_k(i) = c} w_i      (float64 sums, fixed order, no atomics)
+ *                              a cluster of total weight 0 KEEPS ITS POSITION: c_k[c] = c_{k-1}[c]
+ *                   inertia_k = sum_i w_i s_i, s_i the very value the kernel compared (the distance to c_{k-1}), widened
+ *                   shift_k   = sum_c |c_k[c] - c_{k-1}[c]|^2
+ *   the first k with shift_k <= tol (absolute) stops: KMVP_OK; k == maxit stops: KMVP_E_NOT_CONVERGED, everything written.
+ * Outputs, the same in both cases: centroids = c_k, labels (N int64) = l_k, cluster_weight_or_null (C doubles) = the
+ * weights of l_k's clusters, *iters = k, *inertia = inertia_k, *shift = shift_k.
+ * Conventions
+ *  - every returned centroid of positive weight is the weighted mean of the points that carry its label; every label is
+ *    the nearest RETURNED centroid whenever *shift == 0, which is the only way tol = 0 converges -- and it is reached
+ *    exactly, because equal labels give bitwise equal sums.
+ *  - the stopping test is made on the device in every iteration (three state words cross to the host per iteration: it
+ *    only learns whether to launch another); nothing depends on when the host looks.
+ *  - chaining: maxit = 1 called k times, each call fed the previous call's centroids, gives the bits of one call with
+ *    maxit = k (nothing but the float64 centroids is carried from one iteration to the next).
+ *  - a point without a qualifying centroid (a NaN coordinate, or every distance overflowed) gets label -1, enters no sum
+ *    and ends the solve; so does a non-finite inertia or shift: KMVP_E_NOT_CONVERGED with the outputs written.  A
+ *    non-finite initial centroid and a negative or non-finite weight are KMVP_E_INVALID (host checks).
+ *  - bitwise reproducible run to run, and independent of "segments" ("chunk": accepted, ignored).
+ *  - a product, gradient, log-sum-exp or kmvp_nearest on the same context returns the same bits before and after the
+ *    call as without it: the target image of the points (packed once per kmvp_set_points), the centroid records and the
+ *    state live in buffers of the solver's own.
+ * Per iteration six launches: the C centroid records rewritten from the float64 centroids, lowd_knn_kernel<D, 1>
+ * (kmvp_last_kernel_name) and its segment merge, both untouched, the centroid update (csrc/kmvp_kmeans.hip: every
+ * workgroup walks a contiguous run of labels in index order, every thread owning the clusters of one residue modulo 256
+ * in LDS; then the workgroups' partial sums in a fixed order) and one block that forms the new centroids and the verdict
+ * (csrc/kmvp_kmeans_step.hpp).  kmvp_last_dispatch_note is ""; kmvp_last_kernel_ms and kmvp_last_total_ms both cover the
+ * whole solve.
+ * float32 and float64 contexts (float16 data: a float32 context of float16-rounded points), D <= 8, C <= 65536.
+ * KMVP_E_UNSUPPORTED with a message for bfloat16 contexts, D > 8, an explicit "fast_sqdists" of 1 .. 4, an attached
+ * communicator, a source slice (M < M_total) and C > 65536.  KMVP_E_INVALID for no points set, N < 1, C < 1, tol < 0 or
+ * NaN, maxit < 1 and a NULL centroids, labels, iters, inertia or shift. */
+int kmvp_kmeans(kmvp_ctx* ctx, int C, const double* weights_or_null, double tol, int maxit, double* centroids,
+                int64_t* labels, double* cluster_weight_or_null, int* iters, double* inertia, double* shift);
+
 /* BaseProduct.get_result (base.py:107-116): (N,E) float64 row-major. */
 int kmvp_get_result(kmvp_ctx* ctx, double* out, int64_t out_len);
 

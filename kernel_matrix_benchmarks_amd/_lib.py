@@ -55,6 +55,8 @@ SYMBOLS = [
     ("kmvp_gaussian_logsumexp_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_absexp_logsumexp_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_nearest", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    ("kmvp_kmeans", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
+                               _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
     ("kmvp_get_result", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("kmvp_gaussian_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
@@ -365,6 +367,32 @@ class Context:
         if rc not in (0, 6):
             self._check(rc)
         return u, v, iters.value, err.value, rc == 0
+
+    def kmeans(self, C, centroids0, weights, tol, maxit):
+        """Lloyd's k-means on the TARGETS of set_points (include/kmvp.h kmvp_kmeans): centroids0 (C, D) float64 initial
+        centroids, weights (N) float64 >= 0 or None (every weight 1), tol absolute on sum_c |c_k - c_{k-1}|^2.  Returns
+        (centroids, labels, cluster_weight, iterations, inertia, shift, converged); raises on every status but OK and
+        NOT_CONVERGED."""
+        C = int(C)
+        N, D = getattr(self, "N", 0), getattr(self, "D", 0)
+        # the library reads C * D and N doubles from the pointers: a shorter array must never reach it
+        cent = np.array(centroids0, dtype=np.float64, order="C", ndmin=2)  # a copy: written in place by the library
+        if C >= 1 and cent.shape != (C, D):  # (C < 1 is refused by the library before it reads anything)
+            raise ValueError(f"the initial centroids have shape {cent.shape}, expected ({C}, {D})")
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+            if weights.shape != (N,):
+                raise ValueError(f"weights has shape {weights.shape}, expected ({N},)")
+        labels = np.full(N, -1, dtype=np.int64)
+        cluster_weight = np.zeros(max(C, 0), dtype=np.float64)
+        iters = ctypes.c_int(0)
+        inertia, shift = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        rc = self._lib.kmvp_kmeans(self._ctx, C, None if weights is None else weights.ctypes.data, float(tol), int(maxit),
+                                   cent.ctypes.data, labels.ctypes.data, cluster_weight.ctypes.data, ctypes.byref(iters),
+                                   ctypes.byref(inertia), ctypes.byref(shift))
+        if rc not in (0, 6):
+            self._check(rc)
+        return cent, labels, cluster_weight, iters.value, inertia.value, shift.value, rc == 0
 
     def set_solver_diagonal(self, d_or_none, ridge=0.0):
         """A = K + ridge I + diag(d) for the solves that follow (include/kmvp.h kmvp_set_solver_diagonal); d: one float64

@@ -1040,3 +1040,185 @@ class MI355XSinkhorn:
             self.done()
         except Exception:
             pass
+
+
+KMEANS_MAX_D = NEAREST_MAX_D
+KMEANS_MAX_CLUSTERS = 65536
+KMEANS_INITS = ("random", "k-means++")
+
+
+class MI355XKMeans:
+    """Lloyd's k-means on one MI355X, resident on the device (include/kmvp.h kmvp_kmeans; the pair loop is
+    lowd_knn_kernel at K = 1, the centroid update a deterministic, atomics-free kernel of its own).  An extension: the
+    reference's plugin API has no such role, so the class is not registered in algos.yaml.
+
+        minimise  sum_i w_i |x_i - c_{l(i)}|^2   over n_clusters centroids c and the assignment l
+
+    Call order: prepare_data, fit, query, then get_centroids / get_labels / get_cluster_weights / predict /
+    get_additional, done.  ``tol`` is ABSOLUTE on sum_c |c_k - c_{k-1}|^2, the squared displacement of the centroids in
+    one iteration, in the units of the points squared; tol = 0 (the default) stops at the fixed point, which Lloyd's
+    iteration reaches exactly.  A cluster that no point of positive weight is assigned to keeps its position.
+
+    Initialisation happens on the host, from ``seed`` (the library itself draws nothing):
+      init="random"     n_clusters distinct points, drawn without replacement;
+      init="k-means++"  D^2 sampling in numpy: every next centroid is a point drawn with probability proportional to its
+                        weight times its squared distance to the nearest centroid chosen so far.  O(N * n_clusters) work
+                        and n_clusters passes over the points ON THE HOST: meant for moderate n_clusters, not timed.
+    query(init=array) takes explicit (n_clusters, D) centroids instead, which also serves as a warm start.
+    ``options``: device, segments (the result does not depend on it)."""
+
+    def __init__(self, *, n_clusters, dimension, precision=np.float32, tol=0.0, maxit=300, init="random", seed=0, device=0,
+                 segments=0):
+        if int(n_clusters) < 1:
+            raise ValueError(f"n_clusters must be >= 1, not {n_clusters!r}")
+        if init not in KMEANS_INITS:
+            raise ValueError(f"init must be one of {KMEANS_INITS}, not {init!r}")
+        if not float(tol) >= 0:
+            raise ValueError(f"tol must be >= 0, not {tol!r}")
+        self.n_clusters, self.dimension = int(n_clusters), int(dimension)
+        self.precision = precision
+        self._dtype_code, self._host_dtype = _lib.dtype_code(precision)
+        self._round = _lib.input_rounding(precision)  # float16: rounded points, float32 arithmetic
+        self.tol, self.maxit = float(tol), int(maxit)
+        self.init, self.seed = init, seed
+        self.device = device
+        self._options = dict(segments=segments)
+        self._ctx = self._predict_ctx = None
+        self.centroids = self.labels = self.cluster_weights = None
+        self.iterations, self.inertia, self.shift, self.converged = 0, float("nan"), float("nan"), False
+        self.name = f"MI355XKMeans({_precision_name(precision)}, n_clusters={self.n_clusters})"
+
+    def _as_device_points(self, points, what):
+        p = np.asarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != self.dimension:
+            raise ValueError(f"{what} has shape {p.shape}, expected (N, {self.dimension})")
+        if self._round is not None:
+            p = p.astype(self._round)
+        return np.ascontiguousarray(p, dtype=self._host_dtype)
+
+    def _new_context(self):
+        ctx = _lib.Context(self.device)
+        for key, value in self._options.items():
+            if value:
+                ctx.set_option(key, value)
+        return ctx
+
+    # -- untimed -------------------------------------------------------------------
+    def prepare_data(self, *, points, weights=None):
+        x = self._as_device_points(points, "points")
+        self.N, self.D = x.shape
+        if self.N < 1:
+            raise ValueError("k-means needs at least one point")
+        if weights is not None:
+            weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+            if weights.shape != (self.N,):
+                raise ValueError(f"weights has {weights.size} entries for {self.N} points")
+            if not (np.all(weights >= 0) and np.all(np.isfinite(weights))):  # (NaN fails the first)
+                raise ValueError("weights must be non-negative and finite")
+        self._x, self._w = x, weights  # the points as the device holds them
+        if self._ctx is None:
+            self._ctx = self._new_context()
+        self._ctx.set_points(x, None, self._dtype_code)  # the cloud is its own target set: the points of kmvp_kmeans
+        self.centroids = self.labels = self.cluster_weights = None
+
+    def _initial_centroids(self):
+        rs = np.random.RandomState(self.seed)
+        x = np.asarray(self._x, dtype=np.float64)
+        C = self.n_clusters
+        if self.init == "random":
+            if C > self.N:
+                raise ValueError(f"init='random' draws {C} distinct points, and there are only {self.N}")
+            return x[rs.choice(self.N, size=C, replace=False)]
+        w = np.ones(self.N) if self._w is None else self._w
+        if not np.sum(w) > 0:
+            raise ValueError("init='k-means++' needs a point of positive weight")
+        cent = np.empty((C, self.D))
+        cent[0] = x[rs.choice(self.N, p=w / np.sum(w))]
+        near = np.sum((x - cent[0]) ** 2, axis=1)
+        for c in range(1, C):
+            p = w * near
+            total = float(np.sum(p))
+            # every point of positive weight already coincides with a centroid: fall back to the weights themselves
+            cent[c] = x[rs.choice(self.N, p=p / total if total > 0 else w / np.sum(w))]
+            near = np.minimum(near, np.sum((x - cent[c]) ** 2, axis=1))
+        return cent
+
+    # -- timed ---------------------------------------------------------------------
+    def fit(self):
+        """Nothing to build ahead of the first solve: it packs the points' layout itself, once per prepare_data."""
+
+    def query(self, init=None):
+        """Runs Lloyd's iteration from ``init`` ((n_clusters, D) centroids: explicit initial centroids or a warm start,
+        e.g. get_centroids() of an earlier solve) or from the constructor's init= rule.  Synchronous.  Not converged
+        (maxit reached, or a point without a label / a non-finite inertia) is a result, reported by
+        get_additional()["converged"]; every other failure raises."""
+        if self._ctx is None:
+            raise RuntimeError("MI355XKMeans.query() needs prepare_data() first")
+        if init is None:
+            c0 = self._initial_centroids()
+        else:
+            c0 = np.asarray(init, dtype=np.float64)
+            if c0.shape != (self.n_clusters, self.D):
+                raise ValueError(f"init has shape {c0.shape}, expected ({self.n_clusters}, {self.D})")
+        (self.centroids, self.labels, self.cluster_weights, self.iterations, self.inertia, self.shift,
+         self.converged) = self._ctx.kmeans(self.n_clusters, c0, self._w, self.tol, self.maxit)
+
+    def set_query_arguments(self, tol=None, maxit=None):
+        if tol is not None:
+            self.tol = float(tol)
+        if maxit is not None:
+            self.maxit = int(maxit)
+
+    # -- results -------------------------------------------------------------------
+    def _need_solution(self, method):
+        if self.centroids is None:
+            raise RuntimeError(f"MI355XKMeans.{method}: no solution yet -- call query() after prepare_data() first")
+
+    def get_centroids(self):
+        """(n_clusters, D) float64: the weighted means of the points that carry each label."""
+        self._need_solution("get_centroids")
+        return self.centroids
+
+    def get_labels(self):
+        """(N,) int64: the cluster of every point (-1: a point without a qualifying centroid, e.g. a NaN coordinate)."""
+        self._need_solution("get_labels")
+        return self.labels
+
+    def get_cluster_weights(self):
+        """(n_clusters,) float64: the total weight of every cluster (the point count without weights)."""
+        self._need_solution("get_cluster_weights")
+        return self.cluster_weights
+
+    def predict(self, points):
+        """(M,) int64: the nearest final centroid of every row of ``points`` -- kmvp_nearest with K = 1 against the
+        centroids rounded to the working precision, the rule the iteration itself assigns by (ties: the smaller index)."""
+        self._need_solution("predict")
+        x = self._as_device_points(points, "points")
+        if self._predict_ctx is None:  # a context of its own: the solver's keeps the training points
+            self._predict_ctx = self._new_context()
+        self._predict_ctx.set_points(np.ascontiguousarray(self.centroids, dtype=self._host_dtype), x, self._dtype_code)
+        idx, _ = self._predict_ctx.run_nearest(1, False)
+        return np.ascontiguousarray(idx[:, 0])
+
+    def get_memory_usage(self):
+        """Device kB held by the contexts."""
+        return sum(ctx.device_bytes for ctx in (self._ctx, self._predict_ctx) if ctx is not None) / 1024
+
+    def get_additional(self):
+        extra = {"iterations": self.iterations, "inertia": self.inertia, "shift": self.shift, "converged": bool(self.converged)}
+        if self._ctx is not None:
+            extra.update(device_kernel_ms=self._ctx.last_kernel_ms, device_total_ms=self._ctx.last_total_ms,
+                         device_kernel=self._ctx.last_kernel_name, device_bytes=self._ctx.device_bytes)
+        return extra
+
+    def done(self):
+        for ctx in (self._ctx, self._predict_ctx):
+            if ctx is not None:
+                ctx.close()
+        self._ctx = self._predict_ctx = None
+
+    def __del__(self):
+        try:
+            self.done()
+        except Exception:
+            pass

@@ -90,7 +90,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
                     &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     release(*b);
   for (int i = 0; i < 5; ++i)
@@ -194,6 +194,10 @@ int kmvp_gaussian_logsumexp_grad(kmvp_ctx* c) { return run_logsumexp_grad(c, K_G
 int kmvp_absexp_logsumexp_grad(kmvp_ctx* c) { return run_logsumexp_grad(c, K_ABSEXP); }
 int kmvp_nearest(kmvp_ctx* c, int K, int exclude_self, int64_t* out_idx, double* out_sqdist) {
   return run_nearest(c, K, exclude_self, out_idx, out_sqdist);
+}
+int kmvp_kmeans(kmvp_ctx* c, int C, const double* weights, double tol, int maxit, double* centroids, int64_t* labels,
+                double* cluster_weight, int* iters, double* inertia, double* shift) {
+  return kmeans_solve(c, C, weights, tol, maxit, centroids, labels, cluster_weight, iters, inertia, shift);
 }
 
 int kmvp_get_result(kmvp_ctx* c, double* out, int64_t out_len) {
@@ -406,7 +410,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
                           &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     t += b->cap;
   return (int64_t)t;

@@ -4,6 +4,7 @@
 //   kmvp_product.hip  layouts, launch geometry, the pair-loop paths and the policy that picks one
 //   kmvp_solvers.hip  conjugate gradients, MINRES and the Lanczos quadrature on the product
 //   kmvp_sinkhorn.hip the Sinkhorn iteration of entropic optimal transport on the log-sum-exp
+//   kmvp_kmeans.hip   Lloyd's k-means on the arg-K-min at K = 1
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -135,6 +136,10 @@ struct kmvp_ctx {
   // image of y with records of x (the record's signal slot carries potential + log-weight) -- and the fp64 state
   DevBuf sk_xs_x, sk_rec_y, sk_xs_y, sk_rec_x, sk_state;
   uint64_t sk_points_ver = 0;   // points version the four layouts were packed from (0: none)
+  // k-means (kmvp_kmeans.hip): the target image of the points, the centroid records, the workgroups' partial sums of the
+  // centroid update, and the fp64 state (centroids, cluster sums, weights, labels, state words)
+  DevBuf km_xs, km_rec, km_part, km_state;
+  uint64_t km_points_ver = 0;   // points version km_xs was packed from (0: none)
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
   int packed_layout = -1;  // LAYOUT_* of the path that owns xs / rec right now
@@ -221,5 +226,9 @@ int cg_lanczos(kmvp_ctx* c, int kernel, const void* z_host, int P, double rtol, 
 // kmvp_sinkhorn.hip: kmvp_<kernel>_sinkhorn, the device-resident Sinkhorn iteration on lowd_lse_kernel
 int sinkhorn_solve(kmvp_ctx* c, int kernel, const double* log_a, const double* log_b, double tol, int maxit, double* u,
                    double* v, int* iters, double* err);
+
+// kmvp_kmeans.hip: kmvp_kmeans, the device-resident Lloyd iteration on lowd_knn_kernel<D, 1>
+int kmeans_solve(kmvp_ctx* c, int C, const double* weights, double tol, int maxit, double* centroids, int64_t* labels,
+                 double* cluster_weight, int* iters, double* inertia, double* shift);
 
 }  // namespace kmvp

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kmvp_knn_merge.hpp"
 #include "kmvp_lowd.hpp"
 
 namespace kmvp {
@@ -181,6 +182,16 @@ inline int knn_segments(int opt_segments, int KT, int64_t tile_blocks, int64_t m
   const int64_t cap_len = std::max<int64_t>(1, m_pad / KNN_MIN_SEGMENT);
   const int64_t cap_mem = std::max<int64_t>(1, (int64_t)(4e9 / (2.0 * KT * n_pad * 8)));
   return (int)std::max<int64_t>(1, std::min(for_parallelism, std::min(cap_len, cap_mem)));
+}
+// The segment merge (kmvp_knn_merge.hpp): S lists of KT candidates per target, [list][2 KT][elem_stride], into the Kc
+// smallest in the canonical unpadded layout cand[2 Kc][n] -- distances in rows 0 .. Kc - 1, indices behind them.  What
+// kmvp_nearest (kmvp_product.hip) and the k-means iteration on top of it (kmvp_kmeans.hip) share.
+// (static: a kernel cannot be inline; each of the two units that launch it carries its own copy, the others none)
+static __global__ void knn_merge_kernel(const double* __restrict__ lists, double* __restrict__ cand, int64_t n, int64_t list_stride,
+                                        int64_t elem_stride, int S, int KT, int Kc) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  knn_merge(lists + i, list_stride, elem_stride, S, KT, Kc, cand + i, cand + (int64_t)Kc * n + i, n);
 }
 
 // Gradient of the log-sum-exp with respect to the targets (kmvp_lowd_lse_grad.hpp; kmvp_lowd_lse_grad_inst.hip, one unit

@@ -5,7 +5,7 @@
 // S such lists of one target into the K smallest under the same order; the ranks of a communicator are merged by the same
 // function with `world` lists in place of segments.  knn_drop_self() is the exclude-self rule.
 //
-// Plain C++ with the device attributes behind a macro: the same text runs in knn_merge_kernel (kmvp_product.hip) and,
+// Plain C++ with the device attributes behind a macro: the same text runs in knn_merge_kernel (kmvp_internal.hpp) and,
 // compiled with a host compiler alone, in tests/test_host_knn_merge.py.
 #pragma once
 #include <stdint.h>

@@ -13,7 +13,6 @@
 #include "kmvp_fastmm_pack.hpp"
 #include "kmvp_cfastmm_pack.hpp"
 #include "kmvp_mfma_pack.hpp"
-#include "kmvp_knn_merge.hpp"
 
 namespace kmvp {
 namespace {
@@ -2397,13 +2396,7 @@ int run_logsumexp_grad(kmvp_ctx* c, int kernel) {
 // lowd_knn_kernel leaves KT sorted candidates per (segment, target): part[s][2 KT][n_pad].  knn_merge_kernel folds S lists
 // of one target into Kc = K (+ 1 with exclude_self) candidates in the canonical unpadded layout [2 Kc][N] -- the segments
 // first, then, sharded, the ranks' lists after ONE all-reduce; knn_finish_kernel drops the own index and writes (N, K).
-static __global__ void knn_merge_kernel(const double* __restrict__ lists, double* __restrict__ cand, int64_t n, int64_t list_stride,
-                                        int64_t elem_stride, int S, int KT, int Kc) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  knn_merge(lists + i, list_stride, elem_stride, S, KT, Kc, cand + i, cand + (int64_t)Kc * n + i, n);
-}
-
+// (knn_merge_kernel: kmvp_internal.hpp, shared with the k-means iteration.)
 static __global__ void knn_fill_kernel(double* __restrict__ cand, int64_t n, int Kc) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= 2 * (int64_t)Kc * n) return;
