@@ -472,6 +472,38 @@ int kmvp_absexp_sinkhorn(kmvp_ctx* ctx, const double* log_a_or_null, const doubl
  *   exp(-r), Matern: positive definite only with a non-negative shift) any ridge + d_i < 0.  MINRES takes any sign. */
 int kmvp_set_solver_diagonal(kmvp_ctx* ctx, const double* d_or_null, int64_t n, double ridge);
 
+/* Pivoted-Cholesky preconditioner for the conjugate-gradient entries (an extension, opt-in; what Gaussian-process
+ * libraries that solve by CG use).  rank in 1 .. KMVP_PRECOND_MAX_RANK: the kmvp_<kernel>_cg_solve calls that follow on
+ * this ctx (Gaussian, exp(-r), Matern 3/2 and 5/2) iterate with z = P^-1 r,
+ *     P = L L' + D,   L (N, rank') the first rank' <= rank columns of the pivoted Cholesky factorisation of K,
+ *                     D = diag(ridge + d_i) as kmvp_set_solver_diagonal set it,
+ * applied exactly through the Woodbury identity (2 N rank' flops per column next to the N^2 pair evaluations of the
+ * operator).  rank = 0 (the default) switches it off: the solve is then bit for bit the unpreconditioned one.
+ * kmvp_set_points switches it off too, as it clears the solver diagonal.  rank < 0: KMVP_E_INVALID; rank >
+ * KMVP_PRECOND_MAX_RANK: KMVP_E_UNSUPPORTED; a refused call leaves the previous setting.
+ *   The factor is built inside the first solve that needs it (device-resident: argmax of the residual diagonal with ties
+ *   to the smaller index, one kernel column in the working precision from the raw points by the difference form -- any D
+ *   --, float64 update; no further column once the residual diagonal's maximum is <= 256 unit roundoffs of the working
+ *   precision, hence rank' <= rank) and kept until the points, the kernel, the rank or the solver diagonal change.  On a
+ *   source shard it is built from the targets, the full cloud on every rank: no communication, the same bits everywhere.
+ *   The iteration stops on the same test as the plain one -- sqrt(|r|^2 / |a|^2) <= rtol on the recurrence residual -- so
+ *   rtol, *resid and the 1.5 rtol verdict mean what they mean without it; stop word, first-iteration rule, residual
+ *   replacement, bursts of 8 iterations and their graph replay carry over.  Bitwise reproducible run to run.
+ *   At solve time rank > 0 needs a solver diagonal with ridge + d_i > 0 everywhere (P is positive definite only then):
+ *   KMVP_E_INVALID with a message that names the preconditioner otherwise.
+ *   kmvp_invdist_minres_solve with rank > 0 is KMVP_E_UNSUPPORTED (that matrix is indefinite).  The
+ *   kmvp_<kernel>_lanczos_quadrature entries IGNORE the setting (a preconditioned quadrature needs the log det P
+ *   correction); products, gradients and everything else are unaffected.
+ * kmvp_get_solver_preconditioner: what the LAST kmvp_<kernel>_cg_solve applied -- *rank_built = rank' (0 when it ran
+ * unpreconditioned, nothing else is written then), pivots_or_null (rank' values: the point index of every column),
+ * factor_or_null ((rank', N) float64 row-major: row t = column t of L).
+ * kmvp_last_preconditioner_ms: the build inside the last kmvp_<kernel>_cg_solve, host wall clock (0 when the factor was
+ * reused or the preconditioner is off); kmvp_last_total_ms of that solve includes it. */
+#define KMVP_PRECOND_MAX_RANK 128
+int kmvp_set_solver_preconditioner(kmvp_ctx* ctx, int rank);
+int kmvp_get_solver_preconditioner(kmvp_ctx* ctx, int* rank_built, int64_t* pivots_or_null, double* factor_or_null);
+double kmvp_last_preconditioner_ms(const kmvp_ctx* ctx);
+
 /* Source sharding over the GPUs of one node, one process per GPU:
  * rank 0 calls kmvp_comm_get_unique_id and hands the 128 bytes to every rank
  * out of band; every rank then calls kmvp_comm_init.  world == 1 is allowed. */

@@ -77,6 +77,9 @@ SYMBOLS = [
     ("kmvp_absexp_sinkhorn", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p,
                                         _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_set_solver_diagonal", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_double]),
+    ("kmvp_set_solver_preconditioner", _c.c_int, [_c.c_void_p, _c.c_int]),
+    ("kmvp_get_solver_preconditioner", _c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int), _c.c_void_p, _c.c_void_p]),
+    ("kmvp_last_preconditioner_ms", _c.c_double, [_c.c_void_p]),
     ("kmvp_comm_get_unique_id", _c.c_int, [_c.c_void_p]),
     ("kmvp_comm_init", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int]),
     ("kmvp_comm_init_host", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int]),
@@ -405,6 +408,36 @@ class Context:
         if d.ndim != 1:  # the library reads d.size doubles and compares the count with the points at solve time
             raise ValueError(f"the solver diagonal has shape {d.shape}, expected one value per point")
         self._check(self._lib.kmvp_set_solver_diagonal(self._ctx, d.ctypes.data, d.size, float(ridge)))
+
+    def set_solver_preconditioner(self, rank):
+        """Pivoted-Cholesky preconditioner of rank ``rank`` for the cg_solve calls that follow (include/kmvp.h
+        kmvp_set_solver_preconditioner); 0 switches it off, set_points clears it."""
+        self._check(self._lib.kmvp_set_solver_preconditioner(self._ctx, int(rank)))
+
+    def get_solver_preconditioner(self):
+        """What the last cg_solve applied (include/kmvp.h kmvp_get_solver_preconditioner): (rank_built, pivots int64
+        (rank_built,), factor float64 (rank_built, N), row t = column t of L); (0, empty, empty) when it ran
+        unpreconditioned."""
+        built = ctypes.c_int(0)
+        self._check(self._lib.kmvp_get_solver_preconditioner(self._ctx, ctypes.byref(built), None, None))
+        # the library writes rank_built and rank_built * N elements through the pointers: the arrays are sized from its answer
+        pivots = np.empty(built.value, dtype=np.int64)
+        factor = np.empty((built.value, int(getattr(self, "N", 0))), dtype=np.float64)
+        if built.value:
+            self._check(self._lib.kmvp_get_solver_preconditioner(self._ctx, ctypes.byref(built), pivots.ctypes.data,
+                                                                 factor.ctypes.data))
+        return built.value, pivots, factor
+
+    @property
+    def last_preconditioner_rank(self):
+        """Columns of the factor the last cg_solve applied (0: it ran unpreconditioned), without reading the factor."""
+        built = ctypes.c_int(0)
+        self._check(self._lib.kmvp_get_solver_preconditioner(self._ctx, ctypes.byref(built), None, None))
+        return built.value
+
+    @property
+    def last_preconditioner_ms(self):
+        return float(self._lib.kmvp_last_preconditioner_ms(self._ctx))
 
     def comm_init(self, unique_id, rank, world):
         buf = (ctypes.c_char * UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

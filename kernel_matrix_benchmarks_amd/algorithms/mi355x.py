@@ -526,10 +526,15 @@ class MI355XSolver(BaseSolver):
     ``ridge`` (an extension: the reference's lstsq solves the bare system) regularises it: (K + ridge I) b = a with a
     float, (K + diag(ridge)) b = a with one value per point -- the nugget / noise / ``alpha`` of Kriging, Gaussian
     processes and kernel ridge regression.  Non-negative for the CG kernels, any sign for inverse-distance.  The
-    residual, ``rtol`` and ``converged`` are then about the regularised system."""
+    residual, ``rtol`` and ``converged`` are then about the regularised system.
+
+    ``preconditioner_rank`` (an extension, 0 = off): conjugate gradients preconditioned by a pivoted-Cholesky factor of
+    that many columns plus the ridge (include/kmvp.h kmvp_set_solver_preconditioner); it needs ``ridge`` > 0 and changes
+    the iteration count, not what ``rtol`` and ``converged`` mean."""
 
     def __init__(self, *, kernel, dimension, normalize_rows=False, precision=np.float64,
-                 device=0, rtol=1e-6, maxit=10000, comm=None, refine=None, inner_rtol=1e-3, ridge=0.0):
+                 device=0, rtol=1e-6, maxit=10000, comm=None, refine=None, inner_rtol=1e-3, ridge=0.0,
+                 preconditioner_rank=0):
         super().__init__(kernel=kernel, dimension=dimension, normalize_rows=normalize_rows,
                          precision=precision)
         if kernel not in SUPPORTED_KERNELS:
@@ -565,6 +570,25 @@ class MI355XSolver(BaseSolver):
                            f"MI355XSolver({_precision_name(precision)}, {self.method} + refinement on {refine}, rtol={rtol:g}")
         self._diag_in_ctx = False  # whether the contexts hold a diagonal right now (set_points clears it)
         self._set_ridge(ridge)
+        self._precond_in_ctx = 0   # the rank the context holds right now (set_points clears it)
+        self._set_preconditioner_rank(preconditioner_rank)
+        self._check_preconditioner_ridge()
+
+    def _set_preconditioner_rank(self, rank):
+        """Validates and stores ``preconditioner_rank``; it reaches the library at the next query()."""
+        rank = int(rank)
+        if rank < 0:
+            raise ValueError("preconditioner_rank must be >= 0")
+        if rank > 0 and (self.method != "cg" or self._dot or self.refine):
+            what = "refine" if self.refine else f"kernel {self.kernel}"
+            raise NotImplementedError(f"MI355XSolver(preconditioner_rank > 0) doesn't support {what}.")
+        self.preconditioner_rank = rank
+        self._update_name()
+
+    def _check_preconditioner_ridge(self):
+        if self.preconditioner_rank > 0 and isinstance(self.ridge, float) and self.ridge == 0.0:
+            raise ValueError("preconditioner_rank > 0 needs ridge > 0 (the preconditioner L L' + ridge is positive definite "
+                             "only then)")
 
     def _set_ridge(self, ridge):
         """Validates and stores ``ridge`` (a float, or one value per point); it reaches the library at the next query()."""
@@ -583,11 +607,16 @@ class MI355XSolver(BaseSolver):
             raise ValueError(f"ridge has {r.size} values, the point cloud has {self.M} points")
         self.ridge = float(r) if r.ndim == 0 else r
         self._diag_dirty = True
-        # (the name moves only when a ridge is set: result files of runs without one keep theirs)
-        if r.ndim == 0:
-            self.name = self._base_name + (f", ridge={self.ridge:g})" if self.ridge != 0.0 else ")")
+        self._update_name()
+
+    def _update_name(self):
+        # (the name moves only when a ridge or a preconditioner is set: result files of runs without them keep theirs)
+        if isinstance(self.ridge, float):
+            name = self._base_name + (f", ridge={self.ridge:g}" if self.ridge != 0.0 else "")
         else:
-            self.name = self._base_name + f", ridge=per-point up to {float(np.max(r)):g})"
+            name = self._base_name + f", ridge=per-point up to {float(np.max(self.ridge)):g}"
+        rank = getattr(self, "preconditioner_rank", 0)
+        self.name = name + (f", preconditioner_rank={rank})" if rank else ")")
 
     def _library_diagonal(self):
         """(d or None, ridge) as kmvp_set_solver_diagonal takes them.  exp-dot: the library iterates on G z = D^-1 a
@@ -643,6 +672,7 @@ class MI355XSolver(BaseSolver):
         if not isinstance(self.ridge, float) and self.ridge.size != self.M:
             raise ValueError(f"ridge has {self.ridge.size} values, the point cloud has {self.M} points")
         self._diag_in_ctx, self._diag_dirty = False, True  # kmvp_set_points clears the library's diagonal
+        self._precond_in_ctx = 0                            # and its preconditioner
         if self._ctx is None:
             self._ctx = _lib.Context(self.device)
         world = 1 if self.comm is None else self.comm.world
@@ -673,16 +703,33 @@ class MI355XSolver(BaseSolver):
         if self._a.ndim != 2 or self._a.shape[0] != self.M:
             raise ValueError(f"target_signal has shape {a.shape}, expected ({self.M}, E)")
 
-    def set_query_arguments(self, rtol=None, maxit=None, ridge=None):
+    def set_query_arguments(self, rtol=None, maxit=None, ridge=None, preconditioner_rank=None):
         if rtol is not None:
             self.rtol = rtol
         if maxit is not None:
             self.maxit = maxit
-        if ridge is not None:
-            self._set_ridge(ridge)  # takes effect at the next query()
+        before = (self.ridge, self.preconditioner_rank)
+        try:
+            if ridge is not None:
+                self._set_ridge(ridge)  # takes effect at the next query()
+            if preconditioner_rank is not None:
+                self._set_preconditioner_rank(preconditioner_rank)  # likewise
+            self._check_preconditioner_ridge()
+        except Exception:  # a refused pair leaves the previous one
+            self._set_ridge(before[0])
+            self._set_preconditioner_rank(before[1])
+            raise
+
+    def _apply_preconditioner(self):
+        """Hands the rank to the context when it differs from what the context holds."""
+        self._check_preconditioner_ridge()
+        if self.preconditioner_rank != self._precond_in_ctx:
+            self._ctx.set_solver_preconditioner(self.preconditioner_rank)
+            self._precond_in_ctx = self.preconditioner_rank
 
     def query(self):
         self._apply_diagonal()
+        self._apply_preconditioner()
         if self.refine:
             self._query_refined()
         else:
@@ -860,6 +907,9 @@ class MI355XSolver(BaseSolver):
                  "cg_converged": bool(self.converged), "n_gpus": 1 if self.comm is None else self.comm.world}
         if not isinstance(self.ridge, float) or self.ridge != 0.0:  # like the name: only when one is set
             extra["ridge"] = float(np.max(self.ridge))
+        if self.preconditioner_rank > 0 and self._ctx is not None:  # like the ridge: only when one is set
+            extra["preconditioner_rank"] = self._ctx.last_preconditioner_rank  # as built
+            extra["preconditioner_ms"] = self._ctx.last_preconditioner_ms
         if self._ctx is not None:
             extra["device_kernel"] = self._ctx.last_kernel_name  # the operator's pair-loop kernel
             extra["rccl_ranks"] = self._ctx.rccl_ranks

@@ -89,7 +89,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
-                    &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
+                    &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
                     &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     release(*b);
@@ -134,6 +134,8 @@ int kmvp_set_points(kmvp_ctx* c, const void* y, int64_t M, const void* x_or_null
   c->diag_on = false;  // the solver's diagonal belongs to the points it was set for
   c->diag_n = 0;
   c->diag_ridge = c->diag_min = 0.0;
+  c->precond_rank = 0;  // and so does the preconditioner, built from them and from that diagonal
+  c->pc_used = 0;
   ++c->points_ver;
   return KMVP_OK;
 }
@@ -232,6 +234,8 @@ int kmvp_matern52_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int m
 
 int kmvp_invdist_minres_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
                               int* iters, double* resid) {
+  if (c && c->precond_rank > 0)
+    return fail(c, KMVP_E_UNSUPPORTED, "preconditioner: MINRES has none (the inverse-distance matrix is indefinite); set rank 0");
   return minres_solve(c, K_INVDIST, a, E, rtol, maxit, out_b, iters, resid);
 }
 
@@ -265,6 +269,7 @@ int kmvp_set_solver_diagonal(kmvp_ctx* c, const double* d, int64_t n, double rid
   if (!c) return KMVP_E_INVALID;
   if (!std::isfinite(ridge)) return fail(c, KMVP_E_INVALID, "solver diagonal: ridge is not finite");
   if (n < 0 || (d == nullptr) != (n == 0)) return fail(c, KMVP_E_INVALID, "solver diagonal: pass n values, or NULL and n = 0");
+  ++c->diag_ver;  // a preconditioner built with the previous diagonal is rebuilt
   if (!d) {
     c->diag_on = ridge != 0.0;
     c->diag_n = 0;
@@ -290,6 +295,19 @@ int kmvp_set_solver_diagonal(kmvp_ctx* c, const double* d, int64_t n, double rid
   c->diag_min = lo;
   return KMVP_OK;
 }
+
+int kmvp_set_solver_preconditioner(kmvp_ctx* c, int rank) {
+  if (!c) return KMVP_E_INVALID;
+  if (rank < 0) return fail(c, KMVP_E_INVALID, "preconditioner: rank must be >= 0");
+  if (rank > KMVP_PRECOND_MAX_RANK)
+    return fail(c, KMVP_E_UNSUPPORTED, "preconditioner: rank " + std::to_string(rank) + " is beyond " + std::to_string(KMVP_PRECOND_MAX_RANK));
+  c->precond_rank = rank;
+  return KMVP_OK;
+}
+int kmvp_get_solver_preconditioner(kmvp_ctx* c, int* rank_built, int64_t* pivots, double* factor) {
+  return precond_read(c, rank_built, pivots, factor);
+}
+double kmvp_last_preconditioner_ms(const kmvp_ctx* c) { return c ? c->last_precond_ms : 0.0; }
 
 int kmvp_comm_get_unique_id(void* id128) {
   if (!id128) return KMVP_E_INVALID;
@@ -409,7 +427,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   if (!c) return 0;
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
-                          &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
+                          &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
                     &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     t += b->cap;

@@ -5,6 +5,7 @@
 //   kmvp_solvers.hip  conjugate gradients, MINRES and the Lanczos quadrature on the product
 //   kmvp_sinkhorn.hip the Sinkhorn iteration of entropic optimal transport on the log-sum-exp
 //   kmvp_kmeans.hip   Lloyd's k-means on the arg-K-min at K = 1
+//   kmvp_precond.hip  the pivoted-Cholesky preconditioner of conjugate gradients: build, apply, read-back
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -132,6 +133,15 @@ struct kmvp_ctx {
   DevBuf scratch;               // CG vectors / dot products
   DevBuf knn;                   // kmvp_nearest: (N, K) int64 indices, then (N, K) float64 squared distances
   DevBuf sdiag;                 // solvers: the effective diagonal ridge + d_i, N doubles (kmvp_set_solver_diagonal)
+  // conjugate gradients' pivoted-Cholesky preconditioner (kmvp_set_solver_preconditioner; layout: kmvp_precond.hip)
+  DevBuf precond;               // residual diagonal, 1 / (ridge + d_i), the factor L [rank][N], pivots, Gram matrix and its factor
+  int precond_rank = 0;         // as requested: 0 = off
+  int pc_built = 0;             // columns the factor in `precond` holds (<= pc_rank)
+  int pc_used = 0;              // columns the last kmvp_<kernel>_cg_solve applied (0: it ran unpreconditioned)
+  int pc_kernel = -1, pc_rank = 0;  // what the factor was built for, with the versions below (pc_points_ver 0: no factor)
+  uint64_t pc_points_ver = 0, pc_diag_ver = 0;
+  uint64_t diag_ver = 0;        // counts kmvp_set_solver_diagonal
+  float last_precond_ms = 0.f;  // the build inside the last kmvp_<kernel>_cg_solve (0: reused, or off)
   // Sinkhorn (kmvp_sinkhorn.hip): layouts of its own for both directions -- target image of x with records of y, target
   // image of y with records of x (the record's signal slot carries potential + log-weight) -- and the fp64 state
   DevBuf sk_xs_x, sk_rec_y, sk_xs_y, sk_rec_x, sk_state;
@@ -214,6 +224,28 @@ int run_dscale(kmvp_ctx* c, int kernel);      // kmvp_<kernel>_dscale: (N, E D) 
 int run_logsumexp(kmvp_ctx* c, int kernel);   // kmvp_<kernel>_logsumexp: (N, E) into c->out, synchronous
 int run_logsumexp_grad(kmvp_ctx* c, int kernel);  // kmvp_<kernel>_logsumexp_grad: (N, E D) into c->out, synchronous
 int run_nearest(kmvp_ctx* c, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);  // kmvp_nearest: synchronous, into the caller's arrays
+
+// The solver's diagonal (kmvp_set_solver_diagonal) as the kernels take it: dg[i] = ridge + d_i per point, or nullptr and the
+// scalar.  Both are fixed for a whole solve, so a captured burst stays valid.
+struct Diag {
+  const double* dg;
+  double ridge;
+  __device__ __forceinline__ double at(int64_t i) const { return dg ? dg[i] : ridge; }
+};
+inline Diag solver_diag(const kmvp_ctx* c) { return Diag{c->diag_n ? (const double*)c->sdiag.p : nullptr, c->diag_ridge}; }
+
+// kmvp_precond.hip: P = L L' + D, L the rank-R pivoted Cholesky factor of the kernel matrix and D the solver's diagonal
+// Builds the factor for (points, kernel, rank, diagonal) unless the context holds it; c->pc_built columns afterwards.
+int precond_prepare(kmvp_ctx* c, int kernel);
+constexpr int PC_APPLY_BLOCKS = 256;  // workgroups of the apply's first launch
+// doubles of scratch one apply needs for E columns: the partial sums of L' D^-1 r, then w = C^-1 (L' D^-1 r)
+inline size_t precond_scratch(int R, int E) { return (size_t)(PC_APPLY_BLOCKS + 1) * (size_t)R * (size_t)E; }
+// z = P^-1 r for the (N, E) row-major r, and rz_partial[block][e] = the block's share of r . z (cg_dot_kernel's layout for
+// `rz_blocks` workgroups of 256).  Three launches on the context's stream; nothing once *stop != 0.
+void precond_apply(kmvp_ctx* c, const double* r, double* z, int E, double* scratch, double* rz_partial, int rz_blocks,
+                   const double* stop);
+// kmvp_get_solver_preconditioner
+int precond_read(kmvp_ctx* c, int* rank_built, int64_t* pivots, double* factor);
 
 // kmvp_solvers.hip
 int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit, double* out_b,

@@ -52,14 +52,6 @@ __global__ void cg_dot_kernel(const double* __restrict__ u, const double* __rest
   }
 }
 
-// The solver's diagonal (kmvp_set_solver_diagonal) as the kernels take it: dg[i] = ridge + d_i per point, or nullptr and the
-// scalar.  Both are fixed for a whole solve, so a captured burst stays valid.
-struct Diag {
-  const double* dg;
-  double ridge;
-  __device__ __forceinline__ double at(int64_t i) const { return dg ? dg[i] : ridge; }
-};
-
 // CG's first consumer of K p with the diagonal on: Ap[i][e] += diag_i p[i][e] in place (Ap = K p on entry, the full
 // replicated vector after the all-reduce), and partial[block][e] = sum of p . Ap in the same sweep -- the layout of
 // cg_dot_kernel, so cg_scalars_kernel reads it unchanged.
@@ -243,8 +235,6 @@ static int cg_dots(kmvp_ctx* c, const double* u, const double* v, const Krylov& 
   return KMVP_OK;
 }
 
-static Diag solver_diag(const kmvp_ctx* c) { return Diag{c->diag_n ? (const double*)c->sdiag.p : nullptr, c->diag_ridge}; }
-
 // K applied to the device vector v (N,E) double, N = all points; the result lands in c->out
 // (N,E) double.  With source sharding the Krylov vectors are replicated on every
 // rank, the operator is sharded: this rank's signal is its own slice v[j_offset .. j_offset+M)
@@ -353,9 +343,10 @@ struct BurstGraph {
 };
 
 // The host's part of a device-resident iteration: while it < maxit and rel > rtol, one burst of
-// iterations (`body`, through `graph` when there is one), then a look at the device state (k.stop + 2
-// doubles, read into `state`): the iteration count, `rel` as `rel_of` computes it from the state, and
-// the stop word, set by the device once the tolerance was met inside the burst.
+// iterations (`body`, through `graph` when there is one), then a look at the device state (the k.stop + 2
+// doubles and whatever the solver keeps behind them, read into `state`): the iteration count, `rel` as
+// `rel_of` computes it from the state, and the stop word, set by the device once the tolerance was met
+// inside the burst.
 template <typename Body, typename Rel>
 static int run_bursts(kmvp_ctx* c, const Krylov& k, int maxit, double rtol, int& it, double& rel,
                       std::vector<double>& state, const Body& body, const Rel& rel_of, BurstGraph* graph) {
@@ -364,7 +355,7 @@ static int run_bursts(kmvp_ctx* c, const Krylov& k, int maxit, double rtol, int&
     const int burst = std::min(CG_CHECK, maxit - it);
     if (int rc = graph ? graph->run(c, burst, body) : body(burst)) return rc;
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(state.data(), k.state, sizeof(double) * (k.stop + 2), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(state.data(), k.state, sizeof(double) * state.size(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     it = (int)state[k.stop + 1];  // iterations that changed the iterate
     rel = rel_of();
@@ -402,8 +393,16 @@ static int solver_end(kmvp_ctx* c, const char* method, const double* x, const Kr
 // ------------------------------------------------------------------------------------
 // conjugate gradients
 
+static int pcg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit, double* out_b, int* iters,
+                     double* resid);
+
 int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit,
              double* out_b, int* iters, double* resid) {
+  if (c) {
+    c->last_precond_ms = 0.f;
+    c->pc_used = 0;
+    if (c->precond_rank > 0 && c->N > 0) return pcg_solve(c, kernel, a_host, E, rtol, maxit, out_b, iters, resid);
+  }
   Krylov k;  // x, r, p; state: scal = [rs_old | alpha | beta | |a|^2] x E, stop, iterations
   if (int rc = solver_begin(c, a_host, E, rtol, maxit, out_b, 3, 4 * (size_t)E, k)) return rc;
   if (c->diag_on && c->diag_min < 0.0)
@@ -488,6 +487,139 @@ int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, in
     rel = true_rel;
   }
   return solver_end(c, "conjugate gradients", x, k, out_b, it, true_rel, rtol, iters, resid);
+}
+
+// ------------------------------------------------------------------------------------
+// preconditioned conjugate gradients (kmvp_set_solver_preconditioner): cg_solve's driver around z = P^-1 r
+//   x = 0, r = a, z = P^-1 r, p = z, rho = r . z
+//   alpha = rho / pAp (cg_scalars_kernel's mode 1 and its guards);  x += alpha p;  r -= alpha Ap;  rs = r . r, the stop
+//   test and the count exactly as cg_scalars_kernel's mode 2 makes them;  z = P^-1 r;  rho' = r . z;  beta = rho' / rho
+//   (0 when rho <= 0);  p = z + beta p
+// State: [rho | alpha | beta | |a|^2] x E, stop, iterations -- cg_solve's layout, with rho in the place of rs_old, so that
+// cg_scalars_kernel (mode 1), cg_update_xr_kernel and cg_update_p_kernel (with z for r) serve unchanged -- then rs x E.
+
+// One block.  mode 2 (after r . r): rs[e] = sum, the count and the stop word;  mode 3 (after r . z): beta and rho.
+__global__ void __launch_bounds__(CG_BLOCKS) pcg_scalars_kernel(const double* __restrict__ partial, double* __restrict__ scal,
+                                                               int E, int mode, double rtol) {
+  __shared__ double red[CG_BLOCKS];
+  double* stop = scal + 4 * E;
+  if (*stop != 0.0) return;  // uniform: every thread reads the same word
+  bool not_met = false;
+  for (int e = 0; e < E; ++e) {
+    const double v = block_sum_partials(partial, E, e, red);
+    if (threadIdx.x != 0) continue;
+    if (mode == 2) {
+      scal[4 * E + 2 + e] = v;
+      const double a2 = scal[3 * E + e];
+      if (a2 > 0.0 && !(sqrt(v / a2) <= rtol)) not_met = true;  // NaN / inf: not met
+    } else {
+      const double rho = scal[e];
+      scal[2 * E + e] = rho > 0.0 ? v / rho : 0.0;
+      scal[e] = v;
+    }
+  }
+  if (mode == 2 && threadIdx.x == 0) {
+    scal[4 * E + 1] += 1.0;
+    if (!not_met) *stop = 1.0;
+  }
+}
+
+static int pcg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit, double* out_b, int* iters,
+                     double* resid) {
+  Krylov k;  // x, r, p, z; state: see above; then the apply's scratch
+  const int rank = c->precond_rank;
+  const size_t rs_at = 4 * (size_t)std::max(E, 0) + 2;
+  if (int rc = solver_begin(c, a_host, E, rtol, maxit, out_b, 4, 4 * (size_t)E, k, (size_t)E + precond_scratch(rank, std::max(E, 0))))
+    return rc;
+  if (!c->diag_on || !(c->diag_min > 0.0))
+    return fail(c, KMVP_E_INVALID, "preconditioner: P = L L' + D needs a solver diagonal with ridge + d_i > 0 everywhere (" +
+                                       (c->diag_on ? "smallest: " + std::to_string(c->diag_min) : std::string("none is set")) + ")");
+  if (int rc = precond_prepare(c, kernel)) return rc;
+  c->pc_used = c->pc_built;
+  SolveGuard guard{c};
+  BurstGraph graph(c);
+  const Diag diag = solver_diag(c);
+  const int64_t m = k.m;
+  const size_t vec = k.n * sizeof(double);
+  double *x = k.vec(0), *r = k.vec(1), *p = k.vec(2), *z = k.vec(3), *scal = k.state;
+  double* pc_scratch = scal + rs_at + E;
+  const double* stop = scal + 4 * (size_t)E;
+
+  int rc = load_rhs(c, a_host, r, k);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(x, 0, vec, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::vector<double> anorm2, rs_new;
+  if ((rc = cg_dots(c, r, r, k, anorm2))) return rc;
+
+  auto worst = [&](const double* r2) {
+    double wv = 0.0;
+    for (int e = 0; e < E; ++e) {
+      const double v = anorm2[e] > 0 ? std::sqrt(r2[e] / anorm2[e]) : (anorm2[e] == 0 ? 0.0 : NAN);
+      fold_worst(wv, v);
+    }
+    return wv;
+  };
+
+  std::vector<double> state(rs_at + E, 0.0);
+  for (int e = 0; e < E; ++e) {
+    state[3 * E + e] = anorm2[e];
+    state[rs_at + e] = anorm2[e];
+  }
+  HIP_TRY(c, hipMemcpyAsync(scal, state.data(), sizeof(double) * state.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const unsigned vblocks = blocks_for(m * E);
+  // z = P^-1 r, rho = r . z (and beta, which the start does not use), on the stream
+  auto precondition = [&] {
+    precond_apply(c, r, z, E, pc_scratch, k.partial, CG_BLOCKS, stop);
+    hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, scal, E, 3, rtol);
+  };
+  // the start, and every restart: p = z = P^-1 r with rho = 0 on entry (beta = 0)
+  auto start = [&]() -> int {
+    precondition();
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(p, z, vec, hipMemcpyDeviceToDevice, c->stream));
+    return KMVP_OK;
+  };
+  if ((rc = start())) return rc;
+  auto body = [&](int burst) -> int {
+    for (int i = 0; i < burst; ++i) {
+      if (int rcb = cg_apply(c, kernel, p, k)) return rcb;
+      double* Ap = (double*)c->out.p;
+      hipLaunchKernelGGL(cg_diag_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, p, Ap, diag, m, E, k.partial);
+      hipLaunchKernelGGL(cg_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, scal, E, 1, rtol);
+      hipLaunchKernelGGL(cg_update_xr_kernel, dim3(vblocks), dim3(256), 0, c->stream, x, r, p, Ap, scal, m, E);
+      hipLaunchKernelGGL(cg_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, r, r, m, E, k.partial);
+      hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, scal, E, 2, rtol);
+      precondition();
+      hipLaunchKernelGGL(cg_update_p_kernel, dim3(vblocks), dim3(256), 0, c->stream, p, z, scal, m, E);
+    }
+    return KMVP_OK;
+  };
+  auto rel_of = [&] { return worst(state.data() + rs_at); };
+  int it = 0;
+  double rel = worst(anorm2.data());
+  double true_rel = NAN, prev_true = INFINITY;
+  constexpr int CG_MAX_RESTARTS = 3;  // residual replacement as in cg_solve, with z = P^-1 r, p = z at a restart
+  for (int pass = 0;; ++pass) {
+    if ((rc = run_bursts(c, k, maxit, rtol, it, rel, state, body, rel_of, &graph))) return rc;
+    if ((rc = true_residual(c, kernel, a_host, x, p, k, rs_new))) return rc;  // p = a - A x
+    true_rel = worst(rs_new.data());
+    const bool met = std::isfinite(true_rel) && true_rel <= rtol * 1.5;
+    if (met || !std::isfinite(true_rel) || it >= maxit || pass >= CG_MAX_RESTARTS || !(true_rel <= 0.5 * prev_true)) break;
+    prev_true = true_rel;
+    const double zero = 0.0;
+    std::vector<double> rho0(E, 0.0);
+    HIP_TRY(c, hipMemcpyAsync(r, p, vec, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(scal, rho0.data(), sizeof(double) * E, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(scal + rs_at, rs_new.data(), sizeof(double) * E, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(scal + 4 * (size_t)E, &zero, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((rc = start())) return rc;
+    rel = true_rel;
+  }
+  c->last_total_ms += c->last_precond_ms;  // the build, when it happened in this call
+  return solver_end(c, "preconditioned conjugate gradients", x, k, out_b, it, true_rel, rtol, iters, resid);
 }
 
 
