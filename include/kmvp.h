@@ -493,16 +493,63 @@ int kmvp_set_solver_diagonal(kmvp_ctx* ctx, const double* d_or_null, int64_t n, 
  *   KMVP_E_INVALID with a message that names the preconditioner otherwise.
  *   kmvp_invdist_minres_solve with rank > 0 is KMVP_E_UNSUPPORTED (that matrix is indefinite).  The
  *   kmvp_<kernel>_lanczos_quadrature entries IGNORE the setting (a preconditioned quadrature needs the log det P
- *   correction); products, gradients and everything else are unaffected.
- * kmvp_get_solver_preconditioner: what the LAST kmvp_<kernel>_cg_solve applied -- *rank_built = rank' (0 when it ran
- * unpreconditioned, nothing else is written then), pivots_or_null (rank' values: the point index of every column),
- * factor_or_null ((rank', N) float64 row-major: row t = column t of L).
- * kmvp_last_preconditioner_ms: the build inside the last kmvp_<kernel>_cg_solve, host wall clock (0 when the factor was
- * reused or the preconditioner is off); kmvp_last_total_ms of that solve includes it. */
+ *   correction: the kmvp_<kernel>_lanczos_quadrature_precond entries below make it); products, gradients and everything
+ *   else are unaffected.
+ * kmvp_get_solver_preconditioner: what the LAST kmvp_<kernel>_cg_solve (or kmvp_<kernel>_lanczos_quadrature_precond)
+ * applied -- *rank_built = rank' (0 when it ran unpreconditioned, nothing else is written then), pivots_or_null (rank'
+ * values: the point index of every column), factor_or_null ((rank', N) float64 row-major: row t = column t of L).
+ * kmvp_last_preconditioner_ms: the build inside the last of those calls, host wall clock (0 when the factor was reused or
+ * the preconditioner is off); kmvp_last_total_ms of that call includes it. */
 #define KMVP_PRECOND_MAX_RANK 128
 int kmvp_set_solver_preconditioner(kmvp_ctx* ctx, int rank);
 int kmvp_get_solver_preconditioner(kmvp_ctx* ctx, int* rank_built, int64_t* pivots_or_null, double* factor_or_null);
 double kmvp_last_preconditioner_ms(const kmvp_ctx* ctx);
+
+/* Preconditioned stochastic Lanczos quadrature (an extension): log det A = log det P + tr log M with P = L L' + D the
+ * preconditioner above (rank >= 1 set by kmvp_set_solver_preconditioner, a solver diagonal with ridge + d_i > 0) and
+ * M = P^-1/2 A P^-1/2, which is close to I: fewer iterations than kmvp_<kernel>_lanczos_quadrature by the factor the
+ * preconditioned solve gains, and a smaller variance, since only tr log M is estimated.
+ *   *logdet_p = sum_i log D_i + 2 sum_t log G_tt, G the Cholesky factor of I + L' D^-1 L (matrix-determinant lemma): exact.
+ *   Probes.  g (N,P) and h (rank,P), float64 row-major in every context, are the caller's (Rademacher: E gg' = I,
+ *   E hh' = I); rows t >= rank' of h are not read.  On the device, in float64,
+ *       z[i][e] = sqrt(D_i) g[i][e] + sum_t L[t][i] h[t][e]      (t ascending, one fma per term)
+ *   so that cov z = P and w = P^-1/2 z has E ww' = I.
+ *   Preconditioned conjugate gradients on A x_e = z_e from x = 0 is conjugate gradients on M xh = w: its coefficients
+ *   alpha_k = rho_k / p'Ap, beta_k = rho_{k+1} / rho_k, rho = r' P^-1 r, are the Lanczos tridiagonal of (M, w_e), and
+ *       wnorm2[e] = rho_0 = z_e' P^-1 z_e = |w_e|^2
+ *       logquad[e] = rho_0 sum_i tau_i^2 log(theta_i)  ~  w_e' log(M) w_e      (mean over e: tr log M)
+ *       invquad[e] = pz_e' x_e,  pz = P^-1 z                                    (mean over e: tr A^-1)
+ *   and for any B, E pz' B x = tr(B A^-1).  x (N,P) or NULL: the iterates as they froze; pz (N,P) or NULL: P^-1 z.
+ *   steps, alpha, beta: as kmvp_<kernel>_lanczos_quadrature.
+ *   Every column is on its own clock as there, with rho in the place of rs: it freezes after the first iteration with
+ *   sqrt(rho_k / rho_0) <= rtol -- the residual of the system whose tridiagonal is recorded --, one step earlier on a
+ *   breakdown (p' A p == 0 or rho <= 0); a column with rho_0 == 0 never starts (steps = 0, logquad = invquad = 0, x = 0);
+ *   NaN never freezes a column; no residual replacement, no true-residual product.
+ * Returns KMVP_OK when every non-zero column froze on the tolerance with a finite logquad, otherwise
+ * KMVP_E_NOT_CONVERGED with everything written.  KMVP_E_INVALID: rank == 0 (the message names the preconditioner), no
+ * solver diagonal or ridge + d_i <= 0 somewhere, targets != sources, P < 1, maxit < 0, rtol <= 0, a NULL g, h, logdet_p,
+ * logquad, invquad, wnorm2 or steps; a bfloat16 context is KMVP_E_UNSUPPORTED.  A refused call leaves the factor and the
+ * setting in place.  The factor is built inside the call unless the context holds the current one;
+ * kmvp_get_solver_preconditioner and kmvp_last_preconditioner_ms then speak of this call as they do of a solve.
+ * Device-resident (one look of the host every 8 iterations, the burst replayed as a graph in long runs; the operator
+ * sharded and the vectors replicated with a communicator, the factor built from the full cloud on every rank: every rank
+ * returns the same bits); fixed summation order, no atomics: bitwise reproducible.  There is no inverse-distance entry. */
+int kmvp_gaussian_lanczos_quadrature_precond(kmvp_ctx* ctx, const double* g, const double* h, int P, double rtol, int maxit,
+                                             double* logdet_p, double* logquad, double* invquad, double* wnorm2, int* steps,
+                                             double* x_or_null, double* pz_or_null, double* alpha_or_null,
+                                             double* beta_or_null);
+int kmvp_absexp_lanczos_quadrature_precond(kmvp_ctx* ctx, const double* g, const double* h, int P, double rtol, int maxit,
+                                           double* logdet_p, double* logquad, double* invquad, double* wnorm2, int* steps,
+                                           double* x_or_null, double* pz_or_null, double* alpha_or_null,
+                                           double* beta_or_null);
+int kmvp_matern32_lanczos_quadrature_precond(kmvp_ctx* ctx, const double* g, const double* h, int P, double rtol, int maxit,
+                                             double* logdet_p, double* logquad, double* invquad, double* wnorm2, int* steps,
+                                             double* x_or_null, double* pz_or_null, double* alpha_or_null,
+                                             double* beta_or_null);
+int kmvp_matern52_lanczos_quadrature_precond(kmvp_ctx* ctx, const double* g, const double* h, int P, double rtol, int maxit,
+                                             double* logdet_p, double* logquad, double* invquad, double* wnorm2, int* steps,
+                                             double* x_or_null, double* pz_or_null, double* alpha_or_null,
+                                             double* beta_or_null);
 
 /* Source sharding over the GPUs of one node, one process per GPU:
  * rank 0 calls kmvp_comm_get_unique_id and hands the 128 bytes to every rank

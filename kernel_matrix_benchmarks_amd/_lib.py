@@ -72,6 +72,10 @@ SYMBOLS = [
     ("kmvp_absexp_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
     ("kmvp_matern32_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
     ("kmvp_matern52_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
+    ("kmvp_gaussian_lanczos_quadrature_precond", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 9),
+    ("kmvp_absexp_lanczos_quadrature_precond", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 9),
+    ("kmvp_matern32_lanczos_quadrature_precond", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 9),
+    ("kmvp_matern52_lanczos_quadrature_precond", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 9),
     ("kmvp_gaussian_sinkhorn", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p,
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_absexp_sinkhorn", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p,
@@ -335,6 +339,53 @@ class Context:
         out = {"logquad": logquad, "invquad": invquad, "steps": steps.astype(np.int64), "converged": rc == 0}
         if want_x:
             out["x"] = x
+        if want_coefficients:
+            out["alpha"], out["beta"] = alpha, beta
+        return out
+
+    def lanczos_quadrature_precond(self, kernel, g, h, rtol, maxit, want_x=False, want_pz=False, want_coefficients=False):
+        """Preconditioned stochastic Lanczos quadrature (include/kmvp.h kmvp_<kernel>_lanczos_quadrature_precond) on the
+        probes z = L h + D^1/2 g formed on the device from g (N, P) and h (rank, P), float64, with ``rank`` what
+        set_solver_preconditioner was given (pass it as h's row count).  Returns a dict: logdet_p (float), logquad,
+        invquad, wnorm2 (P float64), steps (P int), converged, and x, pz (N, P) / alpha, beta (maxit, P) when asked for;
+        raises on every status but OK and NOT_CONVERGED."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_lanczos_quadrature_precond,
+            "absolute-exponential": self._lib.kmvp_absexp_lanczos_quadrature_precond,
+            "matern-3/2": self._lib.kmvp_matern32_lanczos_quadrature_precond,
+            "matern-5/2": self._lib.kmvp_matern52_lanczos_quadrature_precond,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no preconditioned Lanczos quadrature for kernel {kernel}")
+        # the library reads N * P and (at most) rank * P doubles from the pointers: shorter arrays must never reach it
+        g, h = np.asarray(g), np.asarray(h)
+        if g.dtype != np.float64 or g.ndim != 2 or g.shape[0] != getattr(self, "N", g.shape[0]) or not g.flags.c_contiguous:
+            raise ValueError(f"g has shape {g.shape} and dtype {g.dtype}, expected a contiguous float64 ({getattr(self, 'N', '?')}, P) array")
+        N, P = g.shape
+        if h.dtype != np.float64 or h.ndim != 2 or h.shape[1] != P or not h.flags.c_contiguous or h.shape[0] > 128:
+            raise ValueError(f"h has shape {h.shape} and dtype {h.dtype}, expected a contiguous float64 (rank, {P}) array")
+        if h.shape[0] < 128:  # the library reads as many rows as the factor has columns, at most the rank it was given (<= 128)
+            h = np.concatenate([h, np.zeros((128 - h.shape[0], P))], axis=0)
+        maxit = int(maxit)
+        logdet_p = ctypes.c_double(0.0)
+        logquad, invquad, wnorm2 = (np.empty(P, dtype=np.float64) for _ in range(3))
+        steps = np.empty(P, dtype=np.intc)
+        x = np.empty((N, P), dtype=np.float64) if want_x else None
+        pz = np.empty((N, P), dtype=np.float64) if want_pz else None
+        alpha = np.empty((max(maxit, 0), P), dtype=np.float64) if want_coefficients else None
+        beta = np.empty((max(maxit, 0), P), dtype=np.float64) if want_coefficients else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = entry(self._ctx, g.ctypes.data, h.ctypes.data, P, float(rtol), maxit, ctypes.addressof(logdet_p),
+                   logquad.ctypes.data, invquad.ctypes.data, wnorm2.ctypes.data, steps.ctypes.data, ptr(x), ptr(pz), ptr(alpha),
+                   ptr(beta))
+        if rc not in (0, 6):
+            self._check(rc)
+        out = {"logdet_p": logdet_p.value, "logquad": logquad, "invquad": invquad, "wnorm2": wnorm2,
+               "steps": steps.astype(np.int64), "converged": rc == 0}
+        if want_x:
+            out["x"] = x
+        if want_pz:
+            out["pz"] = pz
         if want_coefficients:
             out["alpha"], out["beta"] = alpha, beta
         return out

@@ -256,6 +256,18 @@ int kmvp_matern52_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double r
   return cg_lanczos(c, K_MATERN52, z, P, rtol, maxit, logquad, invquad, steps, x, alpha, beta);
 }
 
+#define KMVP_LANCZOS_PRECOND_ENTRY(NAME, K)                                                                                  \
+  int kmvp_##NAME##_lanczos_quadrature_precond(kmvp_ctx* c, const double* g, const double* h, int P, double rtol, int maxit,  \
+                                               double* logdet_p, double* logquad, double* invquad, double* wnorm2,           \
+                                               int* steps, double* x, double* pz, double* alpha, double* beta) {             \
+    return cg_lanczos_precond(c, K, g, h, P, rtol, maxit, logdet_p, logquad, invquad, wnorm2, steps, x, pz, alpha, beta);    \
+  }
+KMVP_LANCZOS_PRECOND_ENTRY(gaussian, K_GAUSSIAN)
+KMVP_LANCZOS_PRECOND_ENTRY(absexp, K_ABSEXP)
+KMVP_LANCZOS_PRECOND_ENTRY(matern32, K_MATERN32)
+KMVP_LANCZOS_PRECOND_ENTRY(matern52, K_MATERN52)
+#undef KMVP_LANCZOS_PRECOND_ENTRY
+
 int kmvp_gaussian_sinkhorn(kmvp_ctx* c, const double* log_a, const double* log_b, double tol, int maxit, double* u, double* v,
                            int* iters, double* err) {
   return sinkhorn_solve(c, K_GAUSSIAN, log_a, log_b, tol, maxit, u, v, iters, err);

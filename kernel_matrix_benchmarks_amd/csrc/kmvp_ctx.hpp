@@ -137,11 +137,12 @@ struct kmvp_ctx {
   DevBuf precond;               // residual diagonal, 1 / (ridge + d_i), the factor L [rank][N], pivots, Gram matrix and its factor
   int precond_rank = 0;         // as requested: 0 = off
   int pc_built = 0;             // columns the factor in `precond` holds (<= pc_rank)
-  int pc_used = 0;              // columns the last kmvp_<kernel>_cg_solve applied (0: it ran unpreconditioned)
+  int pc_used = 0;              // columns the last kmvp_<kernel>_cg_solve or _lanczos_quadrature_precond applied (0: it ran unpreconditioned)
   int pc_kernel = -1, pc_rank = 0;  // what the factor was built for, with the versions below (pc_points_ver 0: no factor)
   uint64_t pc_points_ver = 0, pc_diag_ver = 0;
   uint64_t diag_ver = 0;        // counts kmvp_set_solver_diagonal
-  float last_precond_ms = 0.f;  // the build inside the last kmvp_<kernel>_cg_solve (0: reused, or off)
+  float last_precond_ms = 0.f;  // the build inside the last kmvp_<kernel>_cg_solve or _lanczos_quadrature_precond (0: reused, or off)
+  double pc_logdet_c = 0.0;     // log det (I + L' D^-1 L) of the factor in `precond`, from its Cholesky factor (pc_logdet)
   // Sinkhorn (kmvp_sinkhorn.hip): layouts of its own for both directions -- target image of x with records of y, target
   // image of y with records of x (the record's signal slot carries potential + log-weight) -- and the fp64 state
   DevBuf sk_xs_x, sk_rec_y, sk_xs_y, sk_rec_x, sk_state;
@@ -244,6 +245,12 @@ inline size_t precond_scratch(int R, int E) { return (size_t)(PC_APPLY_BLOCKS + 
 // `rz_blocks` workgroups of 256).  Three launches on the context's stream; nothing once *stop != 0.
 void precond_apply(kmvp_ctx* c, const double* r, double* z, int E, double* scratch, double* rz_partial, int rz_blocks,
                    const double* stop);
+// The probes of the preconditioned quadrature, z[i][e] = sqrt(D_i) g[i][e] + sum_t L[t][i] h[t][e] (t ascending over the
+// columns built, one fma per term) for the device arrays g (N, P) and h (rank', P); one launch on the context's stream.
+void precond_probes(kmvp_ctx* c, const double* g, const double* h, int P, double* z);
+constexpr int PC_LOGD_BLOCKS = 64;  // workgroups of the partial sums of log D_i
+// out[PC_LOGD_BLOCKS] = sum_i log D_i, the partial sums out[0 .. PC_LOGD_BLOCKS) added in workgroup order; two launches
+void precond_logdiag(kmvp_ctx* c, double* out);
 // kmvp_get_solver_preconditioner
 int precond_read(kmvp_ctx* c, int* rank_built, int64_t* pivots, double* factor);
 
@@ -254,6 +261,9 @@ int minres_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol
                  double* out_b, int* iters, double* resid);
 int cg_lanczos(kmvp_ctx* c, int kernel, const void* z_host, int P, double rtol, int maxit, double* logquad, double* invquad,
                int* steps, double* x_out, double* alpha_out, double* beta_out);
+int cg_lanczos_precond(kmvp_ctx* c, int kernel, const double* g_host, const double* h_host, int P, double rtol, int maxit,
+                       double* logdet_p, double* logquad, double* invquad, double* wnorm2, int* steps, double* x_out,
+                       double* pz_out, double* alpha_out, double* beta_out);
 
 // kmvp_sinkhorn.hip: kmvp_<kernel>_sinkhorn, the device-resident Sinkhorn iteration on lowd_lse_kernel
 int sinkhorn_solve(kmvp_ctx* c, int kernel, const double* log_a, const double* log_b, double tol, int maxit, double* u,

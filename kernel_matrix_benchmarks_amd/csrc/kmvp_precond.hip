@@ -19,6 +19,11 @@
 //   pc_solve_kernel    one workgroup: the partials added in workgroup order, C w = t per column by substitution, 16 rows
 //                      at a time
 //   pc_finish_kernel   z_i = (r_i - sum_t L[t][i] w_t) / D_i and the partials of r . z
+//
+// The preconditioned Lanczos quadrature (kmvp_<kernel>_lanczos_quadrature_precond; driver: cg_lanczos_precond) takes from here
+//   pc_probe_kernel    the probes z = D^1/2 g + L h, whose covariance is P for Rademacher g and h
+//   pc_logd_kernel, pc_logd_fold_kernel   sum_i log D_i, which with log det C off the Cholesky factor (pc_logdet, kept at the
+//                      build) is log det P
 #include <chrono>
 
 #include "kmvp_ctx.hpp"
@@ -276,6 +281,7 @@ int precond_prepare(kmvp_ctx* c, int kernel) {
     return fail(c, KMVP_E_INVALID, "preconditioner: I + L' D^-1 L is not positive definite (non-finite points or diagonal?)");
   HIP_TRY(c, hipMemcpyAsync(buf + lay.chol, gram.data(), sizeof(double) * gram.size(), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // gram is a local
+  c->pc_logdet_c = pc_logdet(gram.data(), built, R);
   c->pc_built = built;
   c->pc_kernel = kernel;
   c->pc_rank = R;
@@ -417,6 +423,61 @@ void precond_apply(kmvp_ctx* c, const double* r, double* z, int E, double* scrat
                      buf + lay.chol, R, lay.R, E, stop, w);
   hipLaunchKernelGGL(pc_finish_kernel, dim3(rz_blocks), dim3(PC_THREADS), 0, c->stream, buf + lay.L, lay.n, R, r,
                      (const double*)w, solver_diag(c), E, stop, z, rz_partial);
+}
+
+// ------------------------------------------------------------------------------------
+// the preconditioned quadrature's share (kmvp_<kernel>_lanczos_quadrature_precond): probes with covariance P, log det D
+
+// z[i][e] = sqrt(D_i) g[i][e] + sum_t L[t][i] h[t][e], t ascending, one fma per term.  One thread per (i, e): a workgroup
+// is 256 consecutive points of one column (blockIdx.y), so a row of L is read coalesced and h[t][e] is uniform.
+__global__ void __launch_bounds__(PC_THREADS) pc_probe_kernel(const double* __restrict__ L, int64_t n, int R, Diag diag,
+                                                               const double* __restrict__ g, const double* __restrict__ h,
+                                                               int P, double* __restrict__ z) {
+  const int64_t i = (int64_t)blockIdx.x * PC_THREADS + threadIdx.x;
+  const int e = blockIdx.y;
+  if (i >= n) return;
+  double acc = sqrt(diag.at(i)) * g[i * P + e];
+  for (int t = 0; t < R; ++t) acc = fma(L[(int64_t)t * n + i], h[(int64_t)t * P + e], acc);
+  z[i * P + e] = acc;
+}
+
+// part[block] = sum of log D_i over the block's contiguous run of points (pc_gram_kernel's mapping): every thread its
+// strided share in ascending i, then the tree over the 256 threads.
+__global__ void __launch_bounds__(PC_THREADS) pc_logd_kernel(Diag diag, int64_t n, int64_t chunk, double* __restrict__ part) {
+  __shared__ double red[PC_THREADS];
+  const int64_t i0 = (int64_t)blockIdx.x * chunk;
+  const int64_t i1 = i0 + chunk < n ? i0 + chunk : n;
+  double acc = 0.0;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += PC_THREADS) acc += log(diag.at(i));
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = PC_THREADS / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+// part[nblocks] = the partial sums in block order
+__global__ void pc_logd_fold_kernel(double* __restrict__ part, int nblocks) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double v = 0.0;
+  for (int b = 0; b < nblocks; ++b) v += part[b];
+  part[nblocks] = v;
+}
+
+void precond_probes(kmvp_ctx* c, const double* g, const double* h, int P, double* z) {
+  const PcLayout lay(c->N, c->pc_rank);
+  const double* buf = (const double*)c->precond.p;
+  hipLaunchKernelGGL(pc_probe_kernel, dim3(lay.nb, P), dim3(PC_THREADS), 0, c->stream, buf + lay.L, lay.n, c->pc_built,
+                     solver_diag(c), g, h, P, z);
+}
+
+void precond_logdiag(kmvp_ctx* c, double* out) {
+  const int64_t n = c->N;
+  const int64_t chunk = (n + PC_LOGD_BLOCKS - 1) / PC_LOGD_BLOCKS;
+  hipLaunchKernelGGL(pc_logd_kernel, dim3(PC_LOGD_BLOCKS), dim3(PC_THREADS), 0, c->stream, solver_diag(c), n, chunk, out);
+  hipLaunchKernelGGL(pc_logd_fold_kernel, dim3(1), dim3(64), 0, c->stream, out, PC_LOGD_BLOCKS);
 }
 
 int precond_read(kmvp_ctx* c, int* rank_built, int64_t* pivots, double* factor) {

@@ -3,7 +3,7 @@
 //
 // P = L L' + D is applied through the Woodbury identity, P^-1 r = D^-1 r - D^-1 L C^-1 L' D^-1 r with the R x R matrix
 // C = I + L' D^-1 L, R <= 128.  C is symmetric positive definite: pc_cholesky() factors it once per build, C = G G', and
-// every apply solves C w = t by pc_forward() (G y = t) and pc_backward() (G' w = y).
+// every apply solves C w = t by pc_forward() (G y = t) and pc_backward() (G' w = y); pc_logdet() reads log det C off G.
 //
 // Plain C++ with the device attributes behind a macro: the same text runs on the host for the build, in pc_solve_kernel
 // (kmvp_precond.hip) for the apply -- there on the 16 x 16 diagonal blocks of the factor -- and, compiled with a host
@@ -55,6 +55,14 @@ KMVP_HD inline void pc_backward(const double* g, int n, int ld, double* v, int s
     for (int k = i + 1; k < n; ++k) s = __builtin_fma(-g[k * ld + i], v[k * stride], s);
     v[i * stride] = s / g[i * ld + i];
   }
+}
+
+// log det (G G') = 2 sum_t log G_tt of a factor pc_cholesky() left, added in ascending t: the factor's share of
+// log det P = sum_i log D_i + log det (I + L' D^-1 L) (the matrix-determinant lemma; kmvp_<kernel>_lanczos_quadrature_precond)
+KMVP_HD inline double pc_logdet(const double* g, int n, int ld) {
+  double s = 0.0;
+  for (int t = 0; t < n; ++t) s += __builtin_log(g[t * ld + t]);
+  return 2.0 * s;
 }
 
 }  // namespace kmvp

@@ -803,6 +803,132 @@ int cg_lanczos(kmvp_ctx* c, int kernel, const void* z_host, int P, double rtol, 
   return KMVP_OK;
 }
 
+// cg_lanczos around z = P^-1 r, as pcg_solve is cg_solve around it (include/kmvp.h kmvp_<kernel>_lanczos_quadrature_precond):
+//   z = L h + D^1/2 g;  x = 0, r = z, pz = P^-1 z, p = pz, rho_0 = z . pz
+//   alpha = rho / pAp;  x += alpha p;  r -= alpha Ap;  zr = P^-1 r;  rho' = r . zr;  beta = rho' / rho;  p = zr + beta p
+// in the live columns.  These are the coefficients of conjugate gradients on M xh = w, M = P^-1/2 A P^-1/2, w = P^-1/2 z,
+// whose residual norm is sqrt(rho): the state is LZ_* with rho in LZ_RS and rho_0 in LZ_Z2, so lanczos_scalars_kernel --
+// mode 1 after p . Ap, mode 2 after the partials of r . zr that precond_apply leaves -- and the two update kernels (with zr
+// for r in lanczos_update_p_kernel) serve unchanged, and the column freezes on sqrt(rho / rho_0) <= rtol without a dot
+// product of its own.  Five Krylov vectors: pz is kept for invquad = pz . x and for the caller's trace estimates.
+int cg_lanczos_precond(kmvp_ctx* c, int kernel, const double* g_host, const double* h_host, int P, double rtol, int maxit,
+                       double* logdet_p, double* logquad, double* invquad, double* wnorm2, int* steps, double* x_out,
+                       double* pz_out, double* alpha_out, double* beta_out) {
+  if (c && (!h_host || !logdet_p || !logquad || !invquad || !wnorm2 || !steps)) return fail(c, KMVP_E_INVALID, "bad solver arguments");
+  if (c && c->dtype == KMVP_BF16 && c->have_points)
+    return fail(c, KMVP_E_UNSUPPORTED, "the Lanczos quadrature needs a float32 or float64 context");
+  Krylov k;  // x, r, p, zr, pz; state: LZ_FIELDS x P, stop, iterations; alpha and beta of every iteration, (maxit, P) each; the
+             // partial sums of log D_i and their sum; the apply's scratch
+  const int rank = c ? c->precond_rank : 0;
+  const size_t rows = (size_t)std::max(maxit, 0) * (size_t)std::max(P, 0);
+  if (int rc = solver_begin(c, g_host, P, rtol, maxit, logquad, 5, (size_t)LZ_FIELDS * P, k,
+                            2 * rows + PC_LOGD_BLOCKS + 1 + precond_scratch(rank, std::max(P, 0))))
+    return rc;
+  if (rank < 1)
+    return fail(c, KMVP_E_INVALID, "preconditioner: the preconditioned Lanczos quadrature needs kmvp_set_solver_preconditioner with rank >= 1");
+  if (!c->diag_on || !(c->diag_min > 0.0))
+    return fail(c, KMVP_E_INVALID, "preconditioner: P = L L' + D needs a solver diagonal with ridge + d_i > 0 everywhere (" +
+                                       (c->diag_on ? "smallest: " + std::to_string(c->diag_min) : std::string("none is set")) + ")");
+  if (c->N < 1) return fail(c, KMVP_E_INVALID, "preconditioner: the cloud is empty");
+  c->last_precond_ms = 0.f;
+  if (int rc = precond_prepare(c, kernel)) return rc;
+  c->pc_used = c->pc_built;
+  SolveGuard guard{c};
+  BurstGraph graph(c);
+  const Diag diag = solver_diag(c);
+  const int64_t m = k.m;
+  const size_t vec = k.n * sizeof(double);
+  double *x = k.vec(0), *r = k.vec(1), *p = k.vec(2), *zr = k.vec(3), *pz = k.vec(4), *st = k.state;
+  double *hist_alpha = st + k.stop + 2, *hist_beta = hist_alpha + rows;
+  double *logd = hist_alpha + 2 * rows, *pc_scratch = logd + PC_LOGD_BLOCKS + 1;
+  const double* stop = st + k.stop;
+  HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
+
+  // g in x's place and the rows of h that have a column in the apply's scratch, until the probes are formed: r = z;
+  // then x = 0, history = 0, the state's stop word = 0 (the apply reads it), pz = P^-1 z with the partials of z . pz, p = pz
+  HIP_TRY(c, hipMemcpyAsync(x, g_host, vec, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(pc_scratch, h_host, sizeof(double) * (size_t)c->pc_built * P, hipMemcpyHostToDevice, c->stream));
+  precond_probes(c, x, pc_scratch, P, r);
+  precond_logdiag(c, logd);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemsetAsync(x, 0, vec, c->stream));
+  HIP_TRY(c, hipMemsetAsync(st, 0, sizeof(double) * (k.stop + 2 + 2 * rows), c->stream));
+  precond_apply(c, r, pz, P, pc_scratch, k.partial, CG_BLOCKS, stop);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(p, pz, vec, hipMemcpyDeviceToDevice, c->stream));
+  std::vector<double> host_partial((size_t)CG_BLOCKS * P), rho0(P, 0.0), pzx;
+  double sum_logd = 0.0;
+  HIP_TRY(c, hipMemcpyAsync(host_partial.data(), k.partial, sizeof(double) * host_partial.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&sum_logd, logd + PC_LOGD_BLOCKS, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < CG_BLOCKS; ++b)  // as cg_dots adds them
+    for (int e = 0; e < P; ++e) rho0[e] += host_partial[(size_t)b * P + e];
+
+  std::vector<double> state(k.stop + 2, 0.0);
+  for (int e = 0; e < P; ++e) {
+    state[(size_t)LZ_RS * P + e] = rho0[e];
+    state[(size_t)LZ_Z2 * P + e] = rho0[e];
+    state[(size_t)LZ_FROZEN * P + e] = rho0[e] == 0.0 ? LZ_ZERO : LZ_LIVE;
+  }
+  HIP_TRY(c, hipMemcpyAsync(st, state.data(), sizeof(double) * state.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const unsigned vblocks = blocks_for(m * P);
+  auto body = [&](int burst) -> int {
+    for (int i = 0; i < burst; ++i) {
+      if (int rcb = cg_apply(c, kernel, p, k)) return rcb;
+      double* Ap = (double*)c->out.p;
+      hipLaunchKernelGGL(cg_diag_dot_kernel, dim3(CG_BLOCKS), dim3(256), 0, c->stream, p, Ap, diag, m, P, k.partial);
+      hipLaunchKernelGGL(lanczos_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, st, P, 1, rtol, hist_alpha,
+                         hist_beta, maxit);
+      hipLaunchKernelGGL(lanczos_update_xr_kernel, dim3(vblocks), dim3(256), 0, c->stream, x, r, p, Ap, st, m, P);
+      precond_apply(c, r, zr, P, pc_scratch, k.partial, CG_BLOCKS, stop);  // zr = P^-1 r and the partials of r . zr
+      hipLaunchKernelGGL(lanczos_scalars_kernel, dim3(1), dim3(CG_BLOCKS), 0, c->stream, k.partial, st, P, 2, rtol, hist_alpha,
+                         hist_beta, maxit);
+      hipLaunchKernelGGL(lanczos_update_p_kernel, dim3(vblocks), dim3(256), 0, c->stream, p, zr, st, m, P);
+    }
+    return KMVP_OK;
+  };
+  auto rel_of = [&] {
+    for (int e = 0; e < P; ++e)
+      if (state[(size_t)LZ_FROZEN * P + e] == LZ_LIVE) return (double)INFINITY;
+    return 0.0;
+  };
+  int it = 0;
+  double rel = rel_of();
+  if (int rc = run_bursts(c, k, maxit, rtol, it, rel, state, body, rel_of, &graph)) return rc;
+
+  if (int rc = cg_dots(c, pz, x, k, pzx)) return rc;
+  std::vector<double> hist(2 * rows);
+  HIP_TRY(c, hipMemcpyAsync(state.data(), st, sizeof(double) * state.size(), hipMemcpyDeviceToHost, c->stream));
+  if (rows) HIP_TRY(c, hipMemcpyAsync(hist.data(), hist_alpha, sizeof(double) * 2 * rows, hipMemcpyDeviceToHost, c->stream));
+  if (x_out) HIP_TRY(c, hipMemcpyAsync(x_out, x, vec, hipMemcpyDeviceToHost, c->stream));
+  if (pz_out) HIP_TRY(c, hipMemcpyAsync(pz_out, pz, vec, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
+  c->last_kernel_ms = c->last_total_ms;  // both cover the iteration; the total also the build, when it happened in this call
+  c->last_total_ms += c->last_precond_ms;
+
+  *logdet_p = sum_logd + c->pc_logdet_c;
+  bool ok = true;
+  for (int e = 0; e < P; ++e) {
+    const double frozen = state[(size_t)LZ_FROZEN * P + e];
+    steps[e] = (int)state[(size_t)LZ_STEPS * P + e];
+    wnorm2[e] = rho0[e];
+    logquad[e] = rho0[e] * lanczos_quadrature_log(hist.data() + e, hist.data() + rows + e, steps[e], P);
+    invquad[e] = pzx[e];
+    if (frozen != LZ_ZERO && !(frozen == LZ_TOLERANCE && std::isfinite(logquad[e]))) ok = false;
+  }
+  if (alpha_out && rows) memcpy(alpha_out, hist.data(), sizeof(double) * rows);
+  if (beta_out && rows) memcpy(beta_out, hist.data() + rows, sizeof(double) * rows);
+  if (!ok) {
+    c->err = "preconditioned Lanczos quadrature: a column did not reach the requested tolerance on the recurrence residual, "
+             "or its quadrature is not finite (operator not positive definite, non-finite operator or probe)";
+    return KMVP_E_NOT_CONVERGED;
+  }
+  return KMVP_OK;
+}
+
 
 // ------------------------------------------------------------------------------------
 // MINRES (Paige & Saunders) for the symmetric INDEFINITE inverse-distance systems (zero
