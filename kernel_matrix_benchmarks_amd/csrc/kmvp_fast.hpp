@@ -60,6 +60,7 @@ struct FastArgs {
   const unsigned char* img;  // source stages [m_stages][stage_bytes]
   double* part;              // partial sums [segments][NE][n_pad]
   int64_t n_pad;
+  int64_t m;                 // sources of this context (a slice of m_total when the sources are sharded)
   int64_t m_tiles;           // source tiles of 32
   int64_t m_stages;          // source stages of fast_stage_tiles(KS) tiles
   int64_t seg_stages;        // stages per segment
@@ -73,6 +74,7 @@ struct FastArgs {
                              // sqrt turns that into 3e-4 R)
 };
 
+// (kexp2 is the bare v_exp_f32: a kernel value below 2^-126, i.e. k < e^-87.3, comes back as 0, not as a denormal)
 template <int KERNEL>
 __device__ __forceinline__ float fast_kval(float s) {
   if constexpr (KERNEL == K_GAUSSIAN) {
@@ -176,7 +178,9 @@ __global__ void __launch_bounds__(BLOCK_THREADS) fast_kernel(const FastArgs a) {
     fast_target_operand<D, 0>(xb[tt], h, hi, mid, lo);
     if (KERNEL == K_INVDIST || (KERNEL == K_ABSEXP && a.same_points)) {
       const int64_t g = ((tile0 + tt) * FAST_TILE + r) % (a.m_total + 1);  // (same points: the target's own index)
-      jz[tt] = (g < a.m_total) ? g - a.j_offset : (int64_t)-1;
+      // (only a LIVE source of this slice: a pad row behind the slice's last source has b = 0 but density adds k itself,
+      // and exp(-r)'s own-pair rule would give it k = 1)
+      jz[tt] = (g < a.m_total && g - a.j_offset < a.m) ? g - a.j_offset : (int64_t)-1;
     } else {
       jz[tt] = -1;
     }

@@ -996,6 +996,7 @@ int run_product_fast(kmvp_ctx* c, int kernel, int sig) {
   a.xr = (const float*)c->xs.p;
   a.img = (const unsigned char*)c->rec.p;
   a.part = (double*)c->part.p;
+  a.m = M;
   a.m_tiles = m_tiles;
   a.chunk_stages = std::max(1, c->opt_chunk / (FAST_TILE * ST));
   a.j_offset = c->j_offset;

@@ -111,6 +111,65 @@ def chain_length(path, D, M, chunk=512, seg_len=None):
     return max(1, min(n, seg_len if seg_len else M, M if M else 1))
 
 
+def kernel_constant(kernel):
+    """scale_for: the constant the float32 paths fold into the coordinates."""
+    return C_GAUSSIAN if kernel == "gaussian" else (C_ABSEXP if kernel == "absolute-exponential" else 1.0)
+
+
+def cloud_geometry(y, xa, same):
+    """What the kernels see of the clouds: the midpoint and half-diagonal of the bounding box of both (measure_clouds),
+    the diameter of the sources' box."""
+    D = y.shape[1]
+    pts = np.concatenate((y, xa)) if not same else y
+    fin = np.isfinite(pts).all(axis=1)
+    lo = pts[fin].min(axis=0) if fin.any() else np.zeros(D)
+    hi = pts[fin].max(axis=0) if fin.any() else np.zeros(D)
+    radius2 = float((((hi - lo) / 2) ** 2).sum())
+    yf = np.isfinite(y).all(axis=1)
+    ydiam = float(np.sqrt(((y[yf].max(axis=0) - y[yf].min(axis=0)) ** 2).sum())) if yf.any() else 0.0
+    return dict(radius2=radius2, ydiam=ydiam, mid=0.5 * (lo + hi))
+
+
+def expansion_error(x, y, mid, c, r, tail, t_extra=0.0):
+    """e_S of the expansion around one centre (fast_kernel, fastmm_kernel), in scaled units: the k-ordered chain -- 6 D
+    roundings of partials <= A, then `tail` roundings of partials <= T_abs = |x'|^2 + |y'|^2 + A + t_extra -- and the
+    operands' roundings (the docstring's first two items).  (The centre is bounded, not restated.)"""
+    u = U_RNE
+    D = y.shape[1]
+    nx = ((x - mid) ** 2).sum(1)[:, None] * c * c
+    ny = ((y - mid) ** 2).sum(1)[None, :] * c * c
+    A = 2 * (np.abs(x - mid) * c) @ (np.abs(y - mid) * c).T  # any prefix of the 6 D product columns
+    Tabs = nx + ny + A + t_extra
+    return u * (6 * D * A + tail * Tabs) + 4 * u * r * (np.sqrt(nx) + np.sqrt(ny)) \
+        + (u + 2.0 ** -27) * (nx + ny) + U_ACC * A / 2
+
+
+def centred_error(r, ss, ydiam, c, D):
+    """e_S of the expansion around the Morton group's centre (cfast_kernel, cfastmm_kernel), recomputed or not."""
+    # a pair the kernel does not recompute has S > tau_g = CF_KAPPA R_g^2, so R_g^2 < S / CF_KAPPA; and
+    # R_g <= Dy.  |x''| <= sqrt(s) + R_g, |y''| <= R_g: T_abs <= (sqrt(s) + 2 R_g)^2
+    u = U_RNE
+    dy2 = (ydiam * c) ** 2
+    t0 = u * 34 * (r + 2 * np.sqrt(dy2)) ** 2
+    rg2 = np.minimum(dy2, (ss + t0) / CF_KAPPA)
+    Tabs = (r + 2 * np.sqrt(rg2)) ** 2
+    e_nr = u * 34 * Tabs + 8 * u * r * np.sqrt(Tabs) + 2 * u * Tabs
+    return np.maximum(e_nr, _gamma(D + 1) * ss)                    # recomputed or not: either bound
+
+
+def absexp_log_error(e_s, r, arg=0.0):
+    """L of exp(-r) from the bound e_s on S: |sqrt S - r| <= min(sqrt e_s, e_s / r), v_sqrt_f32 and v_exp_f32 at 2 ulp;
+    `arg`: what forming the exponent's argument in fp32 adds (log2 units)."""
+    dr = np.minimum(np.sqrt(e_s), e_s / r) + TRANS * (r + np.sqrt(e_s)) + arg
+    return np.log(2.0) * dr + TRANS
+
+
+def invdist_log_error(ratio):
+    """L of 1/r from ratio = e_s / s: rsq(S) / rsq(s) <= 1 / sqrt(1 - ratio) (no linearisation); v_rsq_f32 at 2 ulp.
+    (ratio is capped at 1/2: rows with such pairs are flagged by every caller.)"""
+    return -0.5 * np.log1p(-np.minimum(ratio, 0.5)) + TRANS
+
+
 def f32mm_product(kernel, y, x=None, b=None, normalize_rows=False, *, path="fastmm", online=None, rows=None, chunk=512,
                   seg_len=None, j_offset=0, M_total=None, rounding=True):
     """Modelled result of run_product_fastmm / run_product_cfastmm and its per-element band.
@@ -129,15 +188,7 @@ def f32mm_product(kernel, y, x=None, b=None, normalize_rows=False, *, path="fast
     rows = np.arange(xa.shape[0], dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64)
     M, D = y.shape
     b = np.ones((M, 1)) if b is None else np.asarray(b, dtype=np.float64)
-    # what the kernels see of the clouds: the midpoint and half-diagonal of the bounding box of both (measure_clouds)
-    pts = np.concatenate((y, xa)) if not same else y
-    fin = np.isfinite(pts).all(axis=1)
-    lo = pts[fin].min(axis=0) if fin.any() else np.zeros(D)
-    hi = pts[fin].max(axis=0) if fin.any() else np.zeros(D)
-    radius2 = float((((hi - lo) / 2) ** 2).sum())
-    yf = np.isfinite(y).all(axis=1)
-    ydiam = float(np.sqrt(((y[yf].max(axis=0) - y[yf].min(axis=0)) ** 2).sum())) if yf.any() else 0.0
-    geo = dict(radius2=radius2, ydiam=ydiam, mid=0.5 * (lo + hi))
+    geo = cloud_geometry(y, xa, same)
     block = max(1, 2 ** 21 // max(1, M))
     parts = [_block(kernel, y, xa, b, normalize_rows, path, online, rows[r0:r0 + block], chunk, seg_len, j_offset, M_total,
                     rounding, geo) for r0 in range(0, max(len(rows), 1), block)]
@@ -194,24 +245,19 @@ def _block(kernel, y, xa, b, normalize_rows, path, online, rows, chunk, seg_len,
             e_s = u * (6 * D * A + 3 * (A + FMM_SHIFT + kop)) + 2 * u * A + U_ACC * A
             L = np.log(2.0) * e_s + TRANS
         else:
-            c = C_GAUSSIAN if kernel == "gaussian" else (C_ABSEXP if kernel == "absolute-exponential" else 1.0)
+            c = kernel_constant(kernel)
             ss = s * c * c                                          # scaled squared distance
             r = np.sqrt(ss)
             e_exact = _gamma(D + 1) * ss
             if path == "fastmm":
-                mid = geo["mid"]                                    # (the centre is bounded, not restated)
-                nx = ((x - mid) ** 2).sum(1)[:, None] * c * c
-                ny = ((y - mid) ** 2).sum(1)[None, :] * c * c
-                A = 2 * (np.abs(x - mid) * c) @ (np.abs(y - mid) * c).T  # any prefix of the 6 D product columns
-                Tabs = nx + ny + A
+                t_extra = 0.0
                 if kernel == "gaussian":
                     smax = np.max(np.where(np.isfinite(ss), ss, 0.0), axis=1, keepdims=True) if M else np.zeros((n, 1))
                     kopg = (smax + 1.0) if online else 0.0         # |kop| <= the row's largest exponent + 1
-                    Tabs = Tabs + FMM_SHIFT + kopg
+                    t_extra = FMM_SHIFT + kopg
                 # k-ordered chain: 6 D roundings of partials <= A, then 9 of partials <= Tabs (norm pieces, shift
                 # columns); the online rescale's fp32 add: one more
-                e_exp = u * (6 * D * A + 10 * Tabs) + 4 * u * r * (np.sqrt(nx) + np.sqrt(ny)) \
-                    + (u + 2.0 ** -27) * (nx + ny) + U_ACC * A / 2
+                e_exp = expansion_error(x, y, geo["mid"], c, r, 10, t_extra)
                 if kernel == "gaussian":
                     e_s = e_exp
                 else:                                               # exp(-r): the closest pairs recomputed
@@ -219,23 +265,15 @@ def _block(kernel, y, xa, b, normalize_rows, path, online, rows, chunk, seg_len,
                     sure = ss + e_exp <= 0.5 * tau
                     e_s = np.where(sure, e_exact, np.where(ss - e_exp > 2.0 * tau, e_exp, np.maximum(e_exp, e_exact)))
             else:
-                # a pair the kernel does not recompute has S > tau_g = CF_KAPPA R_g^2, so R_g^2 < S / CF_KAPPA; and
-                # R_g <= Dy.  |x''| <= sqrt(s) + R_g, |y''| <= R_g: T_abs <= (sqrt(s) + 2 R_g)^2
-                dy2 = (geo["ydiam"] * c) ** 2
-                t0 = u * 34 * (r + 2 * np.sqrt(dy2)) ** 2
-                rg2 = np.minimum(dy2, (ss + t0) / CF_KAPPA)
-                Tabs = (r + 2 * np.sqrt(rg2)) ** 2
-                e_nr = u * 34 * Tabs + 8 * u * r * np.sqrt(Tabs) + 2 * u * Tabs
-                e_s = np.maximum(e_nr, e_exact)                     # recomputed or not: either bound
+                e_s = centred_error(r, ss, geo["ydiam"], c, D)
             if kernel == "gaussian":
                 L = np.log(2.0) * e_s + TRANS
             elif kernel == "absolute-exponential":
                 kopa = np.max(np.where(np.isfinite(r), r, 0.0), axis=1, keepdims=True) + 1.0 if M else 1.0
-                dr = np.minimum(np.sqrt(e_s), e_s / r) + TRANS * (r + np.sqrt(e_s)) + u * (FMM_SHIFT + kopa + r)
-                L = np.log(2.0) * dr + TRANS
+                L = absexp_log_error(e_s, r, u * (FMM_SHIFT + kopa + r))
             else:
                 ratio = e_s / ss
-                L = -0.5 * np.log1p(-np.minimum(ratio, 0.5)) + TRANS
+                L = invdist_log_error(ratio)
                 live = kf != 0.0
                 flagged |= ((ratio > FLAG_1R) & live).any(axis=1)
         L = np.where(np.isfinite(L), L, 0.0)
