@@ -136,7 +136,7 @@ int kmvp_expdot_norm(kmvp_ctx* ctx);
  * signal columns at D <= 8 in blocks of four); sharded like the others (no index-based rule: j_offset / M_total do not
  * enter the values).  KMVP_E_UNSUPPORTED for bfloat16 contexts and when "fast_sqdists" asks for a matrix-core form
  * (1 .. 4) explicitly: none is built for them; the default -1 and 0 take the difference form, and
- * kmvp_last_dispatch_note is "". */
+ * kmvp_last_dispatch_note is "" (but for the pair it names when "targets_per_lane" or "feed" is set). */
 int kmvp_matern32(kmvp_ctx* ctx);
 int kmvp_matern32_norm(kmvp_ctx* ctx);
 int kmvp_matern52(kmvp_ctx* ctx);
@@ -641,7 +641,9 @@ const char* kmvp_last_kernel_name(const kmvp_ctx* ctx);
 /* The fastest forms are narrow (kmvp_set_option "fast_sqdists").  When the last product did NOT take the cell form
  * although kernel, precision and dimension would allow it, this says which condition failed (too few points per
  * cloud, too few points per grid cell, the radius rule, ...); "" when nothing faster applied.  get_additional()
- * stores it as "dispatch_note". */
+ * stores it as "dispatch_note".  When "targets_per_lane" or "feed" is set and lowd_kernel serves the product, the note
+ * also ends in "lowd_kernel runs targets_per_lane = T, feed = F": only D = 3 with one column carries every pair, and a
+ * pair that is not built is replaced by (1, 1) or (2, 0) without an error. */
 const char* kmvp_last_dispatch_note(const kmvp_ctx* ctx);
 
 #ifdef __cplusplus

@@ -134,6 +134,13 @@ __device__ __forceinline__ double kexp_neg_f64(double s, const double* __restric
   return ldexp(t * p, ni >> 6);
 }
 
+// The clamps above and below (fmin: kexp_neg_f64's 800, the Matern exponents' 192 and 800) return their OTHER argument for
+// a NaN, so a NaN squared distance became e^-800 = 0 where the reference -- and v_exp_f32, v_rsq_f32 on the float32
+// Gaussian, exp(-r) and 1/r -- give NaN: a NaN target coordinate left a row of finite sums in float64 and in the Matern
+// kernels.  Every pair of such a target is NaN, so the three kernels restore the row when they write it, outside the pair
+// loop.  (A NaN SOURCE coordinate still contributes 0 there, not NaN to every row: a known limit.)
+__device__ __forceinline__ double nan_target(bool any_nan, double v) { return any_nan ? __builtin_nan("") : v; }
+
 // float64 Matern (see matern_value above): r from the same rsq + one-step form as exp(-r) below, t = sqrt(2 nu) r clamped
 // at kexp_neg_f64's own 800 (e^-800 = 2^-1154: exactly 0), then the polynomial.  Per pair after s: exp(-r)'s
 // instructions (v_rsq_f64, 6 fp64 operations and the two compares with their selects for r; 15 in kexp_neg_f64, whose own
@@ -447,12 +454,15 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_kernel(const LowdArgs<real
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     const int64_t i = i0 + t * 64 + lane;
+    bool x_nan = false;
+#pragma unroll
+    for (int d = 0; d < D; ++d) x_nan |= x[t][d] != x[t][d];
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
       double v;
       if constexpr (F32) v = accd[t][e];
       else v = (double)acc[t][e];
-      a.part[((int64_t)seg * NE + e) * a.n_pad + i] = v;
+      a.part[((int64_t)seg * NE + e) * a.n_pad + i] = nan_target(x_nan, v);
     }
   }
 }
@@ -499,6 +509,9 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_mid_kernel(
     const int64_t g = ic % (m_total + 1);
     jz = (g < m_total) ? g - j_offset : (int64_t)-1;
   }
+  bool x_nan = false;  // nan_target above
+#pragma unroll
+  for (int d = 0; d < DMAX; ++d) x_nan |= xr[d] != xr[d];
   const int64_t j0 = (int64_t)seg * seg_len;
   int64_t j1 = j0 + seg_len;
   if (j1 > m) j1 = m;
@@ -537,9 +550,9 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_mid_kernel(
       if constexpr (SIG != SIG_DENSITY) {
 #pragma unroll
         for (int q = 0; q < EBW; ++q)
-          if (EBW * blk + q < E) part[((int64_t)seg * NE + EBW * blk + q) * n_pad + i] = accd[q];
+          if (EBW * blk + q < E) part[((int64_t)seg * NE + EBW * blk + q) * n_pad + i] = nan_target(x_nan, accd[q]);
       }
-      if (SIG != SIG_PRODUCT && blk == 0) part[((int64_t)seg * NE + (NE - 1)) * n_pad + i] = dend;
+      if (SIG != SIG_PRODUCT && blk == 0) part[((int64_t)seg * NE + (NE - 1)) * n_pad + i] = nan_target(x_nan, dend);
     }
   }
 }
@@ -573,6 +586,8 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_big_kernel(
     const int64_t g = ic % (m_total + 1);
     jz = (g < m_total) ? g - j_offset : (int64_t)-1;
   }
+  bool x_nan = false;  // nan_target above
+  for (int d = 0; d < DP; ++d) x_nan |= xrow[d] != xrow[d];
   const int64_t j0 = (int64_t)seg * seg_len;
   int64_t j1 = j0 + seg_len;
   if (j1 > m) j1 = m;
@@ -638,9 +653,9 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_big_kernel(
       if constexpr (SIG != SIG_DENSITY) {
 #pragma unroll
         for (int q = 0; q < 8; ++q)
-          if (8 * blk + q < E) part[((int64_t)seg * NE + 8 * blk + q) * n_pad + i] = accd[q];
+          if (8 * blk + q < E) part[((int64_t)seg * NE + 8 * blk + q) * n_pad + i] = nan_target(x_nan, accd[q]);
       }
-      if (SIG != SIG_PRODUCT && blk == 0) part[((int64_t)seg * NE + (NE - 1)) * n_pad + i] = dend;
+      if (SIG != SIG_PRODUCT && blk == 0) part[((int64_t)seg * NE + (NE - 1)) * n_pad + i] = nan_target(x_nan, dend);
     }
   }
 }

@@ -101,9 +101,10 @@ hipError_t KMVP_CAT(KMVP_FN, _generic)(int sig, const real* x, const real* y, co
     if (kernel_name) *kernel_name = "lowd_mid_kernel";
     const int ebw = lowd_mid_colblock((int)sizeof(real), D, E);  // signal columns per pass (the host pads b to it)
     const int EPm = (E + ebw - 1) / ebw * ebw;
+    // (density estimation has one column: the 32-column block is built for the two signal modes only)
 #define KMVP_MID(SIGV, DCH)                                                                                           \
   do {                                                                                                                \
-    if constexpr (sizeof(real) == 4 && DCH <= 8) {                                                                    \
+    if constexpr (sizeof(real) == 4 && DCH <= 8 && SIGV != SIG_DENSITY) {                                             \
       if (ebw == 32) {                                                                                                \
         hipLaunchKernelGGL((lowd_mid_kernel<KERNEL, SIGV, real, DCH, 32>), grid, dim3(BLOCK_THREADS), 0, stream, x, y, \
                            b, part, n, n_pad, m, E, EPm, NE, segments, seg_len, j_offset, m_total);                   \
@@ -113,9 +114,11 @@ hipError_t KMVP_CAT(KMVP_FN, _generic)(int sig, const real* x, const real* y, co
     hipLaunchKernelGGL((lowd_mid_kernel<KERNEL, SIGV, real, DCH, 8>), grid, dim3(BLOCK_THREADS), 0, stream, x, y, b,  \
                        part, n, n_pad, m, E, EPm, NE, segments, seg_len, j_offset, m_total);                          \
   } while (0)
+    // D <= LOWD_MAX_D = 8 never comes here: run_product() sends it to lowd_kernel (E <= 4, density) or to
+    // run_product_blocked (E > 4), so DCH = 1 is not built
 #define KMVP_MID_D(SIGV)                \
   switch ((D + 7) / 8) {                \
-    case 1: KMVP_MID(SIGV, 1); break;   \
+    case 1: return hipErrorInvalidValue; \
     case 2: KMVP_MID(SIGV, 2); break;   \
     case 3: KMVP_MID(SIGV, 3); break;   \
     case 4: KMVP_MID(SIGV, 4); break;   \

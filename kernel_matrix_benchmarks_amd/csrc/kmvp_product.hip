@@ -459,6 +459,13 @@ int run_product_t(kmvp_ctx* c, int kernel, int sig) {
         tune.feed = DEFAULT_FEED;
       }
     }
+    if (c->opt_T > 0 || c->opt_feed >= 0) {
+      // a requested pair that is not instantiated was replaced above without an error: say which pair runs
+      char buf[96];
+      snprintf(buf, sizeof buf, "%slowd_kernel runs targets_per_lane = %d, feed = %d", c->note.empty() ? "" : "; ",
+               tune.targets_per_lane, tune.feed);
+      c->note += buf;
+    }
     const int EB = sig == SIG_DENSITY ? 0 : E;
     const int R = (D + EB + 3) / 4 * 4;
     LowdArgs<real> a = lowd_geometry<real>(c, tune.targets_per_lane, R, NE);
