@@ -350,6 +350,55 @@ int kmvp_nearest(kmvp_ctx* ctx, int K, int exclude_self, int64_t* out_idx, doubl
 int kmvp_kmeans(kmvp_ctx* ctx, int C, const double* weights_or_null, double tol, int maxit, double* centroids,
                 int64_t* labels, double* cluster_weight_or_null, int* iters, double* inertia, double* shift);
 
+/* Gaussian mean-shift, resident on the device (an extension: the solver on top of the gradient of the log-sum-exp, as
+ * Sinkhorn is on top of the log-sum-exp and k-means on top of the arg-K-min).  For the Gaussian G = -2 (x_i - ybar_i) with
+ * ybar_i the softmax-weighted barycentre of the sources, so x_i + G_i / 2 IS the mean-shift update; it inherits the integer
+ * shift of the log-sum-exp and is finite for a seed so far from the data that the float32 product is 0 / 0.
+ * There is no exp(-r) entry: its mean-shift update is a Weiszfeld-type ratio sum p y / r over sum p / r, which the sums of
+ * kmvp_absexp_logsumexp_grad (sum p (x - y) / r over sum p) do not give.
+ * The sources y (M,D) and the signal come from the context as for kmvp_gaussian_logsumexp_grad; the signal is read as
+ * log-weights c, ONE column (b == NULL: c = 0; -inf: mass 0).  The seeds are the context's TARGETS -- x (N,D), or the cloud
+ * itself when x_or_null == NULL.  The bandwidth is the caller's scaling of the points, as everywhere in this family.
+ * The positions z are float64 on the device, z_0 = the seeds; real() rounds to the working precision.  For k = 1, 2, ... and
+ * every ACTIVE point i:
+ *   base_i  = (double) real(z_{k-1,i})
+ *   G_i     = the row kmvp_gaussian_logsumexp_grad returns for a target at real(z_{k-1,i}), bit for bit
+ *   h_d     = 0.5 G_i[d],   z_{k,i}[d] = base_i[d] + h_d
+ *   q_i     = sum_d h_d h_d   (d ascending from 0; every product and every sum rounded on its own, no fused multiply-add:
+ *                              a numpy restatement reproduces the bits)
+ *   point i FREEZES after the first sweep with q_i <= tol * tol: it keeps the z_k of that sweep, iters[i] = k, step2[i] = q_i.
+ *   A point whose G has a non-finite component (a row without a live term, a NaN coordinate, an overflowed difference)
+ *   freezes too: its modes row is NaN in all D components, step2[i] is NaN, iters[i] the sweep at which this happened.
+ * The solve ends when no point is active, or after maxit sweeps; points still active then have iters = maxit and the q of
+ * the last sweep.  Outputs (all required): modes (N,D) float64 row-major, iters (N ints), step2 (N doubles), *sweeps = the
+ * sweeps run, *target_sweeps = sum_k (active points in sweep k): the solver's work in units of M pair evaluations.
+ * KMVP_OK if and only if every point froze with a finite q <= tol^2; otherwise KMVP_E_NOT_CONVERGED with everything written.
+ * Conventions
+ *  - every target's arithmetic is its own (in lowd_lse_grad_kernel lanes are targets and the shift moves per lane): a
+ *    point's trajectory depends neither on which other points are still active nor on where in the target image it sits.
+ *    What does enter the bits is the geometry of the source axis -- segment count, segment length, "chunk" --, pinned at
+ *    the first sweep to what kmvp_gaussian_logsumexp_grad takes for these (N, M, options) and kept while the active set
+ *    shrinks.  So the solve gives the bits of a host loop that calls kmvp_gaussian_logsumexp_grad on all N moved targets
+ *    every sweep.  Honours "segments" and "chunk".
+ *  - the freeze is decided on the device in every sweep; four state words (stop, sweeps, active points, target_sweeps)
+ *    cross to the host per sweep, and it sizes the next launch from them.  Nothing else crosses until the end.
+ *  - "meanshift_compact" (kmvp_set_option) 0 keeps the frozen points in the launch; the results are the same bit for bit,
+ *    and *target_sweeps does not depend on it.
+ *  - bitwise reproducible run to run.  kmvp_get_result is not involved.
+ *  - a product, gradient, log-sum-exp, kmvp_nearest or kmvp_kmeans on the same context returns the same bits before and
+ *    after the call as without it: the moving target image, the positions, the index lists and the state live in buffers
+ *    of the solver's own; the source records are the product's own, under its bookkeeping, packed only if stale.
+ * Per sweep seven launches: the target image of the active points, lowd_lse_grad_kernel (kmvp_last_kernel_name) and its
+ * segment merge, both untouched, the step (csrc/kmvp_meanshift.hip; the rule: csrc/kmvp_meanshift_step.hpp, on the quotient
+ * V / Z of the gradient's own finish), an order-preserving stream compaction of the active index list, and the state words.
+ * kmvp_last_dispatch_note is ""; kmvp_last_kernel_ms and kmvp_last_total_ms both cover the whole solve.
+ * float32 and float64 contexts (float16 data: a float32 context of float16-rounded points), D <= 8.
+ * KMVP_E_UNSUPPORTED with a message for bfloat16 contexts, D > 8, more than one signal column, an explicit "fast_sqdists"
+ * of 1 .. 4, an attached communicator and a source slice (M < M_total).  KMVP_E_INVALID for no points or no signal set,
+ * tol < 0 or NaN, maxit < 1, N < 1, M < 1 and a NULL output. */
+int kmvp_gaussian_meanshift(kmvp_ctx* ctx, double tol, int maxit, double* modes, int* iters, double* step2, int* sweeps,
+                            int64_t* target_sweeps);
+
 /* BaseProduct.get_result (base.py:107-116): (N,E) float64 row-major. */
 int kmvp_get_result(kmvp_ctx* ctx, double* out, int64_t out_len);
 
@@ -622,6 +671,9 @@ int kmvp_comm_init_host(kmvp_ctx* ctx, kmvp_host_allreduce_fn fn, void* user, in
  *                      (default) and 1 = such a workgroup builds every source operand once and shares it through LDS,
  *                      wherever the kernel holds that body (eight target tiles per wavefront); 0 = never, every wavefront
  *                      builds its own.  The sums are the same bit for bit either way
+ *   "meanshift_compact" kmvp_gaussian_meanshift: -1 (default) and 1 = the list of active points is compacted after every
+ *                      sweep, so the pair loop covers the points still moving; 0 = never, frozen points ride along and are
+ *                      ignored.  The results are the same bit for bit either way: it exists to measure what compaction saves
  *   "mfma_variant"     bf16 path, software-pipelined kernel: -1 = by kernel (default: exp(-r) 4, others 0), 0 = plain,
  *                      1 = denominators on the matrix pipe (one more accumulator tile per target tile), 4 = loop rotated by one
  *                      transcendental stage, 5 = both (csrc/kmvp_mfma.hpp, mfma_pipe_kernel VAR) */

@@ -57,6 +57,8 @@ SYMBOLS = [
     ("kmvp_nearest", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     ("kmvp_kmeans", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
                                _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("kmvp_gaussian_meanshift", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                           _c.POINTER(_c.c_int), _c.POINTER(_c.c_int64)]),
     ("kmvp_get_result", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("kmvp_gaussian_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
@@ -447,6 +449,24 @@ class Context:
         if rc not in (0, 6):
             self._check(rc)
         return cent, labels, cluster_weight, iters.value, inertia.value, shift.value, rc == 0
+
+    def meanshift(self, tol, maxit):
+        """Gaussian mean-shift of the TARGETS of set_points over the sources, the signal read as one column of log-weights
+        (include/kmvp.h kmvp_gaussian_meanshift).  Returns a dict: modes (N, D) float64, iters (N) int64, step2 (N) float64,
+        sweeps, target_sweeps, converged; raises on every status but OK and NOT_CONVERGED."""
+        N, D = int(getattr(self, "N", 0)), int(getattr(self, "D", 0))
+        # the library writes N * D, N and N elements through the pointers: the arrays are sized here, from the points it was given
+        modes = np.full((N, D), np.nan, dtype=np.float64)
+        iters = np.zeros(N, dtype=np.intc)
+        step2 = np.full(N, np.nan, dtype=np.float64)
+        sweeps = ctypes.c_int(0)
+        target_sweeps = ctypes.c_int64(0)
+        rc = self._lib.kmvp_gaussian_meanshift(self._ctx, float(tol), int(maxit), modes.ctypes.data, iters.ctypes.data,
+                                               step2.ctypes.data, ctypes.byref(sweeps), ctypes.byref(target_sweeps))
+        if rc not in (0, 6):
+            self._check(rc)
+        return {"modes": modes, "iters": iters.astype(np.int64), "step2": step2, "sweeps": sweeps.value,
+                "target_sweeps": target_sweeps.value, "converged": rc == 0}
 
     def set_solver_diagonal(self, d_or_none, ridge=0.0):
         """A = K + ridge I + diag(d) for the solves that follow (include/kmvp.h kmvp_set_solver_diagonal); d: one float64

@@ -1313,3 +1313,175 @@ class MI355XKMeans:
             self.done()
         except Exception:
             pass
+
+
+MEANSHIFT_MAX_D = NEAREST_MAX_D
+
+
+class MI355XMeanShift:
+    """Gaussian mean-shift on one MI355X, resident on the device (include/kmvp.h kmvp_gaussian_meanshift; the pair loop is
+    lowd_lse_grad_kernel: for the Gaussian the gradient of the log-sum-exp is -2 (x - ybar), so x + G / 2 is the mean-shift
+    update, on the integer shift of the log-sum-exp).  The mode-seeking counterpart of MI355XKMeans: clustering without a
+    cluster count.  An extension: the reference's plugin API has no such role, so the class is not registered in
+    algos.yaml.
+
+        every seed x climbs   x <- sum_j w_j exp(-|x - y_j|^2) y_j / sum_j w_j exp(-|x - y_j|^2)
+
+    until its step is within ``tol`` (absolute, in the units of the points) or ``maxit`` sweeps have run; a point that has
+    arrived drops out of the launch.  The bandwidth is the caller's scaling of the points: a Gaussian of bandwidth h is
+    exp(-|x - y|^2) on points divided by h.
+
+    Call order: prepare_data, set_query_arguments, query, then get_modes / get_iterations / get_clusters /
+    get_additional, done.  ``options``: device, segments, chunk, compact (False: frozen points ride along; the results are
+    the same bit for bit)."""
+
+    def __init__(self, *, dimension, precision=np.float32, tol=1e-4, maxit=1000, device=0, segments=0, chunk=0, compact=True):
+        if not float(tol) >= 0:
+            raise ValueError(f"tol must be >= 0, not {tol!r}")
+        self.dimension = int(dimension)
+        self.precision = precision
+        self._dtype_code, self._host_dtype = _lib.dtype_code(precision)
+        if self._dtype_code == _lib.KMVP_BF16:
+            raise NotImplementedError("MI355XMeanShift: float32, float64 and float16 only")
+        self._round = _lib.input_rounding(precision)  # float16: rounded points, float32 arithmetic
+        self.tol, self.maxit = float(tol), int(maxit)
+        self.device = device
+        self._options = dict(segments=segments, chunk=chunk)
+        self._compact = bool(compact)
+        self._ctx = None
+        self.modes = self.iterations = self.step2 = None
+        self.sweeps, self.target_sweeps, self.converged = 0, 0, False
+        self.name = f"MI355XMeanShift({_precision_name(precision)})"
+
+    def _as_device_points(self, points, what):
+        p = np.asarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != self.dimension:
+            raise ValueError(f"{what} has shape {p.shape}, expected (N, {self.dimension})")
+        if self._round is not None:
+            p = p.astype(self._round)
+        return np.ascontiguousarray(p, dtype=self._host_dtype)
+
+    # -- untimed -------------------------------------------------------------------
+    def prepare_data(self, *, points, weights=None, seeds=None):
+        """points (M, D): the data; weights (M,) >= 0 and finite or None (every weight 1; 0: a point of mass 0); seeds
+        (N, D) or None: the points themselves."""
+        y = self._as_device_points(points, "points")
+        self.M, self.D = y.shape
+        if self.M < 1:
+            raise ValueError("mean-shift needs at least one point")
+        x = None if seeds is None else self._as_device_points(seeds, "seeds")
+        self.N = self.M if x is None else x.shape[0]
+        if self.N < 1:
+            raise ValueError("mean-shift needs at least one seed")
+        log_w = None
+        if weights is not None:
+            w = np.asarray(weights, dtype=np.float64).reshape(-1)
+            if w.shape != (self.M,):
+                raise ValueError(f"weights has {w.size} entries for {self.M} points")
+            if not (np.all(w >= 0) and np.all(np.isfinite(w))):  # (NaN fails the first)
+                raise ValueError("weights must be non-negative and finite")
+            with np.errstate(divide="ignore"):
+                log_w = np.ascontiguousarray(np.log(w).reshape(-1, 1), dtype=self._host_dtype)  # 0 -> -inf: mass 0
+        if self._ctx is None:
+            self._ctx = _lib.Context(self.device)
+            for key, value in self._options.items():
+                if value:
+                    self._ctx.set_option(key, value)
+            if not self._compact:
+                self._ctx.set_option("meanshift_compact", 0)
+        self._ctx.set_points(y, x, self._dtype_code)
+        self._ctx.set_signal(log_w)
+        self.modes = self.iterations = self.step2 = None
+
+    def set_query_arguments(self, tol=None, maxit=None):
+        if tol is not None:
+            self.tol = float(tol)
+        if maxit is not None:
+            self.maxit = int(maxit)
+
+    # -- timed ---------------------------------------------------------------------
+    def fit(self):
+        """Nothing to build ahead of the first solve: it packs the source records itself, once per prepare_data."""
+
+    def query(self):
+        """Runs the iteration from the seeds.  Synchronous.  Not converged (maxit reached, or a point whose gradient is
+        not finite) is a result, reported by get_additional(); every other failure raises."""
+        if self._ctx is None:
+            raise RuntimeError("MI355XMeanShift.query() needs prepare_data() first")
+        r = self._ctx.meanshift(self.tol, self.maxit)
+        self.modes, self.iterations, self.step2 = r["modes"], r["iters"], r["step2"]
+        self.sweeps, self.target_sweeps, self.converged = r["sweeps"], r["target_sweeps"], r["converged"]
+
+    # -- results -------------------------------------------------------------------
+    def _need_solution(self, method):
+        if self.modes is None:
+            raise RuntimeError(f"MI355XMeanShift.{method}: no solution yet -- call query() after prepare_data() first")
+
+    def _arrived(self):
+        with np.errstate(invalid="ignore"):
+            return np.all(np.isfinite(self.modes), axis=1) & (self.step2 <= self.tol * self.tol)
+
+    def get_modes(self):
+        """(N, D) float64: where every seed ended up (a NaN row: its gradient was not finite)."""
+        self._need_solution("get_modes")
+        return self.modes
+
+    def get_iterations(self):
+        """(N,) int64: the sweep after which every seed froze (the sweeps run, for one still moving at the end)."""
+        self._need_solution("get_iterations")
+        return self.iterations
+
+    def get_clusters(self, merge_radius):
+        """(centres (C, D) float64, labels (N,) int64) by a host rule: walk the converged modes -- finite, last step within
+        tol -- in ascending index; a mode founds a centre if no earlier centre lies within ``merge_radius`` of it
+        (Euclidean distance in float64, the squares added with d ascending, <=).  Afterwards every converged point gets the label of its nearest centre, ties
+        to the smaller label; unconverged or NaN points get -1.  One vectorised numpy pass over the points per centre."""
+        self._need_solution("get_clusters")
+        ok = self._arrived()
+        idx = np.flatnonzero(ok)
+        z = self.modes[idx]
+        centres = []
+        near = np.full(idx.size, np.inf)    # distance of every converged mode to its nearest centre so far
+        label = np.full(idx.size, -1, dtype=np.int64)
+        while True:
+            # the first mode, in index order, that no centre founded so far covers (near only shrinks, so everything
+            # before it stays covered: the walk never has to look back)
+            open_ = np.flatnonzero(near > merge_radius)
+            if open_.size == 0:
+                break
+            c = z[open_[0]]
+            s = np.zeros(idx.size)
+            for d in range(self.D):  # the squares added with d ascending
+                s = s + (z[:, d] - c[d]) ** 2
+            dist = np.sqrt(s)
+            closer = dist < near  # strictly: a tie stays with the smaller label
+            label[closer] = len(centres)
+            near = np.where(closer, dist, near)
+            centres.append(c.copy())
+        labels = np.full(self.N, -1, dtype=np.int64)
+        labels[idx] = label
+        return np.array(centres, dtype=np.float64).reshape(len(centres), self.D), labels
+
+    def get_memory_usage(self):
+        """Device kB held by the context."""
+        return (self._ctx.device_bytes if self._ctx is not None else 0) / 1024
+
+    def get_additional(self):
+        extra = {"sweeps": self.sweeps, "target_sweeps": self.target_sweeps, "converged": bool(self.converged)}
+        if self.modes is not None:
+            extra["unconverged"] = int(self.N - np.count_nonzero(self._arrived()))
+        if self._ctx is not None:
+            extra.update(device_kernel_ms=self._ctx.last_kernel_ms, device_total_ms=self._ctx.last_total_ms,
+                         device_kernel=self._ctx.last_kernel_name, device_bytes=self._ctx.device_bytes)
+        return extra
+
+    def done(self):
+        if self._ctx is not None:
+            self._ctx.close()
+        self._ctx = None
+
+    def __del__(self):
+        try:
+            self.done()
+        except Exception:
+            pass

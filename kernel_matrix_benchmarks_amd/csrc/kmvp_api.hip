@@ -90,7 +90,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
                     &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     release(*b);
   for (int i = 0; i < 5; ++i)
@@ -200,6 +200,10 @@ int kmvp_nearest(kmvp_ctx* c, int K, int exclude_self, int64_t* out_idx, double*
 int kmvp_kmeans(kmvp_ctx* c, int C, const double* weights, double tol, int maxit, double* centroids, int64_t* labels,
                 double* cluster_weight, int* iters, double* inertia, double* shift) {
   return kmeans_solve(c, C, weights, tol, maxit, centroids, labels, cluster_weight, iters, inertia, shift);
+}
+int kmvp_gaussian_meanshift(kmvp_ctx* c, double tol, int maxit, double* modes, int* iters, double* step2, int* sweeps,
+                            int64_t* target_sweeps) {
+  return meanshift_solve(c, tol, maxit, modes, iters, step2, sweeps, target_sweeps);
 }
 
 int kmvp_get_result(kmvp_ctx* c, double* out, int64_t out_len) {
@@ -426,6 +430,9 @@ int kmvp_set_option(kmvp_ctx* c, const char* key, int64_t value) {
     if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
       return fail(c, KMVP_E_INVALID, "fast_tiles must be 0 (auto), 1, 2, 4 or 8");
     c->opt_fast_tiles = (int)value;
+  } else if (k == "meanshift_compact") {
+    if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "meanshift_compact must be -1 (default), 0 or 1");
+    c->opt_meanshift_compact = (int)value;
   } else if (k == "chunk") {
     if (value < 8 || value > (1 << 24)) return fail(c, KMVP_E_INVALID, "chunk out of range");
     c->opt_chunk = (int)value;
@@ -440,7 +447,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
                           &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
     t += b->cap;
   return (int64_t)t;

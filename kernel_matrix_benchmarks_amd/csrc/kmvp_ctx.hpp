@@ -5,6 +5,7 @@
 //   kmvp_solvers.hip  conjugate gradients, MINRES and the Lanczos quadrature on the product
 //   kmvp_sinkhorn.hip the Sinkhorn iteration of entropic optimal transport on the log-sum-exp
 //   kmvp_kmeans.hip   Lloyd's k-means on the arg-K-min at K = 1
+//   kmvp_meanshift.hip Gaussian mean-shift on the gradient of the log-sum-exp
 //   kmvp_precond.hip  the pivoted-Cholesky preconditioner of conjugate gradients: build, apply, read-back
 #pragma once
 #include <dlfcn.h>
@@ -151,6 +152,9 @@ struct kmvp_ctx {
   // centroid update, and the fp64 state (centroids, cluster sums, weights, labels, state words)
   DevBuf km_xs, km_rec, km_part, km_state;
   uint64_t km_points_ver = 0;   // points version km_xs was packed from (0: none)
+  // mean-shift (kmvp_meanshift.hip): the moving target image of the active points, the fp64 state (positions, step2, the
+  // state words, iters, the two index lists, the keep flags) and the scratch of the stream compaction
+  DevBuf ms_xs, ms_state, ms_tmp;
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
   int packed_layout = -1;  // LAYOUT_* of the path that owns xs / rec right now
@@ -168,6 +172,7 @@ struct kmvp_ctx {
   int opt_cell_shared_build = -1;         // cellmm16_kernel's one-cell workgroups build each source operand once: -1 / 1 = where the kernel holds that body (cell_shared_build), 0 = never
   int opt_cell_fused = -1;                // cellmm16_kernel's two tile lists: -1 / 1 = one launch where it applies (fused_cell_grid), 0 = two launches
   int opt_mfma_variant = -1;              // bf16 path: VAR of mfma_pipe_kernel (kmvp_mfma.hpp); -1 = by kernel
+  int opt_meanshift_compact = -1;         // mean-shift: -1 / 1 = the active list is compacted after every sweep, 0 = never (frozen lanes ride along)
   int opt_same_global = 0;                // the targets ARE the (unsharded) sources although x was passed explicitly
   int opt_partial = 0;                    // a source slice (M < M_total) may run WITHOUT a communicator: the caller sums the shards
   uint64_t perm_ver = 0;                  // points version the Morton order belongs to
@@ -214,6 +219,28 @@ inline unsigned blocks_for(int64_t n, int threads = 256) { return (unsigned)((n 
 
 int ensure(kmvp_ctx* c, DevBuf& b, size_t bytes);  // grow-only device buffer
 void release(DevBuf& b);
+
+// What the shared xs / rec buffers hold: the layout of one path for one kernel and T (targets per lane or tiles per
+// wavefront, and whatever else the layout depends on), packed from one version of the points, and -- the signal image --
+// from one version of the signal for one product kind `sig` (-1: an image that is not reusable as it is).
+struct PackKey {
+  int layout, kernel, T;
+};
+inline bool points_stale(const kmvp_ctx* c, PackKey k) {
+  return c->packed_points_ver != c->points_ver || c->packed_kernel != k.kernel || c->packed_layout != k.layout ||
+         c->packed_T != k.T;
+}
+inline bool signal_stale(const kmvp_ctx* c, PackKey k, int sig) {
+  return points_stale(c, k) || sig < 0 || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
+}
+inline void record_packed(kmvp_ctx* c, PackKey k, int sig) {
+  c->packed_points_ver = c->points_ver;
+  c->packed_signal_ver = c->signal_ver;
+  c->packed_layout = k.layout;
+  c->packed_kernel = k.kernel;
+  c->packed_T = k.T;
+  c->packed_sig = sig;
+}
 
 // kmvp_product.hip: the product a = K b [/ K 1] with everything query() times, and the
 // bounding box of the freshly uploaded clouds (asynchronous on the context's stream)
@@ -272,5 +299,9 @@ int sinkhorn_solve(kmvp_ctx* c, int kernel, const double* log_a, const double* l
 // kmvp_kmeans.hip: kmvp_kmeans, the device-resident Lloyd iteration on lowd_knn_kernel<D, 1>
 int kmeans_solve(kmvp_ctx* c, int C, const double* weights, double tol, int maxit, double* centroids, int64_t* labels,
                  double* cluster_weight, int* iters, double* inertia, double* shift);
+
+// kmvp_meanshift.hip: kmvp_gaussian_meanshift, the device-resident mean-shift iteration on lowd_lse_grad_kernel
+int meanshift_solve(kmvp_ctx* c, double tol, int maxit, double* modes, int* iters, double* step2, int* sweeps,
+                    int64_t* target_sweeps);
 
 }  // namespace kmvp

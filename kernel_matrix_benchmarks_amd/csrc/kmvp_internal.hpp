@@ -202,6 +202,53 @@ KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_grad_absexp_f32, float)
 KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_grad_gaussian_f64, double)
 KMVP_DECLARE_LOWD_LSE(launch_lowd_lse_grad_absexp_f64, double)
 
+// What the gradient of the log-sum-exp (kmvp_product.hip run_logsumexp_grad_t) and the mean-shift iteration on top of it
+// (kmvp_meanshift.hip) share: the launch switch, the segment merge and the quotient V / Z.
+inline hipError_t launch_lowd_lse_grad(int kernel, int D, int E, int sig, const LowdArgs<float>& args, dim3 grid, hipStream_t s,
+                                       const char** name) {
+  switch (kernel) {
+    case K_GAUSSIAN: return launch_lowd_lse_grad_gaussian_f32(D, E, sig, args, grid, s, name);
+    case K_ABSEXP: return launch_lowd_lse_grad_absexp_f32(D, E, sig, args, grid, s, name);
+    default: return hipErrorInvalidValue;
+  }
+}
+inline hipError_t launch_lowd_lse_grad(int kernel, int D, int E, int sig, const LowdArgs<double>& args, dim3 grid, hipStream_t s,
+                                       const char** name) {
+  switch (kernel) {
+    case K_GAUSSIAN: return launch_lowd_lse_grad_gaussian_f64(D, E, sig, args, grid, s, name);
+    case K_ABSEXP: return launch_lowd_lse_grad_absexp_f64(D, E, sig, args, grid, s, name);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The segment merge: K_q = min_s k[s][q],   sums[t][q] = sum_s part[s][t][q] 2^(K_q - k[s][q]) for the NS = D + 1 sums t
+// that share the exponent (index order; every factor <= 1 and exact).  One thread per (t, q).
+// (static: a kernel cannot be inline; each of the two units that launch it carries its own copy, the others none)
+static __global__ void lse_grad_reduce_kernel(const double* __restrict__ part, double* __restrict__ sums, double* __restrict__ kmin,
+                                              int64_t count /* NC * n_pad */, int NS, int segments) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)NS * count) return;
+  const int64_t q = idx % count;
+  const int64_t stride = (int64_t)(NS + 1) * count;  // one segment
+  const double* kexp = part + (int64_t)NS * count + q;
+  double K = INFINITY;
+  for (int s = 0; s < segments; ++s) K = fmin(K, kexp[s * stride]);
+  double v = 0.0;
+  for (int s = 0; s < segments; ++s) {
+    const double ks = kexp[s * stride];
+    if (ks < INFINITY) v += ldexp(part[s * stride + idx], (int)fmax(K - ks, -100000.0));
+  }
+  sums[idx] = v;
+  if (idx < count) kmin[q] = K;
+}
+
+// One component of the gradient from the merged sums: constant V[d] / Z (the common scale cancels); `none`: no live term
+// anywhere, the softmax does not exist.  finish_lse_grad_kernel (kmvp_product.hip) and the mean-shift step
+// (kmvp_meanshift.hip) both go through this one expression, so the step sees the gradient's own bits.
+__device__ __forceinline__ double lse_grad_value(bool none, double constant, double v, double z) {
+  return none ? __builtin_nan("") : constant * v / z;
+}
+
 // bf16 MFMA path (kmvp_mfma.hpp): largest shapes instantiated
 constexpr int MFMA_MAX_KS = 9;  // D <= 16*9 - 6 = 138
 constexpr int MFMA_MAX_NT = 4;  // E <= 128

@@ -280,27 +280,7 @@ int complete(kmvp_ctx* c, int64_t N, int E) {
   return KMVP_OK;
 }
 
-// What the shared xs / rec buffers hold: the layout of one path for one kernel and T (targets per lane or tiles per
-// wavefront, and whatever else the layout depends on), packed from one version of the points, and -- the signal image --
-// from one version of the signal for one product kind `sig` (-1: an image that is not reusable as it is).
-struct PackKey {
-  int layout, kernel, T;
-};
-bool points_stale(const kmvp_ctx* c, PackKey k) {
-  return c->packed_points_ver != c->points_ver || c->packed_kernel != k.kernel || c->packed_layout != k.layout ||
-         c->packed_T != k.T;
-}
-bool signal_stale(const kmvp_ctx* c, PackKey k, int sig) {
-  return points_stale(c, k) || sig < 0 || c->packed_signal_ver != c->signal_ver || c->packed_sig != sig;
-}
-void record_packed(kmvp_ctx* c, PackKey k, int sig) {
-  c->packed_points_ver = c->points_ver;
-  c->packed_signal_ver = c->signal_ver;
-  c->packed_layout = k.layout;
-  c->packed_kernel = k.kernel;
-  c->packed_T = k.T;
-  c->packed_sig = sig;
-}
+// (PackKey, points_stale, signal_stale, record_packed: kmvp_ctx.hpp, shared with the mean-shift iteration.)
 
 // In-place all-reduce of `count` doubles on the device over the ranks of the attached exchange: ncclAllReduce on the
 // context's stream, or -- rehearsal transport (kmvp_comm_init_host) -- device -> host, the caller's callback (e.g. gloo),
@@ -744,45 +724,12 @@ int run_logsumexp_t(kmvp_ctx* c, int kernel, int sig) {
 // live source), all fp64: part[s][k NC + c][i] for sum k (0: the denominator Z, 1 + d: the numerator V[d]) and
 // part[s][(D + 1) NC + c][i].  With q = (column, target) as ONE index of NC * n_pad (sharded: NC * N) entries the sums are
 // [D + 1][q] and the exponents [q]: lse_reduce_kernel's arithmetic and finish_lse's exchange with D + 1 sums per exponent.
-hipError_t launch_lowd_lse_grad(int kernel, int D, int E, int sig, const LowdArgs<float>& args, dim3 grid, hipStream_t s,
-                                const char** name) {
-  switch (kernel) {
-    case K_GAUSSIAN: return launch_lowd_lse_grad_gaussian_f32(D, E, sig, args, grid, s, name);
-    case K_ABSEXP: return launch_lowd_lse_grad_absexp_f32(D, E, sig, args, grid, s, name);
-    default: return hipErrorInvalidValue;
-  }
-}
-hipError_t launch_lowd_lse_grad(int kernel, int D, int E, int sig, const LowdArgs<double>& args, dim3 grid, hipStream_t s,
-                                const char** name) {
-  switch (kernel) {
-    case K_GAUSSIAN: return launch_lowd_lse_grad_gaussian_f64(D, E, sig, args, grid, s, name);
-    case K_ABSEXP: return launch_lowd_lse_grad_absexp_f64(D, E, sig, args, grid, s, name);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-// The segment merge: K_q = min_s k[s][q],   sums[t][q] = sum_s part[s][t][q] 2^(K_q - k[s][q]) for the NS = D + 1 sums t
-// that share the exponent (index order; every factor <= 1 and exact).  One thread per (t, q).
-__global__ void lse_grad_reduce_kernel(const double* __restrict__ part, double* __restrict__ sums, double* __restrict__ kmin,
-                                       int64_t count /* NC * n_pad */, int NS, int segments) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)NS * count) return;
-  const int64_t q = idx % count;
-  const int64_t stride = (int64_t)(NS + 1) * count;  // one segment
-  const double* kexp = part + (int64_t)NS * count + q;
-  double K = INFINITY;
-  for (int s = 0; s < segments; ++s) K = fmin(K, kexp[s * stride]);
-  double v = 0.0;
-  for (int s = 0; s < segments; ++s) {
-    const double ks = kexp[s * stride];
-    if (ks < INFINITY) v += ldexp(part[s * stride + idx], (int)fmax(K - ks, -100000.0));
-  }
-  sums[idx] = v;
-  if (idx < count) kmin[q] = K;
-}
+// (launch_lowd_lse_grad and the segment merge lse_grad_reduce_kernel: kmvp_internal.hpp, shared with the mean-shift
+// iteration.)
 
 // out[i][e D + d] = constant V[d] / Z with Z = sums[0][e][i], V[d] = sums[1 + d][e][i]: the common scale cancels.
 // K = +inf (no live term anywhere): NaN in all D components -- exactly the entries where the log-sum-exp is -inf.
+// (The expression itself: lse_grad_value, kmvp_internal.hpp.)
 __global__ void finish_lse_grad_kernel(const double* __restrict__ sums, const double* __restrict__ kshift,
                                        double* __restrict__ out, int64_t n, int64_t n_pad, int NC, int D, double constant) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -792,7 +739,7 @@ __global__ void finish_lse_grad_kernel(const double* __restrict__ sums, const do
   const bool none = !(kshift[e * n_pad + i] < 1.0e300);
   const double z = sums[e * n_pad + i];
   for (int d = 0; d < D; ++d)
-    out[q * D + d] = none ? __builtin_nan("") : constant * sums[(int64_t)(1 + d) * count + e * n_pad + i] / z;
+    out[q * D + d] = lse_grad_value(none, constant, sums[(int64_t)(1 + d) * count + e * n_pad + i], z);
 }
 
 // Tail of the gradient: c->sums [D + 1][NC][n_pad] and c->kshift [NC][n_pad].  Sharded as finish_lse: the canonical
