@@ -667,6 +667,12 @@ int kmvp_comm_init_host(kmvp_ctx* ctx, kmvp_host_allreduce_fn fn, void* user, in
  *   "cell_fused"       cellmm16_kernel's two lists of target tiles (whole groups per cell; the cells' leftover tiles): -1 =
  *                      automatic (default) and 1 = ONE launch, the leftover list's workgroups behind the others, where both
  *                      lists fit one grid; 0 = always two launches.  The sums are the same bit for bit either way
+ *   "cell_balance"     the cells of the float32 cell form: 1 = the lattice is kept in x and y and every (x, y) column is cut
+ *                      along z by point count (1024 points, one workgroup of target tiles, per cell; shorter only where the
+ *                      accuracy bound on a cell's width or the column ends), wherever that applies: D = 3, float32, eight
+ *                      target tiles per wavefront, at most ~256 lattice cells along z; -1 = automatic (default): as 1 from the
+ *                      sizes at which cellmm16_kernel is taken by itself (N >= 500000, M >= 100000); 0 = never, the lattice's
+ *                      cells.  Results agree to the cell form's accuracy, not bit for bit: the cells differ
  *   "cell_shared_build" cellmm16_kernel's workgroups whose four wavefronts own target tiles of ONE cell: -1 = automatic
  *                      (default) and 1 = such a workgroup builds every source operand once and shares it through LDS,
  *                      wherever the kernel holds that body (eight target tiles per wavefront); 0 = never, every wavefront

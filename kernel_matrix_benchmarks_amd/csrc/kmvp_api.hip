@@ -91,7 +91,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
                     &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
                     &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp,
-                    &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
+                    &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     release(*b);
   for (int i = 0; i < 5; ++i)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -415,6 +415,9 @@ int kmvp_set_option(kmvp_ctx* c, const char* key, int64_t value) {
   } else if (k == "cell_fused") {
     if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "cell_fused must be -1 (automatic), 0 (two launches) or 1 (one launch where it applies)");
     c->opt_cell_fused = (int)value;
+  } else if (k == "cell_balance") {
+    if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "cell_balance must be -1 (automatic), 0 (never) or 1 (wherever count-cut cells apply)");
+    c->opt_cell_balance = (int)value;
   } else if (k == "cell_shared_build") {
     if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "cell_shared_build must be -1 (automatic), 0 (never) or 1 (wherever a workgroup is one-cell)");
     c->opt_cell_shared_build = (int)value;
@@ -448,7 +451,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
                           &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
                     &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp,
-                          &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale})
+                          &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     t += b->cap;
   return (int64_t)t;
 }

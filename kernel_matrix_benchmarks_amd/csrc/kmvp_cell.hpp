@@ -59,9 +59,14 @@ struct CellGrid {
   float lo[3];
   float h[3], inv_h[3];  // per axis: the box extent divided into equal cells of side <= the accuracy bound
   int g[3];
+  // count-cut cells (count_cut_cells, kmvp_plan.hpp): the centres of ONE cloud's cells, [cell id][4] floats on the device,
+  // and a tile's key is a cell id.  nullptr: the lattice, whose key holds the cell's index per axis.
+  const float* centres = nullptr;
 };
 
+// The only place a tile's key is decoded into a centre
 __host__ __device__ inline float cell_centre(unsigned key, int a, const CellGrid& grid) {
+  if (grid.centres) return grid.centres[4 * (size_t)key + a];
   return grid.lo[a] + ((float)((key >> (10 * a)) & 1023u) + 0.5f) * grid.h[a];
 }
 

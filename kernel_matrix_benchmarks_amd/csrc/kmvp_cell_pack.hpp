@@ -20,6 +20,25 @@ __global__ void cell_keys_kernel(const float* __restrict__ p, int64_t n, int D, 
   vals[i] = (int)i;
 }
 
+// fine key of every point (D = 3; count_cut_cells, kmvp_plan.hpp): the lattice's x and y cell indices above the point's z
+// in CELL_ZQ equal buckets of the grid's z-extent (zq_per_unit buckets per unit length), clamped likewise.  The bucket is
+// taken in double precision: a point then lies in its bucket, and within a cell's bucket range, exactly
+__global__ void cell_fine_keys_kernel(const float* __restrict__ p, int64_t n, CellGrid grid, double zq_per_unit,
+                                      unsigned* __restrict__ keys, int* __restrict__ vals) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  unsigned column = 0;
+  for (int a = 0; a < 2; ++a) {
+    int c = (int)floorf((p[i * 3 + a] - grid.lo[a]) * grid.inv_h[a]);
+    c = c < 0 ? 0 : (c >= grid.g[a] ? grid.g[a] - 1 : c);
+    column |= (unsigned)c << (10 * a);
+  }
+  int zq = (int)floor(((double)p[i * 3 + 2] - (double)grid.lo[2]) * zq_per_unit);
+  zq = zq < 0 ? 0 : (zq >= CELL_ZQ ? CELL_ZQ - 1 : zq);
+  keys[i] = (column << CELL_ZQ_BITS) | (unsigned)zq;
+  vals[i] = (int)i;
+}
+
 // one block of 32 threads per target tile.  tiles >= n_groups are pad tiles (they repeat the
 // last tile's cell, so a wave never sees a cell change because of them)
 __global__ void __launch_bounds__(CELL_TILE) pack_cell_targets_kernel(

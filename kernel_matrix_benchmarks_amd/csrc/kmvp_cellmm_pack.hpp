@@ -47,16 +47,19 @@ __global__ void cellmm_absmax_kernel(const float* __restrict__ b, int64_t n, int
   if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 
-// scale[0] = sigma_b = 2^(15 - ceil(log2(0.104 max|b|)) - wlog2): the largest first-order entry of A,
-// f W b sigma_b with |f| <= 0.104 and W <= 2^wlog2, stays below 2^15 (f16 overflows at 65504) and the f16 mid
-// parts of ordinary entries stay normal numbers; scale[1] = 1 / (sigma_b 2^6), exact.
-__global__ void cellmm_scale_kernel(const unsigned* __restrict__ bmax_bits, int wlog2, int density,
+// scale[0] = sigma_b = 2^(15 - ceil(log2(fmax max|b|)) - wlog2): the largest first-order entry of A,
+// f W b sigma_b with |f| <= fmax and W <= 2^wlog2, stays below 2^15 -- a factor of two under f16's overflow at 65504 --
+// and the f16 mid parts of ordinary entries stay normal numbers; scale[1] = 1 / (sigma_b 2^6), exact.
+// fmax: the bound on |f| = 2 |e| over all axes on the cells in use (cellmm_fmax, kmvp_product.hip): 0.104 on the lattice in
+// three dimensions, the z-cap of count-cut cells where that is larger.  (A lattice in one or two dimensions has sides up to
+// sqrt(2 CELL_T_MAX / D) = 0.179 and is scaled with 0.104 all the same: that factor of two is what covers it.)
+__global__ void cellmm_scale_kernel(const unsigned* __restrict__ bmax_bits, int wlog2, float fmax, int density,
                                     float* __restrict__ scale) {
   float bmax = density ? 1.f : __int_as_float((int)*bmax_bits);
   int ex = 0;
   if (bmax > 0.f && bmax < INFINITY) {
     int eb;
-    (void)frexpf(bmax * 0.104f, &eb);  // bmax * 0.104 = m 2^eb, m in [0.5, 1)  ->  ceil(log2) <= eb
+    (void)frexpf(bmax * fmax, &eb);  // bmax * fmax = m 2^eb, m in [0.5, 1)  ->  ceil(log2) <= eb
     ex = 15 - eb - wlog2;
     ex = ex < -100 ? -100 : (ex > 100 ? 100 : ex);
   }

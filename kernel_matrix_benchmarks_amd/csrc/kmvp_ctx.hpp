@@ -126,6 +126,7 @@ struct kmvp_ctx {
   // ([start][count][key] per tile), slot of every target in cell order, target tile centres,
   // segment-reduced sums in cell order
   DevBuf cell_tperm, cell_sperm, cell_tgrp, cell_sgrp, cell_slot, cell_tmeta, cell_sums, cell_skey, cell_scentre, cell_scale;
+  DevBuf cell_tcentre, cell_scentre32;  // count-cut cells: [cell][4] float centres of the targets' / the sources' cells (same_points: the sources' serve both)
   DevBuf part, sums, out;       // fp64 partials, reduced sums, final (N,E)
   DevBuf xchg;                  // sharded runs: sums in the canonical unpadded layout [column][N] for the all-reduce
   DevBuf kexp, kshift, xchgk;   // exp(<x,y>): exponents per (segment, target) / per target / per target after the all-reduce(min)
@@ -170,6 +171,7 @@ struct kmvp_ctx {
   int opt_fast = -1, opt_fast_tiles = 0;  // fast_sqdists: -1 auto, 0 never, 1 always, 2 always the centred form, 3 always the cell form
   int opt_cellmm_shape = -1;              // cellmm_kernel's MFMA shape: 0 = 32x32x16, 1 = 16x16x32 (cellmm16_kernel), -1 = by size
   int opt_cell_shared_build = -1;         // cellmm16_kernel's one-cell workgroups build each source operand once: -1 / 1 = where the kernel holds that body (cell_shared_build), 0 = never
+  int opt_cell_balance = -1;              // float32 cell lists: lattice columns cut along z by point count: -1 = where it applies at the sizes cellmm16_kernel is taken by itself, 1 = wherever it applies (cell_balance_applies), 0 = never
   int opt_cell_fused = -1;                // cellmm16_kernel's two tile lists: -1 / 1 = one launch where it applies (fused_cell_grid), 0 = two launches
   int opt_mfma_variant = -1;              // bf16 path: VAR of mfma_pipe_kernel (kmvp_mfma.hpp); -1 = by kernel
   int opt_meanshift_compact = -1;         // mean-shift: -1 / 1 = the active list is compacted after every sweep, 0 = never (frozen lanes ride along)
@@ -178,6 +180,9 @@ struct kmvp_ctx {
   uint64_t perm_ver = 0;                  // points version the Morton order belongs to
   uint64_t cell_ver = 0;                  // points version the cell structures belong to
   int cell_state = 0;                     // for cell_ver: 0 not examined, 1 built, -1 the path does not apply
+  int cell_balance_req = -1;              // the "cell_balance" option the cell structures were built under
+  bool cell_balanced = false;             // the cells are count-cut (tile keys are cell ids, centres come from the tables)
+  float cell_zw = 0.f;                    // count-cut cells: the cap on a cell's width along z
   int cell_tt = 0, cell_tt_req = 0;       // target tiles per wavefront the target tile list was padded for; as requested (0 = auto)
   float cell_lo[3] = {0.f, 0.f, 0.f}, cell_hh[3] = {1.f, 1.f, 1.f};  // grid origin and cell sides per axis
   int cell_g[3] = {1, 1, 1};

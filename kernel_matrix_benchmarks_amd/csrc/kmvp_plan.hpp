@@ -2,6 +2,8 @@
 // become tile lists.  Pure functions of numbers -- no HIP, no context -- so that they compile into kmvp_product.hip and,
 // with a host compiler alone, into tests/test_host_plan.py.  The segment count decides the order of the fp64 partial sums
 // (bitwise results) and the L2 behaviour (speed); the tile lists are what the cell kernels index without a bounds check.
+// Cells are the lattice's (one key per cell, cell_tiles / cell_tiles_split) or, under the "cell_balance" option, columns of
+// the lattice cut along z by point count (count_cut_cells and the two list builders behind it, at the end of this file).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -306,6 +308,106 @@ inline int64_t count_one_cell_blocks(const unsigned* keys, int64_t n_main, int t
     one += same ? 1 : 0;
   }
   return one;
+}
+
+// ---- count-cut cells (the "cell_balance" option) ------------------------------------------------------------------------
+
+// A lattice cell holds whatever falls into it -- 1000 +- 32 points at the headline shape, never a multiple of a tile (32)
+// or of a workgroup's targets (1024) -- so the last source tile of every cell is half empty and every cell's target tiles
+// are padded or spill into the REST list: 5.4 % of the MFMAs multiply padding.  The kernels do not care how a cell is
+// defined: they see a centre and a key per tile and offsets from that centre; only |2 d.e| <= CELL_T_MAX and the f16 operand
+// range tie a cell to a size.  So the lattice is kept in x and y, and each (x, y) column is cut along z BY POINT COUNT.
+//
+// A fine key is (column << CELL_ZQ_BITS) | zq: `column` the 20 bits of the lattice's x and y cell indices, zq the point's z
+// in CELL_ZQ equal buckets of the grid's z-extent.  Walking a column of the sorted fine keys, a cell takes points until it
+// holds `full` points (32 TT WAVES_PER_BLOCK targets: one whole workgroup) or until its bucket range [zlo, zhi] would be
+// wider than `cap` buckets.  A cell the cap stopped with at least `quantum` points (32 TT: a wavefront's tiles; 32 for a
+// cloud that is only a source) is cut back to a multiple of `quantum`, so that it ends on a full tile or tile group; the
+// points cut off start the next cell.  A cell is shorter only there and at the column's end.  Points of one bucket come in
+// arbitrary order, and a cell boundary may fall inside a bucket: both neighbours' ranges then include that bucket, and
+// a bucket of more than `full` points gives several cells of one range and one centre (harmless: a centre is only a point of
+// expansion, and each cell has its own id).  A cell's id is its index, < 2^30: bit 30 and -1 keep their meanings in tile
+// keys.  Deterministic: a function of the sorted keys alone.
+constexpr int CELL_ZQ_BITS = 12;
+constexpr int CELL_ZQ = 1 << CELL_ZQ_BITS;
+constexpr int CELL_BALANCE_MIN_CAP = 16;  // buckets the z-cap must span for the cut to be fine enough (<= ~256 lattice cells along z)
+
+struct CountCell {
+  int64_t first, count;  // points [first, first + count) of the sorted order
+  int zlo, zhi;          // bucket range, both ends included: zhi - zlo + 1 <= cap
+  unsigned column;       // the lattice's x and y cell indices (x | y << 10)
+};
+
+inline std::vector<CountCell> count_cut_cells(const unsigned* fine, int64_t n, int cap, int64_t quantum, int64_t full) {
+  std::vector<CountCell> cells;
+  cells.reserve((size_t)(n / std::max<int64_t>(full, 1)) + 16);
+  const unsigned zmask = (unsigned)CELL_ZQ - 1u;
+  for (int64_t p = 0; p < n;) {
+    const unsigned column = fine[p] >> CELL_ZQ_BITS;
+    const int zlo = (int)(fine[p] & zmask);
+    int64_t e = p + 1;
+    while (e < n && e - p < full && (fine[e] >> CELL_ZQ_BITS) == column && (int)(fine[e] & zmask) - zlo < cap) ++e;
+    const bool by_cap = e < n && e - p < full && (fine[e] >> CELL_ZQ_BITS) == column;
+    int64_t count = e - p;
+    if (by_cap && count >= quantum) count = count / quantum * quantum;
+    cells.push_back({p, count, zlo, (int)(fine[p + count - 1] & zmask), column});
+    p += count;
+  }
+  return cells;
+}
+
+// z-centre of a bucket range: the midpoint of [zlo, zhi + 1) buckets of width bw above lo, rounded once to the float32 the
+// device stores (buckets are cut in double precision, so a point is within half the range's width of it to half an ulp)
+inline float count_cell_zcentre(double lo, double bw, int zlo, int zhi) { return (float)(lo + 0.5 * (double)(zlo + zhi + 1) * bw); }
+
+// Source tiles of count-cut cells: as cell_tiles(), in cell order, the cell's id as the key
+inline TileList count_cell_source_tiles(const std::vector<CountCell>& cells, int tile = CELL_TILE) {
+  TileList l;
+  l.reserve(cells.size() * 33 + 16);
+  for (size_t i = 0; i < cells.size(); ++i) {
+    const CountCell& c = cells[i];
+    l.add_cell(c.first, c.first, c.first + c.count, (unsigned)i, (c.count + tile - 1) / tile, 0, tile);
+  }
+  return l;
+}
+
+// Target tiles of count-cut cells: split_cell_tiles() per cell, both lists padded to whole workgroups, n_main tiles then
+// n_rest (as cell_tiles_split).  The MAIN list is cut into workgroups of TT WAVES_PER_BLOCK tiles in list order, and a short
+// cell (the last of a column, or one the cap stopped) would shift every later cell off the workgroup boundary -- in cell
+// order only a fifth of the headline shape's workgroups are one-cell and take the shared operand build.  So cells whose
+// MAIN tiles fill whole workgroups come first, the others behind them, each class in cell order; slot_of maps the results
+// back, whatever the order of the list.
+inline TileList count_cell_target_tiles(const std::vector<CountCell>& cells, int TT, int64_t* n_main, int64_t* n_rest) {
+  TileList main, rest;
+  main.reserve(cells.size() * 33 + 64);
+  const int64_t per_block = (int64_t)TT * WAVES_PER_BLOCK;
+  for (int pass = 0; pass < 2; ++pass)
+    for (size_t i = 0; i < cells.size(); ++i) {
+      const CountCell& c = cells[i];
+      const CellTiles s = split_cell_tiles((c.count + CELL_TILE - 1) / CELL_TILE, TT);
+      const int64_t m = s.main_live + s.main_empty;
+      if ((m > 0 && m % per_block == 0) != (pass == 0)) continue;
+      main.add_cell(c.first, c.first, c.first + c.count, (unsigned)i, s.main_live, s.main_empty, CELL_TILE);
+      rest.add_cell(c.first, c.first + s.main_live * CELL_TILE, c.first + c.count, (unsigned)i, s.rest_live, s.rest_empty, CELL_TILE);
+    }
+  main.pad_to((size_t)per_block);
+  rest.pad_to((size_t)CELL_REST_TT * WAVES_PER_BLOCK);
+  *n_main = (int64_t)main.size();
+  *n_rest = (int64_t)rest.size();
+  main.append(rest);
+  return main;
+}
+
+// Does the count cut apply to a float32 cell list with tt tiles per wavefront, and is it taken?  opt: the "cell_balance"
+// option, -1 = automatic, 0 = never, 1 = wherever it applies.  It applies in three dimensions, at eight tiles per
+// wavefront (a cell is then one workgroup of the MAIN list), when the z-cap spans enough buckets.  Automatic also asks for
+// the sizes from which the 16x16x32 kernel is taken by itself: below them no result changes unless asked for.
+constexpr bool cell_balance_applies(int D, bool f32, int tt, int cap) {
+  return D == 3 && f32 && tt == CELL_SHARED_TT && cap >= CELL_BALANCE_MIN_CAP;
+}
+constexpr int64_t CELLMM16_AUTO_N = 500000, CELLMM16_AUTO_M = 100000;  // from here cellmm16_kernel is taken by itself (at TT = 8)
+constexpr bool cell_balance_taken(int opt, bool applies, int64_t N, int64_t M) {
+  return opt != 0 && applies && (opt > 0 || (N >= CELLMM16_AUTO_N && M >= CELLMM16_AUTO_M));
 }
 
 }  // namespace kmvp

@@ -1292,8 +1292,9 @@ int run_product_cfastmm(kmvp_ctx* c, int kernel, int sig) {
 
 // Cell order of one cloud: keys -> radix sort; the sorted keys come back to the host, where the
 // tile lists are built (one pass over n keys, once per kmvp_set_points).
+// zq_per_unit > 0 (float32, D = 3): the fine keys of count_cut_cells (kmvp_plan.hpp) instead of the lattice's.
 int cell_sort(kmvp_ctx* c, const void* pts, int64_t n, const CellGrid& grid, kmvp_ctx::DevBuf& perm,
-              std::vector<unsigned>& keys, kmvp_ctx::DevBuf* keys_dev = nullptr) {
+              std::vector<unsigned>& keys, kmvp_ctx::DevBuf* keys_dev = nullptr, double zq_per_unit = 0.0) {
   int rc;
   const int D = c->D;
   const size_t keys_bytes = (size_t)n * sizeof(unsigned);
@@ -1303,6 +1304,9 @@ int cell_sort(kmvp_ctx* c, const void* pts, int64_t n, const CellGrid& grid, kmv
   if (c->dtype == KMVP_F64)
     hipLaunchKernelGGL(cell64_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, (const double*)pts, n, D, grid,
                        b.keys_in, b.vals_in);
+  else if (zq_per_unit > 0.0)
+    hipLaunchKernelGGL(cell_fine_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, (const float*)pts, n, grid,
+                       zq_per_unit, b.keys_in, b.vals_in);
   else
     hipLaunchKernelGGL(cell_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, (const float*)pts, n, D, grid,
                        b.keys_in, b.vals_in);
@@ -1366,6 +1370,70 @@ void cell_load_grid(const kmvp_ctx* c, CellGrid& grid) {
     grid.h[a] = c->cell_hh[a];
     grid.inv_h[a] = 1.f / c->cell_hh[a];
   }
+  grid.centres = nullptr;
+}
+// The grid as the packers of one cloud take it: with that cloud's table of centres where the cells are count-cut (with
+// same_points the sources' sort, cells and table serve both sides, as cell_sperm does)
+CellGrid cell_side_grid(const kmvp_ctx* c, CellGrid grid, bool targets) {
+  if (c->cell_balanced) grid.centres = (const float*)((targets && !c->same_points) ? c->cell_tcentre.p : c->cell_scentre32.p);
+  return grid;
+}
+
+// ---- count-cut cells ("cell_balance": count_cut_cells, kmvp_plan.hpp) -------------------------------------------------------
+
+// The bounds of a count-cut cell, stated once.  Accuracy: |t| = |2 d.e| <= sum_a h_a^T h_a^S / 2 with h_a the full widths
+// of the target's and the source's cell, and both clouds' cells obey the same cap, so with the lattice's h_x and h_y the
+// z-width may reach sqrt(2 CELL_T_MAX - h_x^2 - h_y^2) (>= the lattice's own bound: 0.1095 at h_x = h_y = 0.1).  Range:
+// cellmm_scale_kernel sizes sigma_b from the real bound on |f| = 2 |e| (cellmm_fmax), so no first-order entry of A leaves
+// f16 whatever the width; CELL_Z_WIDTH_MAX = 2^-3 keeps that bound in the binade of the lattice's 0.104, so that sigma_b --
+// and with it the distance of the operands' mid parts from the subnormals -- is at most one power of two below the lattice's.
+constexpr float CELL_Z_WIDTH_MAX = 0.125f;
+constexpr float CMM_F_LATTICE = 0.104f;  // the lattice's bound on |f| in three dimensions: sqrt(2 CELL_T_MAX / 3) = 0.1033
+// The cap in buckets (0: no room); *zq_per_unit buckets per unit length, *bucket the width of one
+int cell_balance_cap(const CellGrid& grid, double* zq_per_unit, double* bucket) {
+  const double room = 2.0 * CELL_T_MAX - (double)grid.h[0] * grid.h[0] - (double)grid.h[1] * grid.h[1];
+  const double extent = (double)grid.g[2] * grid.h[2];
+  *bucket = extent / CELL_ZQ;
+  *zq_per_unit = CELL_ZQ / extent;
+  if (!(room > 0.0) || !(extent > 0.0)) return 0;
+  const double width = std::min(std::sqrt(room), (double)CELL_Z_WIDTH_MAX);
+  return (int)std::min<double>(CELL_ZQ, std::floor(width / *bucket));
+}
+
+// [cell][4] floats: the lattice's x and y centres of the cell's column, the midpoint of its bucket range in z
+int upload_cell_centres(kmvp_ctx* c, const CellGrid& grid, double bucket, const std::vector<CountCell>& cells, kmvp_ctx::DevBuf& buf) {
+  std::vector<float> tab(4 * std::max<size_t>(cells.size(), 1), 0.f);
+  for (size_t i = 0; i < cells.size(); ++i) {
+    tab[4 * i + 0] = cell_centre(cells[i].column, 0, grid);
+    tab[4 * i + 1] = cell_centre(cells[i].column, 1, grid);
+    tab[4 * i + 2] = count_cell_zcentre(grid.lo[2], bucket, cells[i].zlo, cells[i].zhi);
+  }
+  int rc;
+  if ((rc = ensure(c, buf, tab.size() * sizeof(float)))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(buf.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host vector goes out of scope
+  return KMVP_OK;
+}
+
+// Cell order, cells, tables of centres and tile lists of both clouds, cut by point count, for TT tiles per wavefront: a
+// second sort per cloud, with the fine keys, after the lattice sort has chosen TT.  Targets are cut to whole wavefronts
+// (32 TT points) where the cap stops a cell; a cloud that is only a source to whole tiles.
+int cell_prepare_balanced(kmvp_ctx* c, const CellGrid& grid, int TT, int cap, double zq_per_unit, double bucket) {
+  const int64_t quantum = (int64_t)CELL_TILE * TT, full = quantum * WAVES_PER_BLOCK;
+  int rc;
+  std::vector<unsigned> keys;
+  if ((rc = cell_sort(c, c->y_raw.p, c->M, grid, c->cell_sperm, keys, nullptr, zq_per_unit))) return rc;
+  std::vector<CountCell> cells = count_cut_cells(keys.data(), c->M, cap, c->same_points ? quantum : (int64_t)CELL_TILE, full);
+  const TileList sources = count_cell_source_tiles(cells);
+  if ((rc = upload_tiles(c, sources, c->cell_sgrp))) return rc;
+  c->cell_m_tiles = (int64_t)sources.size();
+  if ((rc = upload_cell_centres(c, grid, bucket, cells, c->cell_scentre32))) return rc;
+  if (!c->same_points) {
+    if ((rc = cell_sort(c, c->x_raw.p, c->N, grid, c->cell_tperm, keys, nullptr, zq_per_unit))) return rc;
+    cells = count_cut_cells(keys.data(), c->N, cap, quantum, full);
+    if ((rc = upload_cell_centres(c, grid, bucket, cells, c->cell_tcentre))) return rc;
+  }
+  return upload_tiles(c, count_cell_target_tiles(cells, TT, &c->cell_n_main, &c->cell_n_rest), c->cell_tgrp);
 }
 
 // picoseconds per 32 x 32 tile of pairs of the float32 cell kernels, whole chip, by the tiles a wavefront owns
@@ -1378,8 +1446,11 @@ inline double cell_ps_per_tile(int TT) { return TT >= 8 ? CMM_PS_PER_TILE_MAIN :
 // Leaves c->cell_state = 1 when the path can run, -1 when it cannot (D > 3, non-finite box, more
 // than 1024 cells along an axis).
 int cell_prepare(kmvp_ctx* c, int TT) {
-  if (c->cell_ver == c->points_ver && c->cell_state != 0 && (c->cell_state < 0 || c->cell_tt_req == TT)) return KMVP_OK;
+  if (c->cell_ver == c->points_ver && c->cell_state != 0 && c->cell_balance_req == c->opt_cell_balance &&
+      (c->cell_state < 0 || c->cell_tt_req == TT))
+    return KMVP_OK;
   c->cell_tt_req = TT;
+  c->cell_balance_req = c->opt_cell_balance;
   c->cell_ver = c->points_ver;
   c->cell_state = -1;
   const int D = c->D;
@@ -1410,7 +1481,15 @@ int cell_prepare(kmvp_ctx* c, int TT) {
       }
     }
   }
-  if ((rc = upload_tiles(c, cell_tiles_split(keys.data(), (int64_t)keys.size(), TT, &c->cell_n_main, &c->cell_n_rest), c->cell_tgrp)))
+  // count-cut cells where they apply and are asked for ("cell_balance"); otherwise the lattice's, as ever
+  double zq_per_unit, bucket;
+  const int cap = cell_balance_cap(grid, &zq_per_unit, &bucket);
+  c->cell_balanced = false;
+  if (cell_balance_taken(c->opt_cell_balance, cell_balance_applies(D, c->dtype == KMVP_F32, TT, cap), c->N, c->M)) {
+    c->cell_balanced = true;  // (cell_state stays -1 until the lists are whole)
+    c->cell_zw = (float)((double)cap * bucket);
+    if ((rc = cell_prepare_balanced(c, grid, TT, cap, zq_per_unit, bucket))) return rc;
+  } else if ((rc = upload_tiles(c, cell_tiles_split(keys.data(), (int64_t)keys.size(), TT, &c->cell_n_main, &c->cell_n_rest), c->cell_tgrp)))
     return rc;
   c->cell_n_tiles = c->cell_n_main + c->cell_n_rest;  // (both lists already padded to whole workgroups)
   c->cell_tt = TT;
@@ -1459,7 +1538,7 @@ int pack_cell_targets(kmvp_ctx* c, const CellGrid& grid) {
   if ((rc = ensure(c, c->cell_slot, (size_t)c->N * sizeof(int)))) return rc;
   hipLaunchKernelGGL(pack_cell_targets_kernel, dim3((unsigned)n_tiles), dim3(CELL_TILE), 0, c->stream, x_raw, tperm,
                      tgrp, tgrp + n_tiles, (const unsigned*)(tgrp + 2 * n_tiles), n_tiles, c->D,
-                     grid, (float*)c->xs.p, (float*)c->cell_tmeta.p, (int*)c->cell_slot.p);
+                     cell_side_grid(c, grid, true), (float*)c->xs.p, (float*)c->cell_tmeta.p, (int*)c->cell_slot.p);
   return KMVP_OK;
 }
 
@@ -1488,7 +1567,7 @@ int run_product_cell(kmvp_ctx* c, int sig) {
                        c->stream, (const float*)c->y_raw.p,
                        sig == SIG_DENSITY ? (const float*)nullptr : (const float*)c->b_raw.p,
                        (const int*)c->cell_sperm.p, sgrp, sgrp + c->cell_m_tiles,
-                       (const unsigned*)(sgrp + 2 * c->cell_m_tiles), c->cell_m_tiles, D, grid,
+                       (const unsigned*)(sgrp + 2 * c->cell_m_tiles), c->cell_m_tiles, D, cell_side_grid(c, grid, false),
                        (unsigned char*)c->rec.p);
   }
   HIP_TRY(c, hipGetLastError());
@@ -1529,12 +1608,19 @@ int run_product_cell(kmvp_ctx* c, int sig) {
 // ---- cell form with the sum over the sources in the MFMA accumulator (kmvp_cellmm.hpp): float32, D <= 3,
 // E == 1, plain product / density.  Shares grid, cell order, tile lists and the target layout with cell_kernel.
 
-// log2 of the largest W_j(T) = exp(e_j.(2 D - e_j)) on this grid: |e_a| <= h_a / 2, |D_a| <= g_a h_a
+// log2 of the largest W_j(T) = exp(e_j.(2 D - e_j)) on this grid: |e_a| <= w_a / 2, |D_a| <= g_a h_a, with w_a the cells'
+// width: the lattice's h_a, or along z the cap of count-cut cells (both clouds obey it)
 int cellmm_wlog2(const kmvp_ctx* c) {
   double arg = 0.0;
-  for (int a = 0; a < c->D; ++a) arg += (double)c->cell_hh[a] * ((double)c->cell_g[a] * c->cell_hh[a]);
+  for (int a = 0; a < c->D; ++a) {
+    const double w = (c->cell_balanced && a == 2) ? (double)c->cell_zw : (double)c->cell_hh[a];
+    arg += w * ((double)c->cell_g[a] * c->cell_hh[a]);
+  }
   return (int)std::ceil(arg * 1.4426950408889634);
 }
+// The bound on |f| = 2 |e| over all axes that cellmm_scale_kernel sizes sigma_b from: the lattice's constant, or the width
+// of count-cut cells along z where that is larger
+float cellmm_fmax(const kmvp_ctx* c) { return c->cell_balanced ? std::max(CMM_F_LATTICE, c->cell_zw) : CMM_F_LATTICE; }
 
 // One launch per signal column (and one with b = 1 for the denominator of normalised rows): the weights W_j b_j
 // live in the MFMA's source operand, so a column is an operand, not an extra fma.  E columns cost E launches of
@@ -1573,7 +1659,8 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
     if ((rc = ensure(c, c->rec, (size_t)m_stages * CMM_STAGE_BYTES))) return rc;
     hipLaunchKernelGGL(pack_cellmm_points_kernel, dim3((unsigned)(m_stages * CMM_STAGE_TILES)), dim3(CELL_TILE), 0,
                        c->stream, (const float*)c->y_raw.p, (const int*)c->cell_sperm.p, sgrp, sgrp + c->cell_m_tiles,
-                       (const unsigned*)(sgrp + 2 * c->cell_m_tiles), c->cell_m_tiles, D, grid, (unsigned char*)c->rec.p);
+                       (const unsigned*)(sgrp + 2 * c->cell_m_tiles), c->cell_m_tiles, D, cell_side_grid(c, grid, false),
+                       (unsigned char*)c->rec.p);
     HIP_TRY(c, hipGetLastError());
   }
   record_packed(c, key, image_sig);
@@ -1585,7 +1672,7 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
   // 1e6 points 27.7 -> 26.6 ms, 5e5 equal, 2e5 (smaller cells' tile groups) 1.73 -> 1.96 ms (tools/cellmm_shapes.py).  What
   // counts is how full the TARGET cells are, not the pair count: one of eight ranks' share of config 2 (1e6 targets x 125 000
   // sources) gains 3 % as well (3.72 -> 3.60 ms, tools/c2_shard.py --shape)
-  const int shape = c->opt_cellmm_shape >= 0 ? c->opt_cellmm_shape : ((TT >= 8 && c->N >= 500000 && c->M >= 100000) ? 1 : 0);
+  const int shape = c->opt_cellmm_shape >= 0 ? c->opt_cellmm_shape : ((TT >= 8 && c->N >= CELLMM16_AUTO_N && c->M >= CELLMM16_AUTO_M) ? 1 : 0);
   FusedCellGrid fg = fused_cell_grid(s, TT, c->opt_cell_fused);
   if (shape != 1) fg.fused = false;  // cellmm_kernel keeps its two launches
   CellmmArgs a;
@@ -1604,7 +1691,7 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
         hipLaunchKernelGGL(cellmm_absmax_kernel, dim3((unsigned)std::min<int64_t>(1024, (c->M + 255) / 256)), dim3(256), 0,
                            c->stream, b, c->M, E, col, bmax);
       hipLaunchKernelGGL(cellmm_scale_kernel, dim3(1), dim3(1), 0, c->stream, (const unsigned*)bmax, cellmm_wlog2(c),
-                         b ? 0 : 1, scale);
+                         cellmm_fmax(c), b ? 0 : 1, scale);
       hipLaunchKernelGGL(pack_cellmm_signal_kernel, dim3((unsigned)(m_stages * CMM_STAGE_TILES)), dim3(CELL_TILE), 0,
                          c->stream, b, E, col, (const int*)c->cell_sperm.p, sgrp, sgrp + c->cell_m_tiles, c->cell_m_tiles,
                          (const float*)scale, (unsigned char*)c->rec.p);
@@ -2158,10 +2245,12 @@ int run_product(kmvp_ctx* c, int kernel, bool normalise) {
     if (cells) {
       // cellmm_kernel (weights in the operand, sum in the accumulator) where its f16 operands have the range:
       // clouds inside the radius rule; cell_kernel otherwise (wide clouds) or on request (fast_sqdists = 4)
-      c->note.clear();
+      c->note = c->cell_balanced ? "count-cut cells: the lattice's columns cut along z by point count (cell_balance)" : "";
       if (c->opt_fast != 4 && cellmm_in_range(c))
         return run_product_cellmm(c, sig);  // normalised rows: a second launch with b = 1 for the denominator
-      if (c->opt_fast != 4) c->note = "cell_kernel instead of cellmm_kernel: the clouds are outside the radius rule (f16 operand range)";
+      if (c->opt_fast != 4)
+        c->note = std::string(c->note.empty() ? "" : c->note + "; ") +
+                  "cell_kernel instead of cellmm_kernel: the clouds are outside the radius rule (f16 operand range)";
       return run_product_cell(c, sig);
     }
     if (c->opt_fast == 1 || (c->opt_fast < 0 && global_ok)) return run_product_fast(c, kernel, sig);
