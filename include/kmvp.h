@@ -307,6 +307,49 @@ int kmvp_absexp_logsumexp_grad(kmvp_ctx* ctx);
  * buffer is world * 2 K' * N doubles on every rank. */
 int kmvp_nearest(kmvp_ctx* ctx, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);
 
+/* Batched clouds (an extension: KeOps' `ranges`, PyTorch3D's `lengths`): B clouds concatenated in the arrays of
+ * kmvp_set_points, every reduction restricted to a target's own batch -- Chamfer distances and k-NN graphs on point-cloud
+ * batches, per-sample kernel densities, per-group kernel regressions, in ONE launch instead of one upload, pack and launch
+ * per cloud.  Called after kmvp_set_points:
+ *     y_offsets, x_offsets   B + 1 int64 values each, non-decreasing, from 0 to M (respectively N): batch b owns sources
+ *                            [y_offsets[b], y_offsets[b + 1]) and targets [x_offsets[b], x_offsets[b + 1]).  Empty batches
+ *                            on either side are allowed.  Read during the call.
+ *     x_offsets_or_null      NULL only when the targets are the sources (x_or_null == NULL at kmvp_set_points): it then
+ *                            means x_offsets = y_offsets.
+ *     B == 0 with NULL pointers switches batching off; kmvp_set_points switches it off too, as it clears the solver
+ *     diagonal.  A refused call leaves the previous setting.
+ * KMVP_E_INVALID for: no points set, B < 0, a NULL y_offsets with B > 0 (non-NULL offsets with B == 0), a NULL x_offsets
+ * when the targets are not the sources, and offsets that are not monotone or do not start at 0 and end at M (respectively
+ * N).  KMVP_E_UNSUPPORTED for a batch of more than 2^31 - 8 sources.
+ * While batches are set
+ *  - kmvp_gaussian[_norm], kmvp_absexp[_norm], kmvp_matern32[_norm], kmvp_matern52[_norm] compute the block-diagonal
+ *    reduction a[i, e] = sum_{j in batch(i)} k(x_i, y_j) b[j, e].  The signal is set with kmvp_set_signal as usual: (M, E)
+ *    over the concatenated sources, NULL for density estimation.  The normalised form divides by the batch's own
+ *    sum_j k.  kmvp_get_result reads (N, E) float64 in the caller's order.  A batch without sources gives what the plain
+ *    entry gives for M == 0: rows of 0, of NaN (0 / 0) when normalised; a NaN target coordinate gives a NaN row in every
+ *    other batch.  Normalised density estimation is 1 (NaN in a batch without sources) and launches no pair loop.
+ *  - kmvp_nearest(ctx, K, 0, idx, sqdist) returns every target's K nearest sources of its own batch: indices are positions
+ *    in the concatenated y, nearest first, ties towards the smaller index; where the batch has fewer than K qualifying
+ *    sources the tail is (-1, +inf); a NaN target row is (-1, NaN) -- all as documented for the plain entry (a batch
+ *    without sources: (-1, +inf) throughout, the plain entry's M == 0).
+ *  - every row depends on its own batch alone: it is the same bit for bit whatever the other batches hold, wherever the
+ *    batch stands among them, alone (B = 1) and run to run.
+ *  - everything else returns KMVP_E_UNSUPPORTED with a message that names the batches: kmvp_invdist[_norm] (its flat-index
+ *    zero rule has no per-batch definition), kmvp_expdot[_norm], the gradients, the length-scale derivatives, the
+ *    log-sum-exp and its gradient, the solvers, the Lanczos quadratures, Sinkhorn, k-means, mean-shift, and kmvp_nearest
+ *    with exclude_self != 0.  So do the products and kmvp_nearest themselves on a bfloat16 context, at D > 8, with E > 4
+ *    signal columns (normalised rows included: the denominator rides along as lowd_kernel's does), with an explicit
+ *    "fast_sqdists" of 1 .. 4, with a communicator attached and on a source slice (M < M_total).
+ *  - kmvp_last_kernel_name is "lowd_batch_kernel" or "lowd_batch_knn_kernel" (csrc/kmvp_lowd_batch.hpp: lowd_kernel's
+ *    scalar-cache feed with one source range per wavefront; plan and layout: csrc/kmvp_batch_plan.hpp),
+ *    kmvp_last_dispatch_note is "", kmvp_last_kernel_ms / kmvp_last_total_ms as for a product.  "chunk" is honoured (the
+ *    float32 chain between folds into float64, rounded up to 8); "segments", "feed" and "targets_per_lane" are accepted
+ *    and ignored: a batch is never cut into segments, so a batch with few targets and very many sources runs on few waves.
+ * With batches off every entry returns bit for bit what it returns without this call ever made: target image, records,
+ * tile table and index maps of the batches live in buffers of their own on the context, and the product's pack
+ * bookkeeping is not touched. */
+int kmvp_set_batches(kmvp_ctx* ctx, int B, const int64_t* y_offsets, const int64_t* x_offsets_or_null);
+
 /* Lloyd's k-means, resident on the device (an extension: the solver on top of the arg-K-min at K = 1, as the Krylov
  * solvers are on top of the product and Sinkhorn on top of the log-sum-exp).  Kernel-independent, like kmvp_nearest.  The
  * points are the TARGETS of the context -- x (N,D), or the cloud itself when x_or_null == NULL; the context's sources and

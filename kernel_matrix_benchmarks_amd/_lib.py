@@ -55,6 +55,7 @@ SYMBOLS = [
     ("kmvp_gaussian_logsumexp_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_absexp_logsumexp_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_nearest", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    ("kmvp_set_batches", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
     ("kmvp_kmeans", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
                                _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
     ("kmvp_gaussian_meanshift", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -155,6 +156,21 @@ def input_rounding(precision):
     return np.dtype(np.float16) if np.dtype(precision) == np.float16 else None
 
 
+def batch_offsets(offsets, what, total=None):
+    """Offsets of B >= 1 batches as a contiguous int64 array of B + 1 values: one-dimensional and of an integer dtype;
+    with ``total`` also non-decreasing from 0 to ``total`` (None: left to the library, which answers KMVP_E_INVALID).
+    ValueError otherwise -- decided on the host."""
+    a = np.asarray(offsets)
+    if a.ndim != 1 or a.size < 2:
+        raise ValueError(f"{what} has shape {a.shape}, expected B + 1 offsets (B >= 1) in one dimension")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{what} has dtype {a.dtype}, expected integers")
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    if total is not None and (a[0] != 0 or np.any(np.diff(a) < 0) or a[-1] != total):
+        raise ValueError(f"{what} must be non-decreasing from 0 to {total}")
+    return a
+
+
 class Context:
     """Owns one kmvp_ctx (one GPU).  Thin, typed wrappers; all errors raise KmvpError."""
 
@@ -193,6 +209,23 @@ class Context:
         self._check(self._lib.kmvp_set_points(
             self._ctx, y.ctypes.data, M, None if x is None else x.ctypes.data, N, D, dtype_code_,
             int(j_offset), int(M if M_total is None else M_total)))
+
+    def set_batches(self, y_offsets, x_offsets=None):
+        """Batched clouds (include/kmvp.h kmvp_set_batches): offsets of B + 1 values over the sources and -- None: the
+        sources' own, same points only -- over the targets.  set_batches(None) switches the batches off."""
+        if y_offsets is None:
+            if x_offsets is not None:
+                raise ValueError("target offsets without source offsets")
+            self._check(self._lib.kmvp_set_batches(self._ctx, 0, None, None))
+            return
+        # the library reads B + 1 values from each pointer: arrays of another length must never reach it
+        y_offsets = batch_offsets(y_offsets, "source_batches")
+        if x_offsets is not None:
+            x_offsets = batch_offsets(x_offsets, "target_batches")
+            if x_offsets.size != y_offsets.size:
+                raise ValueError(f"target_batches has {x_offsets.size} offsets, source_batches {y_offsets.size}: both hold B + 1")
+        self._check(self._lib.kmvp_set_batches(self._ctx, y_offsets.size - 1, y_offsets.ctypes.data,
+                                               None if x_offsets is None else x_offsets.ctypes.data))
 
     def fit(self, kernel):
         self._check(self._lib.kmvp_fit(self._ctx, FIT_CODES[kernel]))

@@ -59,6 +59,7 @@ GRADIENT_MAX_D, GRADIENT_MAX_E = 8, 4  # lowd_grad_kernel's instantiations (csrc
 SCALE_DERIVATIVE_KERNELS = ("gaussian", "absolute-exponential", "matern-3/2", "matern-5/2")
 # lowd_lse_kernel: the log-sum-exp reduction is built for these kernels, at the gradient's shapes
 LOGSUMEXP_KERNELS = ("gaussian", "absolute-exponential")
+BATCHED_KERNELS = ("gaussian", "absolute-exponential", "matern-3/2", "matern-5/2")  # kmvp_set_batches
 LOGSUMEXP_MAX_D, LOGSUMEXP_MAX_E = 8, 4
 # lowd_knn_kernel: K nearest neighbours, at the gradient's dimensions; K + 1 candidates are collected with exclude_self
 NEAREST_MAX_D, NEAREST_MAX_K = 8, 16
@@ -141,10 +142,15 @@ class MI355XProduct(BaseProduct):
 
     # -- untimed -------------------------------------------------------------------
     def prepare_data(self, *, source_points, target_points, same_points=False,
-                     density_estimation=False):
+                     density_estimation=False, source_batches=None, target_batches=None):
+        """source_batches / target_batches: B + 1 offsets each into the concatenated sources / targets -- batched clouds
+        (include/kmvp.h kmvp_set_batches): query() is then the block-diagonal product and query_nearest() stays within a
+        target's own batch; the other query_* methods raise the library's error.  target_batches=None with
+        same_points=True means the sources' offsets."""
         # h5py hands numpy.bool_ attributes over (runner.py:41-43)
         self.same_points = bool(same_points)
         self.density_estimation = bool(density_estimation)
+        batches = self._check_batches(source_points, target_points, source_batches, target_batches)
         self._dot_note = ""
         if self._dot:
             d_in = np.asarray(source_points).shape[1]
@@ -213,6 +219,40 @@ class MI355XProduct(BaseProduct):
             self._shard = (0, self.M)
             self._order = None
             self._ctx.set_points(y, x, self._dtype_code)
+        self._batched = batches is not None
+        if batches is not None:
+            self._ctx.set_batches(*batches)
+
+    def _check_batches(self, source_points, target_points, source_batches, target_batches):
+        """The offsets of batched clouds as (source offsets, target offsets or None), or None without batches: everything
+        the host can decide (shape, dtype, monotonicity, what the batches are not built for) is refused here, before any
+        device call."""
+        if source_batches is None and target_batches is None:
+            return None
+        if source_batches is None:
+            raise ValueError("target_batches needs source_batches")
+        if target_batches is None and not self.same_points:
+            raise ValueError("target_batches=None needs same_points=True (the sources' offsets then serve both)")
+        M = np.asarray(source_points).shape[0]
+        yb = _lib.batch_offsets(source_batches, "source_batches", M)
+        xb = None
+        if target_batches is not None:
+            N = M if self.same_points else np.asarray(target_points).shape[0]
+            xb = _lib.batch_offsets(target_batches, "target_batches", N)
+            if xb.size != yb.size:
+                raise ValueError(f"target_batches has {xb.size} offsets, source_batches {yb.size}: both hold B + 1")
+        what = None
+        if self.kernel not in BATCHED_KERNELS:
+            what = f"kernel={self.kernel!r} (gaussian, absolute-exponential, matern-3/2 and matern-5/2 only)"
+        elif self._dtype_code == _lib.KMVP_BF16:
+            what = "precision='bfloat16' (float16, float32 and float64 only)"
+        elif self.fast_sqdists not in (None, False):
+            what = f"fast_sqdists={self.fast_sqdists!r} (the difference form only: None or False)"
+        elif self.comm is not None and self.comm.world > 1:
+            what = "sources sharded over ranks (comm=)"
+        if what is not None:
+            raise NotImplementedError(f"MI355XProduct doesn't support batched clouds with {what}.")
+        return yb, xb
 
     def prepare_query(self, *, source_signal):
         if self._dot_native and self.density_estimation:

@@ -90,7 +90,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
                     &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     release(*b);
   for (int i = 0; i < 5; ++i)
@@ -136,6 +136,8 @@ int kmvp_set_points(kmvp_ctx* c, const void* y, int64_t M, const void* x_or_null
   c->diag_ridge = c->diag_min = 0.0;
   c->precond_rank = 0;  // and so does the preconditioner, built from them and from that diagonal
   c->pc_used = 0;
+  c->bt_on = false;  // and so do the batches (kmvp_set_batches): offsets into the previous clouds
+  c->bt_B = 0;
   ++c->points_ver;
   return KMVP_OK;
 }
@@ -169,40 +171,55 @@ int kmvp_set_signal(kmvp_ctx* c, const void* b_or_null, int E) {
   return KMVP_OK;
 }
 
-int kmvp_gaussian(kmvp_ctx* c) { return run_product(c, K_GAUSSIAN, false); }
-int kmvp_gaussian_norm(kmvp_ctx* c) { return run_product(c, K_GAUSSIAN, true); }
-int kmvp_absexp(kmvp_ctx* c) { return run_product(c, K_ABSEXP, false); }
-int kmvp_absexp_norm(kmvp_ctx* c) { return run_product(c, K_ABSEXP, true); }
-int kmvp_invdist(kmvp_ctx* c) { return run_product(c, K_INVDIST, false); }
-int kmvp_invdist_norm(kmvp_ctx* c) { return run_product(c, K_INVDIST, true); }
-int kmvp_expdot(kmvp_ctx* c) { return run_product(c, K_EXPDOT, false); }
-int kmvp_expdot_norm(kmvp_ctx* c) { return run_product(c, K_EXPDOT, true); }
-int kmvp_matern32(kmvp_ctx* c) { return run_product(c, K_MATERN32, false); }
-int kmvp_matern32_norm(kmvp_ctx* c) { return run_product(c, K_MATERN32, true); }
-int kmvp_matern52(kmvp_ctx* c) { return run_product(c, K_MATERN52, false); }
-int kmvp_matern52_norm(kmvp_ctx* c) { return run_product(c, K_MATERN52, true); }
-int kmvp_gaussian_grad(kmvp_ctx* c) { return run_gradient(c, K_GAUSSIAN); }
-int kmvp_absexp_grad(kmvp_ctx* c) { return run_gradient(c, K_ABSEXP); }
-int kmvp_invdist_grad(kmvp_ctx* c) { return run_gradient(c, K_INVDIST); }
-int kmvp_matern32_grad(kmvp_ctx* c) { return run_gradient(c, K_MATERN32); }
-int kmvp_matern52_grad(kmvp_ctx* c) { return run_gradient(c, K_MATERN52); }
-int kmvp_gaussian_dscale(kmvp_ctx* c) { return run_dscale(c, K_GAUSSIAN); }
-int kmvp_absexp_dscale(kmvp_ctx* c) { return run_dscale(c, K_ABSEXP); }
-int kmvp_matern32_dscale(kmvp_ctx* c) { return run_dscale(c, K_MATERN32); }
-int kmvp_matern52_dscale(kmvp_ctx* c) { return run_dscale(c, K_MATERN52); }
-int kmvp_gaussian_logsumexp(kmvp_ctx* c) { return run_logsumexp(c, K_GAUSSIAN); }
-int kmvp_absexp_logsumexp(kmvp_ctx* c) { return run_logsumexp(c, K_ABSEXP); }
-int kmvp_gaussian_logsumexp_grad(kmvp_ctx* c) { return run_logsumexp_grad(c, K_GAUSSIAN); }
-int kmvp_absexp_logsumexp_grad(kmvp_ctx* c) { return run_logsumexp_grad(c, K_ABSEXP); }
+// Batched clouds (kmvp_set_batches; kmvp_batch.hip): the four products below and kmvp_nearest go to their block-diagonal
+// forms while batches are set; every other compute entry is refused with a message that names them.
+static inline bool batched(const kmvp_ctx* c) { return c && c->bt_on; }
+#define KMVP_NOT_BATCHED(c, what)                   \
+  do {                                              \
+    if (int rc_ = batches_refuse((c), (what))) return rc_; \
+  } while (0)
+
+int kmvp_set_batches(kmvp_ctx* c, int B, const int64_t* y_offsets, const int64_t* x_offsets_or_null) {
+  return set_batches(c, B, y_offsets, x_offsets_or_null);
+}
+
+int kmvp_gaussian(kmvp_ctx* c) { return batched(c) ? run_product_batched(c, K_GAUSSIAN, false) : run_product(c, K_GAUSSIAN, false); }
+int kmvp_gaussian_norm(kmvp_ctx* c) { return batched(c) ? run_product_batched(c, K_GAUSSIAN, true) : run_product(c, K_GAUSSIAN, true); }
+int kmvp_absexp(kmvp_ctx* c) { return batched(c) ? run_product_batched(c, K_ABSEXP, false) : run_product(c, K_ABSEXP, false); }
+int kmvp_absexp_norm(kmvp_ctx* c) { return batched(c) ? run_product_batched(c, K_ABSEXP, true) : run_product(c, K_ABSEXP, true); }
+int kmvp_invdist(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the inverse-distance product"); return run_product(c, K_INVDIST, false); }
+int kmvp_invdist_norm(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the inverse-distance product"); return run_product(c, K_INVDIST, true); }
+int kmvp_expdot(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "exp(<x,y>)"); return run_product(c, K_EXPDOT, false); }
+int kmvp_expdot_norm(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "exp(<x,y>)"); return run_product(c, K_EXPDOT, true); }
+int kmvp_matern32(kmvp_ctx* c) { return batched(c) ? run_product_batched(c, K_MATERN32, false) : run_product(c, K_MATERN32, false); }
+int kmvp_matern32_norm(kmvp_ctx* c) { return batched(c) ? run_product_batched(c, K_MATERN32, true) : run_product(c, K_MATERN32, true); }
+int kmvp_matern52(kmvp_ctx* c) { return batched(c) ? run_product_batched(c, K_MATERN52, false) : run_product(c, K_MATERN52, false); }
+int kmvp_matern52_norm(kmvp_ctx* c) { return batched(c) ? run_product_batched(c, K_MATERN52, true) : run_product(c, K_MATERN52, true); }
+int kmvp_gaussian_grad(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the gradient"); return run_gradient(c, K_GAUSSIAN); }
+int kmvp_absexp_grad(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the gradient"); return run_gradient(c, K_ABSEXP); }
+int kmvp_invdist_grad(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the gradient"); return run_gradient(c, K_INVDIST); }
+int kmvp_matern32_grad(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the gradient"); return run_gradient(c, K_MATERN32); }
+int kmvp_matern52_grad(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the gradient"); return run_gradient(c, K_MATERN52); }
+int kmvp_gaussian_dscale(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the length-scale derivative"); return run_dscale(c, K_GAUSSIAN); }
+int kmvp_absexp_dscale(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the length-scale derivative"); return run_dscale(c, K_ABSEXP); }
+int kmvp_matern32_dscale(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the length-scale derivative"); return run_dscale(c, K_MATERN32); }
+int kmvp_matern52_dscale(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the length-scale derivative"); return run_dscale(c, K_MATERN52); }
+int kmvp_gaussian_logsumexp(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the log-sum-exp"); return run_logsumexp(c, K_GAUSSIAN); }
+int kmvp_absexp_logsumexp(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the log-sum-exp"); return run_logsumexp(c, K_ABSEXP); }
+int kmvp_gaussian_logsumexp_grad(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the gradient of the log-sum-exp"); return run_logsumexp_grad(c, K_GAUSSIAN); }
+int kmvp_absexp_logsumexp_grad(kmvp_ctx* c) { KMVP_NOT_BATCHED(c, "the gradient of the log-sum-exp"); return run_logsumexp_grad(c, K_ABSEXP); }
 int kmvp_nearest(kmvp_ctx* c, int K, int exclude_self, int64_t* out_idx, double* out_sqdist) {
+  if (batched(c)) return run_nearest_batched(c, K, exclude_self, out_idx, out_sqdist);
   return run_nearest(c, K, exclude_self, out_idx, out_sqdist);
 }
 int kmvp_kmeans(kmvp_ctx* c, int C, const double* weights, double tol, int maxit, double* centroids, int64_t* labels,
                 double* cluster_weight, int* iters, double* inertia, double* shift) {
+  KMVP_NOT_BATCHED(c, "k-means");
   return kmeans_solve(c, C, weights, tol, maxit, centroids, labels, cluster_weight, iters, inertia, shift);
 }
 int kmvp_gaussian_meanshift(kmvp_ctx* c, double tol, int maxit, double* modes, int* iters, double* step2, int* sweeps,
                             int64_t* target_sweeps) {
+  KMVP_NOT_BATCHED(c, "mean-shift");
   return meanshift_solve(c, tol, maxit, modes, iters, step2, sweeps, target_sweeps);
 }
 
@@ -221,23 +238,28 @@ int kmvp_get_result(kmvp_ctx* c, double* out, int64_t out_len) {
 
 int kmvp_gaussian_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
                            int* iters, double* resid) {
+  KMVP_NOT_BATCHED(c, "the solver");
   return cg_solve(c, K_GAUSSIAN, a, E, rtol, maxit, out_b, iters, resid);
 }
 int kmvp_absexp_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
                          int* iters, double* resid) {
+  KMVP_NOT_BATCHED(c, "the solver");
   return cg_solve(c, K_ABSEXP, a, E, rtol, maxit, out_b, iters, resid);
 }
 int kmvp_matern32_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
                            int* iters, double* resid) {
+  KMVP_NOT_BATCHED(c, "the solver");
   return cg_solve(c, K_MATERN32, a, E, rtol, maxit, out_b, iters, resid);
 }
 int kmvp_matern52_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
                            int* iters, double* resid) {
+  KMVP_NOT_BATCHED(c, "the solver");
   return cg_solve(c, K_MATERN52, a, E, rtol, maxit, out_b, iters, resid);
 }
 
 int kmvp_invdist_minres_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,
                               int* iters, double* resid) {
+  KMVP_NOT_BATCHED(c, "the solver");
   if (c && c->precond_rank > 0)
     return fail(c, KMVP_E_UNSUPPORTED, "preconditioner: MINRES has none (the inverse-distance matrix is indefinite); set rank 0");
   return minres_solve(c, K_INVDIST, a, E, rtol, maxit, out_b, iters, resid);
@@ -245,18 +267,22 @@ int kmvp_invdist_minres_solve(kmvp_ctx* c, const void* a, int E, double rtol, in
 
 int kmvp_gaussian_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double rtol, int maxit, double* logquad,
                                      double* invquad, int* steps, double* x, double* alpha, double* beta) {
+  KMVP_NOT_BATCHED(c, "the Lanczos quadrature");
   return cg_lanczos(c, K_GAUSSIAN, z, P, rtol, maxit, logquad, invquad, steps, x, alpha, beta);
 }
 int kmvp_absexp_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double rtol, int maxit, double* logquad,
                                    double* invquad, int* steps, double* x, double* alpha, double* beta) {
+  KMVP_NOT_BATCHED(c, "the Lanczos quadrature");
   return cg_lanczos(c, K_ABSEXP, z, P, rtol, maxit, logquad, invquad, steps, x, alpha, beta);
 }
 int kmvp_matern32_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double rtol, int maxit, double* logquad,
                                      double* invquad, int* steps, double* x, double* alpha, double* beta) {
+  KMVP_NOT_BATCHED(c, "the Lanczos quadrature");
   return cg_lanczos(c, K_MATERN32, z, P, rtol, maxit, logquad, invquad, steps, x, alpha, beta);
 }
 int kmvp_matern52_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double rtol, int maxit, double* logquad,
                                      double* invquad, int* steps, double* x, double* alpha, double* beta) {
+  KMVP_NOT_BATCHED(c, "the Lanczos quadrature");
   return cg_lanczos(c, K_MATERN52, z, P, rtol, maxit, logquad, invquad, steps, x, alpha, beta);
 }
 
@@ -264,6 +290,7 @@ int kmvp_matern52_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double r
   int kmvp_##NAME##_lanczos_quadrature_precond(kmvp_ctx* c, const double* g, const double* h, int P, double rtol, int maxit,  \
                                                double* logdet_p, double* logquad, double* invquad, double* wnorm2,           \
                                                int* steps, double* x, double* pz, double* alpha, double* beta) {             \
+    KMVP_NOT_BATCHED(c, "the Lanczos quadrature");                                                                          \
     return cg_lanczos_precond(c, K, g, h, P, rtol, maxit, logdet_p, logquad, invquad, wnorm2, steps, x, pz, alpha, beta);    \
   }
 KMVP_LANCZOS_PRECOND_ENTRY(gaussian, K_GAUSSIAN)
@@ -274,10 +301,12 @@ KMVP_LANCZOS_PRECOND_ENTRY(matern52, K_MATERN52)
 
 int kmvp_gaussian_sinkhorn(kmvp_ctx* c, const double* log_a, const double* log_b, double tol, int maxit, double* u, double* v,
                            int* iters, double* err) {
+  KMVP_NOT_BATCHED(c, "the Sinkhorn iteration");
   return sinkhorn_solve(c, K_GAUSSIAN, log_a, log_b, tol, maxit, u, v, iters, err);
 }
 int kmvp_absexp_sinkhorn(kmvp_ctx* c, const double* log_a, const double* log_b, double tol, int maxit, double* u, double* v,
                          int* iters, double* err) {
+  KMVP_NOT_BATCHED(c, "the Sinkhorn iteration");
   return sinkhorn_solve(c, K_ABSEXP, log_a, log_b, tol, maxit, u, v, iters, err);
 }
 
@@ -450,7 +479,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
                           &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     t += b->cap;
   return (int64_t)t;

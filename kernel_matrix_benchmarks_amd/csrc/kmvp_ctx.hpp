@@ -6,6 +6,7 @@
 //   kmvp_sinkhorn.hip the Sinkhorn iteration of entropic optimal transport on the log-sum-exp
 //   kmvp_kmeans.hip   Lloyd's k-means on the arg-K-min at K = 1
 //   kmvp_meanshift.hip Gaussian mean-shift on the gradient of the log-sum-exp
+//   kmvp_batch.hip    batched clouds: block-diagonal products and nearest neighbours on layouts of their own
 //   kmvp_precond.hip  the pivoted-Cholesky preconditioner of conjugate gradients: build, apply, read-back
 #pragma once
 #include <dlfcn.h>
@@ -156,6 +157,18 @@ struct kmvp_ctx {
   // mean-shift (kmvp_meanshift.hip): the moving target image of the active points, the fp64 state (positions, step2, the
   // state words, iters, the two index lists, the keep flags) and the scratch of the stream compaction
   DevBuf ms_xs, ms_state, ms_tmp;
+  // batched clouds (kmvp_set_batches; kmvp_batch.hip): the plan's tile table and its two index maps, and layouts of their
+  // own -- the target image over the padded slots and the source records of all ranges
+  DevBuf bt_tiles, bt_tmap, bt_smap, bt_xs, bt_rec;
+  bool bt_on = false;           // batches are set: the products and kmvp_nearest are block-diagonal, the rest is refused
+  int bt_B = 0;
+  int64_t bt_n_pad = 0, bt_m_alloc = 0;  // target slots and records of the plan
+  uint64_t bt_ver = 0;          // counts accepted kmvp_set_batches calls with B > 0
+  uint64_t bt_xs_points_ver = 0, bt_xs_ver = 0;    // points / plan version bt_xs was packed from (0: none)
+  uint64_t bt_rec_points_ver = 0, bt_rec_ver = 0;  // the same for the coordinates in bt_rec, laid out for records of
+  int bt_rec_R = 0;                                // bt_rec_R reals
+  uint64_t bt_sig_ver = 0;      // signal version the records' signal slots hold (0: none), of
+  int bt_sig_EB = -1;           // bt_sig_EB columns
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
   int packed_layout = -1;  // LAYOUT_* of the path that owns xs / rec right now
@@ -304,6 +317,14 @@ int sinkhorn_solve(kmvp_ctx* c, int kernel, const double* log_a, const double* l
 // kmvp_kmeans.hip: kmvp_kmeans, the device-resident Lloyd iteration on lowd_knn_kernel<D, 1>
 int kmeans_solve(kmvp_ctx* c, int C, const double* weights, double tol, int maxit, double* centroids, int64_t* labels,
                  double* cluster_weight, int* iters, double* inertia, double* shift);
+
+// kmvp_batch.hip: batched clouds (kmvp_set_batches) -- the plan, the gather-packed layouts, the block-diagonal product
+// and nearest neighbours on lowd_batch_kernel / lowd_batch_knn_kernel.  batches_refuse: KMVP_OK with batches off, else
+// KMVP_E_UNSUPPORTED with a message that names `what` and the batches (the entries that are not built for them).
+int set_batches(kmvp_ctx* c, int B, const int64_t* y_offsets, const int64_t* x_offsets_or_null);
+int run_product_batched(kmvp_ctx* c, int kernel, bool normalise);
+int run_nearest_batched(kmvp_ctx* c, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);
+int batches_refuse(kmvp_ctx* c, const char* what);
 
 // kmvp_meanshift.hip: kmvp_gaussian_meanshift, the device-resident mean-shift iteration on lowd_lse_grad_kernel
 int meanshift_solve(kmvp_ctx* c, double tol, int maxit, double* modes, int* iters, double* step2, int* sweeps,

@@ -194,6 +194,22 @@ static __global__ void knn_merge_kernel(const double* __restrict__ lists, double
   knn_merge(lists + i, list_stride, elem_stride, S, KT, Kc, cand + i, cand + (int64_t)Kc * n + i, n);
 }
 
+// Last step of kmvp_nearest, plain (kmvp_product.hip) and batched (kmvp_batch.hip): cand [2 Kc][n] (modified in place by the exclude-self drop) -> idx (n, K) int64, sqdist (n, K) float64
+// (static: a kernel cannot be inline; each of the two units that launch it carries its own copy, the others none)
+static __global__ void knn_finish_kernel(double* __restrict__ cand, int64_t* __restrict__ idx, double* __restrict__ sqdist,
+                                         int64_t n, int K, int exclude_self) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int Kc = K + (exclude_self ? 1 : 0);
+  double* s = cand + i;
+  double* j = cand + (int64_t)Kc * n + i;
+  if (exclude_self) knn_drop_self(s, j, n, Kc, i);
+  for (int k = 0; k < K; ++k) {
+    sqdist[i * K + k] = s[(int64_t)k * n];
+    idx[i * K + k] = (int64_t)j[(int64_t)k * n];
+  }
+}
+
 // Gradient of the log-sum-exp with respect to the targets (kmvp_lowd_lse_grad.hpp; kmvp_lowd_lse_grad_inst.hip, one unit
 // per kernel x precision): the same shapes.  args.part: [segments][(D + 2) NC][n_pad] -- row k NC + c holds sum k of
 // column c (k = 0: the denominator, k = 1 + d: component d of the numerator), rows (D + 1) NC + c the exponents.

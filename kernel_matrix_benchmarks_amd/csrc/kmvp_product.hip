@@ -2447,20 +2447,7 @@ static __global__ void knn_fill_kernel(double* __restrict__ cand, int64_t n, int
   cand[q] = q < (int64_t)Kc * n ? (double)INFINITY : -1.0;
 }
 
-// cand [2 Kc][n] (modified in place by the exclude-self drop) -> idx (n, K) int64, sqdist (n, K) float64
-static __global__ void knn_finish_kernel(double* __restrict__ cand, int64_t* __restrict__ idx, double* __restrict__ sqdist,
-                                         int64_t n, int K, int exclude_self) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int Kc = K + (exclude_self ? 1 : 0);
-  double* s = cand + i;
-  double* j = cand + (int64_t)Kc * n + i;
-  if (exclude_self) knn_drop_self(s, j, n, Kc, i);
-  for (int k = 0; k < K; ++k) {
-    sqdist[i * K + k] = s[(int64_t)k * n];
-    idx[i * K + k] = (int64_t)j[(int64_t)k * n];
-  }
-}
+// (knn_finish_kernel: kmvp_internal.hpp, shared with the batched clouds.)
 
 template <typename real>
 static int run_nearest_t(kmvp_ctx* c, int Kc) {
