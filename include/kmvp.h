@@ -747,6 +747,24 @@ const char* kmvp_last_kernel_name(const kmvp_ctx* ctx);
  * pair that is not built is replaced by (1, 1) or (2, 0) without an error. */
 const char* kmvp_last_dispatch_note(const kmvp_ctx* ctx);
 
+
+/* The cell layout of the last product on the cell form (cell_kernel, cellmm_kernel, cellmm16_kernel, cell64_kernel), read
+ * back from the structures that kernel read: test infrastructure (oracle/kmvp_cell_model.py takes it as data), read-only.
+ * KMVP_E_INVALID unless such a product has run on the current points.
+ *   info[8]          [0] source cells, in the order the kernels walk them; [1] target cells; [2] 1 = the cells are
+ *                    count-cut ("cell_balance"), 0 = the lattice's; [3] target tiles per wavefront in use; [4] points per
+ *                    target tile (32; float64: 128); [5] whose source image: 0 = cell_kernel's, 1 = cellmm_kernel's /
+ *                    cellmm16_kernel's, 2 = cell64_kernel's records; [6], [7] target tiles of the list of whole groups and
+ *                    of the leftover list (float32)
+ *   sigma_b          the power of two the signal of the LAST column was scaled by (cellmm_kernel, cellmm16_kernel; else 0)
+ *   source_cell [M], target_cell [N]   the cell of every point: an index into the centres below; -1 = in no tile, -2 = in
+ *                    more than one.  A cell of the leftover list is the cell of the same centre in the list of whole groups
+ *   source_centres [3 source_cap], target_centres [3 target_cap]   the stored centres (the float32 kernels' are float32
+ *                    values); KMVP_E_INVALID when a capacity is below the number of cells, which info then holds
+ * Every pointer but info may be NULL: ask for the counts first. */
+int kmvp_cell_layout(kmvp_ctx* ctx, int64_t* info, double* sigma_b, int32_t* source_cell, int32_t* target_cell,
+                     double* source_centres, int64_t source_cap, double* target_centres, int64_t target_cap);
+
 #ifdef __cplusplus
 }
 #endif

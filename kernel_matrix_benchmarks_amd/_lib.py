@@ -97,6 +97,8 @@ SYMBOLS = [
     ("kmvp_device_bytes", _c.c_int64, [_c.c_void_p]),
     ("kmvp_last_kernel_ms", _c.c_double, [_c.c_void_p]),
     ("kmvp_last_total_ms", _c.c_double, [_c.c_void_p]),
+    ("kmvp_cell_layout", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_double), _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                    _c.c_int64, _c.c_void_p, _c.c_int64]),
     ("kmvp_last_kernel_name", _c.c_char_p, [_c.c_void_p]),
     ("kmvp_last_dispatch_note", _c.c_char_p, [_c.c_void_p]),
 ]
@@ -597,6 +599,25 @@ class Context:
     @property
     def last_dispatch_note(self):
         return self._lib.kmvp_last_dispatch_note(self._ctx).decode()
+
+    def cell_layout(self):
+        """The cell layout of the last product on the cell form (include/kmvp.h kmvp_cell_layout), read-only: a dict of
+        source_cell (M,) and target_cell (N,) int32 (an index into the centres; -1: in no tile, -2: in more than one),
+        source_centres and target_centres (cells, 3) float64, count_cut, tiles_per_wavefront, tile_points, image (0
+        cell_kernel, 1 cellmm_kernel / cellmm16_kernel, 2 cell64_kernel), main_tiles, rest_tiles and sigma_b."""
+        if not self._ctx:
+            raise ValueError("the context is closed")
+        info = np.zeros(8, dtype=np.int64)
+        sigma = ctypes.c_double(0.0)
+        self._check(self._lib.kmvp_cell_layout(self._ctx, info.ctypes.data, ctypes.byref(sigma), None, None, None, 0, None, 0))
+        ns, nt = int(info[0]), int(info[1])
+        scell, tcell = np.empty(self.M, dtype=np.int32), np.empty(self.N, dtype=np.int32)
+        scen, tcen = np.empty((max(ns, 1), 3)), np.empty((max(nt, 1), 3))
+        self._check(self._lib.kmvp_cell_layout(self._ctx, info.ctypes.data, ctypes.byref(sigma), scell.ctypes.data,
+                                               tcell.ctypes.data, scen.ctypes.data, ns, tcen.ctypes.data, nt))
+        return {"source_cell": scell, "target_cell": tcell, "source_centres": scen[:ns], "target_centres": tcen[:nt],
+                "count_cut": bool(info[2]), "tiles_per_wavefront": int(info[3]), "tile_points": int(info[4]),
+                "image": int(info[5]), "main_tiles": int(info[6]), "rest_tiles": int(info[7]), "sigma_b": float(sigma.value)}
 
 
 def comm_unique_id():

@@ -487,6 +487,11 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
 double kmvp_last_kernel_ms(const kmvp_ctx* c) { return c ? c->last_kernel_ms : 0.0; }
 double kmvp_last_total_ms(const kmvp_ctx* c) { return c ? c->last_total_ms : 0.0; }
 double kmvp_last_allreduce_ms(const kmvp_ctx* c) { return c ? c->last_allreduce_ms : 0.0; }
+int kmvp_cell_layout(kmvp_ctx* c, int64_t* info, double* sigma_b, int32_t* source_cell, int32_t* target_cell,
+                     double* source_centres, int64_t source_cap, double* target_centres, int64_t target_cap) {
+  if (!c) return KMVP_E_INVALID;
+  return cell_layout_read(c, info, sigma_b, source_cell, target_cell, source_centres, source_cap, target_centres, target_cap);
+}
 const char* kmvp_last_kernel_name(const kmvp_ctx* c) { return c ? c->last_kernel_name : ""; }
 const char* kmvp_last_dispatch_note(const kmvp_ctx* c) { return c ? c->note.c_str() : ""; }
 

@@ -299,6 +299,10 @@ void precond_logdiag(kmvp_ctx* c, double* out);
 // kmvp_get_solver_preconditioner
 int precond_read(kmvp_ctx* c, int* rank_built, int64_t* pivots, double* factor);
 
+// kmvp_product.hip: kmvp_cell_layout, the cell structures the last product on the cell form ran on, read back
+int cell_layout_read(kmvp_ctx* c, int64_t* info, double* sigma_b, int32_t* source_cell, int32_t* target_cell,
+                     double* source_centres, int64_t source_cap, double* target_centres, int64_t target_cap);
+
 // kmvp_solvers.hip
 int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit, double* out_b,
              int* iters, double* resid);

@@ -4,6 +4,9 @@
 //   segment reduction -> [RCCL all-reduce over the source shards] -> normalise.
 // Reference call this serves: BruteForceProductBLAS.query (bruteforce.py:130-153).
 #include "kmvp_ctx.hpp"
+#include <array>
+#include <cstring>
+#include <map>
 #include <vector>
 #include "kmvp_cell_pack.hpp"
 #include "kmvp_cell64_pack.hpp"
@@ -2070,6 +2073,132 @@ int prepare_points(kmvp_ctx* c, int kernel) {
   if (kernel != K_GAUSSIAN || c->D > CELL_MAX_D || c->N == 0 || c->M == 0 || c->centre_ver != c->points_ver) return KMVP_OK;
   if (c->dtype == KMVP_F32 && cells_considered(c, false)) return cell_prepare(c, cell_tiles_request(c));
   if (c->dtype == KMVP_F64 && cells64_considered(c)) return cell64_prepare(c);
+  return KMVP_OK;
+}
+
+// kmvp_cell_layout: the cell structures of the last product on the cell form, read back from what its kernel read -- the
+// stage headers of the source image (float64: the list of source cells), the target tiles' records and the slot of every
+// target.  Nothing is recomputed from the grid, so a model that takes the answer as data restates no rule of the lists.
+// Read-only: no buffer of the context is written.  A point that no tile holds keeps -1, one held twice gets -2.
+int cell_layout_read(kmvp_ctx* c, int64_t* info, double* sigma_b, int32_t* source_cell, int32_t* target_cell,
+                     double* source_centres, int64_t source_cap, double* target_centres, int64_t target_cap) {
+  if (!info) return fail(c, KMVP_E_INVALID, "kmvp_cell_layout: info is NULL");
+  const int layout = c->packed_layout;
+  const bool f64 = layout == LAYOUT_CELL64;
+  if (!c->have_points || c->cell_state != 1 || c->cell_ver != c->points_ver || c->packed_points_ver != c->points_ver ||
+      (layout != LAYOUT_CELL && layout != LAYOUT_CELLMM && !f64) || f64 != (c->dtype == KMVP_F64))
+    return fail(c, KMVP_E_INVALID, "kmvp_cell_layout: no product on the cell form has run on the current points");
+  const int64_t M = c->M, N = c->N;
+  const int tile = f64 ? CELL64_TILE : CELL_TILE;
+  const int* sperm_d = (const int*)c->cell_sperm.p;
+  std::vector<int> sperm((size_t)M);
+  HIP_TRY(c, hipMemcpyAsync(sperm.data(), sperm_d, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+
+  // ---- sources: cell of every source and the centres, in the order the kernels walk the cells
+  std::vector<int32_t> scell((size_t)M, -1);
+  std::vector<double> scen;
+  auto assign = [](std::vector<int32_t>& of, int64_t idx, int64_t n, int32_t id) {
+    if (idx < 0 || idx >= n) return false;
+    of[(size_t)idx] = of[(size_t)idx] == -1 ? id : -2;
+    return true;
+  };
+  bool sound = true;
+  if (f64) {
+    const int64_t cells = c->cell_m_tiles;  // (cell64_prepare: the number of source cells)
+    std::vector<int> runs((size_t)cells * 2);
+    std::vector<double> cen((size_t)cells * 4);
+    HIP_TRY(c, hipMemcpyAsync(runs.data(), c->cell_sgrp.p, runs.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(cen.data(), c->cell_scentre.p, cen.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int64_t sc = 0; sc < cells; ++sc) {
+      for (int a = 0; a < 3; ++a) scen.push_back(cen[(size_t)sc * 4 + a]);
+      for (int64_t p = runs[2 * sc]; p < (int64_t)runs[2 * sc] + runs[2 * sc + 1]; ++p)
+        sound = sound && p >= 0 && p < M && assign(scell, sperm[(size_t)p], M, (int32_t)sc);
+    }
+  } else {
+    const int stage_tiles = layout == LAYOUT_CELL ? CELL_STAGE_TILES : CMM_STAGE_TILES;
+    const int hdr_off = layout == LAYOUT_CELL ? CELL_HDR_OFF : CMM_HDR_OFF;
+    const int stage_bytes = layout == LAYOUT_CELL ? CELL_STAGE_BYTES : CMM_STAGE_BYTES;
+    const int64_t m_tiles = c->cell_m_tiles, m_stages = (m_tiles + stage_tiles - 1) / stage_tiles;
+    std::vector<int> grp((size_t)m_tiles * 3);
+    std::vector<float> hdr((size_t)m_stages * stage_tiles * 4);
+    HIP_TRY(c, hipMemcpyAsync(grp.data(), c->cell_sgrp.p, grp.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (m_stages > 0)
+      HIP_TRY(c, hipMemcpy2DAsync(hdr.data(), (size_t)stage_tiles * 16, (const unsigned char*)c->rec.p + hdr_off, (size_t)stage_bytes,
+                                  (size_t)stage_tiles * 16, (size_t)m_stages, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int key_s = -2;  // a new cell begins where the kernels see the key change
+    for (int64_t t = 0; t < m_tiles; ++t) {
+      const float* h = &hdr[(size_t)t * 4];
+      int key;
+      memcpy(&key, h + 3, sizeof key);
+      if (key != key_s) {
+        key_s = key;
+        for (int a = 0; a < 3; ++a) scen.push_back((double)h[a]);
+      }
+      const int32_t id = (int32_t)(scen.size() / 3) - 1;
+      const int64_t start = grp[(size_t)t], count = grp[(size_t)m_tiles + t];
+      sound = sound && key >= 0 && count >= 0 && count <= CELL_TILE && start >= 0 && start + count <= M;
+      for (int64_t k = 0; sound && k < count; ++k) sound = assign(scell, sperm[(size_t)(start + k)], M, id);
+    }
+  }
+  if (!sound) return fail(c, KMVP_E_DEVICE, "kmvp_cell_layout: the source tile list points outside the cloud");
+
+  // ---- targets: the tile of every target's slot, cells named by their stored centre
+  const int64_t n_tiles = f64 ? round_up(c->cell_n_tiles, WAVES_PER_BLOCK) : c->cell_n_tiles;
+  std::vector<int> slot((size_t)N);
+  std::vector<double> tmeta((size_t)n_tiles * 4);
+  HIP_TRY(c, hipMemcpyAsync(slot.data(), c->cell_slot.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (f64) {
+    HIP_TRY(c, hipMemcpyAsync(tmeta.data(), c->cell_tmeta.p, tmeta.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  } else {
+    std::vector<float> m32((size_t)n_tiles * 4);
+    HIP_TRY(c, hipMemcpyAsync(m32.data(), c->cell_tmeta.p, m32.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t q = 0; q < m32.size(); ++q) tmeta[q] = (q & 3) == 3 ? 0.0 : (double)m32[q];
+  }
+  std::vector<int32_t> tcell((size_t)N, -1);
+  std::vector<double> tcen;
+  std::map<std::array<double, 3>, int32_t> ids;
+  std::vector<char> taken((size_t)n_tiles * tile, 0);
+  for (int64_t i = 0; i < N; ++i) {
+    const int64_t sl = slot[(size_t)i];
+    if (sl < 0 || sl >= n_tiles * tile) continue;  // stays -1
+    const double* m = &tmeta[(size_t)(sl / tile) * 4];
+    const std::array<double, 3> key = {m[0], m[1], m[2]};
+    auto it = ids.find(key);
+    if (it == ids.end()) {
+      it = ids.emplace(key, (int32_t)(tcen.size() / 3)).first;
+      tcen.insert(tcen.end(), key.begin(), key.end());
+    }
+    tcell[(size_t)i] = taken[(size_t)sl] ? -2 : it->second;
+    taken[(size_t)sl] = 1;
+  }
+
+  const int64_t ns = (int64_t)scen.size() / 3, nt = (int64_t)tcen.size() / 3;
+  info[0] = ns;
+  info[1] = nt;
+  info[2] = c->cell_balanced ? 1 : 0;
+  info[3] = c->cell_tt;
+  info[4] = tile;
+  info[5] = layout == LAYOUT_CELL ? 0 : (layout == LAYOUT_CELLMM ? 1 : 2);
+  info[6] = f64 ? 0 : c->cell_n_main;
+  info[7] = f64 ? 0 : c->cell_n_rest;
+  if (sigma_b) {
+    float sc = 0.f;  // of the last column cellmm_kernel / cellmm16_kernel ran
+    if (layout == LAYOUT_CELLMM) {
+      HIP_TRY(c, hipMemcpyAsync(&sc, c->cell_scale.p, sizeof sc, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    *sigma_b = (double)sc;
+  }
+  if ((source_centres && source_cap < ns) || (target_centres && target_cap < nt))
+    return fail(c, KMVP_E_INVALID, "kmvp_cell_layout: room for fewer centres than there are cells (info[0], info[1])");
+  if (source_cell) memcpy(source_cell, scell.data(), (size_t)M * sizeof(int32_t));
+  if (target_cell) memcpy(target_cell, tcell.data(), (size_t)N * sizeof(int32_t));
+  if (source_centres) memcpy(source_centres, scen.data(), scen.size() * sizeof(double));
+  if (target_centres) memcpy(target_centres, tcen.data(), tcen.size() * sizeof(double));
   return KMVP_OK;
 }
 

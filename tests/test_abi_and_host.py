@@ -32,6 +32,25 @@ def test_library_exports_every_declared_symbol():
     assert lib.kmvp_abi_version() == 1
 
 
+def test_cell_layout_is_declared_bound_and_refuses_before_it_touches_the_library():
+    """kmvp_cell_layout (the cell model's read-only accessor): declared in include/kmvp.h, bound with its nine arguments, and
+    the typed wrapper refuses a closed context before the library is called; with no GPU there is no context to ask."""
+    assert "kmvp_cell_layout" in declared_symbols()
+    name, restype, argtypes = [s for s in _lib.SYMBOLS if s[0] == "kmvp_cell_layout"][0]
+    assert restype is ctypes.c_int and len(argtypes) == 9 and argtypes[6] is ctypes.c_int64 and argtypes[8] is ctypes.c_int64
+    header = open(os.path.join(ROOT, "include", "kmvp.h")).read()
+    decl = re.search(r"int kmvp_cell_layout\(([^)]*)\)", header).group(1)
+    assert len(decl.split(",")) == 9 and "int64_t* info" in decl and "double* sigma_b" in decl
+    c = _lib.Context.__new__(_lib.Context)  # never bound to a kmvp_ctx
+    c._ctx = None
+    c.M, c.N = 5, 5
+    with pytest.raises(ValueError, match="closed"):
+        _lib.Context.cell_layout(c)
+    lib = _lib.load()
+    info = (ctypes.c_int64 * 8)()
+    assert lib.kmvp_cell_layout(None, info, None, None, None, None, 0, None, 0) != 0  # a NULL context is an error, not a crash
+
+
 def test_library_is_the_hip_build():
     blob = open(_lib.LIB_PATH, "rb").read()
     assert b"gfx950" in blob, "libkmvp.so carries no gfx950 code object"
