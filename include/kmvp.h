@@ -643,6 +643,59 @@ int kmvp_matern52_lanczos_quadrature_precond(kmvp_ctx* ctx, const double* g, con
                                              double* x_or_null, double* pz_or_null, double* alpha_or_null,
                                              double* beta_or_null);
 
+/* Top-k eigenpairs (an extension: kernel PCA, spectral embedding, the largest eigenvalue for a condition estimate, the
+ * exact top-k a low-rank approximation is judged against -- without the N x N matrix).  The k algebraically largest
+ * eigenpairs of the symmetric operator A on the cloud given to kmvp_set_points (x_or_null == NULL, as for the solvers):
+ *   KMVP_EIG_KERNEL      A = K + ridge I + diag(d) with the diagonal of kmvp_set_solver_diagonal when one is set, else A = K
+ *   KMVP_EIG_CENTERED    A = H K H, H = I - 1 1'/N: kernel PCA
+ *   KMVP_EIG_NORMALIZED  A = S K S, S = diag(q^-1/2), q = K 1 computed here by one density product at the start: spectral
+ *                        embedding; the largest eigenvalue is 1 with eigenvector ~ q^1/2.  degree_or_null (N doubles)
+ *                        receives q (untouched for the other operators).
+ * A solver diagonal set together with op != KMVP_EIG_KERNEL is KMVP_E_INVALID.
+ * The algorithm is the Lanczos process with FULL reorthogonalisation and no restart, held exactly as follows.
+ *   v_1 = v0 / |v0| (N doubles; for the centred operator v0 is centred first).  The library draws nothing.
+ *   j = 1, 2, ...:  w = A v_j      (the operator rounds its argument to the working precision exactly as the solvers do --
+ *                                   for the centred and the normalised operator that argument is H v_j and S v_j;
+ *                                   everything else is float64)
+ *                   h = V_j' w,  w <- w - V_j h;   h' = V_j' w,  w <- w - V_j h'      (classical Gram-Schmidt, twice)
+ *                   alpha_j = h_j + h'_j,   beta_j = |w|_2,   v_{j+1} = w / beta_j
+ *   Breakdown: beta_j <= 1e-13 max_{i<=j} |alpha_i| -- v_{j+1} is not formed and the process ends at step j: the Krylov
+ *   space of v0 is invariant to working accuracy.
+ * The host looks at the process at fixed steps only -- every j >= k with j mod 8 == 0, at breakdown and at j == maxit --
+ * so nothing depends on when it happens to look.  At a look it reads the history (alpha, beta), solves the j x j
+ * tridiagonal (csrc/kmvp_tridiag.hpp), takes the k largest Ritz values theta_1 >= ... >= theta_k and the estimates
+ * beta_j |s_{j,i}| from the last components of their eigenvectors, and stops when every estimate is <= tol |theta_1| (or
+ * at breakdown, or at maxit).  Then X = V_j S[:, top k] is formed on the device and one more k-column application of A
+ * gives the true residuals resid[i] = |A x_i - theta_i x_i|_2 / (|theta_1| |x_i|_2).  The verdict is on these, as for the
+ * solvers: KMVP_OK if every one is finite and <= 1.5 tol, otherwise KMVP_E_NOT_CONVERGED with everything written (also for
+ * a non-finite operator, e.g. a NaN coordinate: the outputs are then non-finite; and for a breakdown before step k).
+ *   eigenvalues (k): the Ritz values, descending.   eigenvectors (N, k) float64 row-major: unit norm, the sign of each
+ *   fixed so that its component of largest magnitude is positive (a tie goes to the smallest index).   resid (k).
+ *   *steps: the steps taken.   alpha_or_null, beta_or_null (maxit each): row j - 1 holds step j; rows >= *steps unspecified.
+ * Inside a burst of steps nothing crosses to the host: a device kernel forms alpha_j and beta_j, appends them to the
+ * history and sets the stop word; the normalisation reads beta_j from device memory.  There is NO graph replay of the
+ * burst (the reorthogonalisation grows with every step, so no two steps launch the same work).  Fixed summation orders,
+ * no atomics: bitwise reproducible run to run.  With a communicator attached the operator is sharded and the basis
+ * replicated, as for the quadrature: every rank returns the same bits.  The context is left as after a solve (no signal);
+ * kmvp_last_kernel_ms and kmvp_last_total_ms both cover the whole call.  kmvp_set_solver_preconditioner is ignored.
+ * KMVP_E_INVALID: no points set, targets != sources, k < 1 or k > N, maxit < k or maxit > min(N, 512), tol not > 0, a NULL
+ * v0, eigenvalues, eigenvectors, resid or steps, a v0 that is non-finite or zero (for the centred operator also: constant,
+ * |H v0| <= 1e-13 |v0|).  KMVP_E_UNSUPPORTED: a bfloat16 context; batches set (kmvp_set_batches).  KMVP_E_NOMEM: the basis
+ * of (maxit + 1) N doubles does not fit.  There is no inverse-distance entry. */
+enum kmvp_eig_operator { KMVP_EIG_KERNEL = 0, KMVP_EIG_CENTERED = 1, KMVP_EIG_NORMALIZED = 2 };
+int kmvp_gaussian_eigsh(kmvp_ctx* ctx, int k, int op, const double* v0, double tol, int maxit, double* eigenvalues,
+                        double* eigenvectors, double* resid, int* steps, double* alpha_or_null, double* beta_or_null,
+                        double* degree_or_null);
+int kmvp_absexp_eigsh(kmvp_ctx* ctx, int k, int op, const double* v0, double tol, int maxit, double* eigenvalues,
+                      double* eigenvectors, double* resid, int* steps, double* alpha_or_null, double* beta_or_null,
+                      double* degree_or_null);
+int kmvp_matern32_eigsh(kmvp_ctx* ctx, int k, int op, const double* v0, double tol, int maxit, double* eigenvalues,
+                        double* eigenvectors, double* resid, int* steps, double* alpha_or_null, double* beta_or_null,
+                        double* degree_or_null);
+int kmvp_matern52_eigsh(kmvp_ctx* ctx, int k, int op, const double* v0, double tol, int maxit, double* eigenvalues,
+                        double* eigenvectors, double* resid, int* steps, double* alpha_or_null, double* beta_or_null,
+                        double* degree_or_null);
+
 /* Source sharding over the GPUs of one node, one process per GPU:
  * rank 0 calls kmvp_comm_get_unique_id and hands the 128 bytes to every rank
  * out of band; every rank then calls kmvp_comm_init.  world == 1 is allowed. */

@@ -75,6 +75,10 @@ SYMBOLS = [
     ("kmvp_absexp_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
     ("kmvp_matern32_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
     ("kmvp_matern52_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
+    ("kmvp_gaussian_eigsh", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int] + [_c.c_void_p] * 7),
+    ("kmvp_absexp_eigsh", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int] + [_c.c_void_p] * 7),
+    ("kmvp_matern32_eigsh", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int] + [_c.c_void_p] * 7),
+    ("kmvp_matern52_eigsh", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int] + [_c.c_void_p] * 7),
     ("kmvp_gaussian_lanczos_quadrature_precond", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 9),
     ("kmvp_absexp_lanczos_quadrature_precond", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 9),
     ("kmvp_matern32_lanczos_quadrature_precond", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 9),
@@ -107,6 +111,9 @@ HOST_ALLREDUCE_FN = _c.CFUNCTYPE(_c.c_int, _c.c_void_p, _c.POINTER(_c.c_double),
 OP_SUM, OP_MIN = 0, 1
 # kernel codes of kmvp_fit (include/kmvp.h)
 FIT_CODES = {"gaussian": 0, "absolute-exponential": 1, "inverse-distance": 2, "matern-3/2": 3, "matern-5/2": 4}
+
+# enum kmvp_eig_operator (include/kmvp.h)
+EIG_OPERATORS = {"kernel": 0, "centered": 1, "normalized": 2}
 
 _lib = None
 
@@ -376,6 +383,50 @@ class Context:
         out = {"logquad": logquad, "invquad": invquad, "steps": steps.astype(np.int64), "converged": rc == 0}
         if want_x:
             out["x"] = x
+        if want_coefficients:
+            out["alpha"], out["beta"] = alpha, beta
+        return out
+
+    def eigsh(self, kernel, k, op, v0, tol, maxit, want_coefficients=False):
+        """The k algebraically largest eigenpairs of the kernel matrix (op "kernel"), its centred form ("centered") or its
+        degree-normalised form ("normalized") by Lanczos with full reorthogonalisation from the start vector v0 (N
+        float64): include/kmvp.h kmvp_<kernel>_eigsh.  Returns a dict: eigenvalues (k), eigenvectors (N, k), resid (k),
+        steps, converged, degree (N; "normalized" only) and alpha, beta (maxit) when asked for; raises on every status but
+        OK and NOT_CONVERGED."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_eigsh,
+            "absolute-exponential": self._lib.kmvp_absexp_eigsh,
+            "matern-3/2": self._lib.kmvp_matern32_eigsh,
+            "matern-5/2": self._lib.kmvp_matern52_eigsh,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no eigen-solver for kernel {kernel}")
+        if op not in EIG_OPERATORS:
+            raise ValueError(f"operator {op!r}: expected one of {sorted(EIG_OPERATORS)}")
+        N = int(getattr(self, "N", 0))
+        k, maxit = int(k), int(maxit)
+        if v0 is not None:
+            # the library reads N doubles from the pointer: anything else must never reach it
+            v0 = np.ascontiguousarray(v0, dtype=np.float64)
+            if v0.shape != (N,):
+                raise ValueError(f"v0 has shape {v0.shape}, expected ({N},): one value per point")
+        # the library writes k, N * k and maxit elements: the arrays are sized here, from the points it was given
+        eigenvalues = np.full(max(k, 0), np.nan)
+        eigenvectors = np.full((N, max(k, 0)), np.nan)
+        resid = np.full(max(k, 0), np.nan)
+        steps = ctypes.c_int(0)
+        alpha = np.full(max(maxit, 0), np.nan) if want_coefficients else None
+        beta = np.full(max(maxit, 0), np.nan) if want_coefficients else None
+        degree = np.full(N, np.nan) if op == "normalized" else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = entry(self._ctx, k, EIG_OPERATORS[op], ptr(v0), float(tol), maxit, eigenvalues.ctypes.data,
+                   eigenvectors.ctypes.data, resid.ctypes.data, ctypes.addressof(steps), ptr(alpha), ptr(beta), ptr(degree))
+        if rc not in (0, 6):
+            self._check(rc)
+        out = {"eigenvalues": eigenvalues, "eigenvectors": eigenvectors, "resid": resid, "steps": steps.value,
+               "converged": rc == 0}
+        if degree is not None:
+            out["degree"] = degree
         if want_coefficients:
             out["alpha"], out["beta"] = alpha, beta
         return out

@@ -1355,6 +1355,203 @@ class MI355XKMeans:
             pass
 
 
+SPECTRAL_KERNELS = ("gaussian", "absolute-exponential", "matern-3/2", "matern-5/2")
+SPECTRAL_OPERATORS = ("kernel", "centered", "normalized")
+SPECTRAL_MAX_STEPS = 512  # csrc/kmvp_eigsh.hip EIG_MAX_STEPS: there is no restart
+
+
+class MI355XSpectral:
+    """The n_components largest eigenpairs of the kernel matrix on one MI355X, by a device-resident Lanczos process with
+    full reorthogonalisation on the on-the-fly product (include/kmvp.h kmvp_<kernel>_eigsh).  An extension: the
+    reference's plugin API has no such role, so the class is not registered in algos.yaml.
+
+        operator="kernel"      A = K (+ ridge I, or + diag(ridge) with one value per point)
+        operator="centered"    A = H K H, H = I - 1 1'/N: kernel PCA (sklearn.decomposition.KernelPCA)
+        operator="normalized"  A = D^-1/2 K D^-1/2, D = diag(K 1): spectral embedding (Ng, Jordan and Weiss)
+
+    Call order: prepare_data, fit, query, then get_eigenvalues / get_eigenvectors / get_residuals / get_degree /
+    get_embedding / transform / get_additional, done.  ``tol`` bounds |A x - theta x| / (theta_1 |x|) of every pair
+    (default: 1e-10 in float64, 1e-4 in float32 and float16); ``maxit`` caps the Lanczos steps (default and most:
+    min(N, 512) -- there is no restart).  The start vector is a normal draw from ``seed`` on the host unless query(v0=)
+    passes one: the library itself draws nothing.  Not converged is a result (get_additional()["converged"]); every
+    other failure raises.  A single start vector finds one copy of a multiple eigenvalue."""
+
+    def __init__(self, *, kernel, dimension, precision=np.float64, n_components, operator="kernel", tol=None, maxit=None,
+                 seed=0, ridge=None, device=0):
+        if kernel not in SPECTRAL_KERNELS:
+            raise NotImplementedError(f"MI355XSpectral doesn't support kernel {kernel}.")
+        if operator not in SPECTRAL_OPERATORS:
+            raise ValueError(f"operator must be one of {SPECTRAL_OPERATORS}, not {operator!r}")
+        if int(n_components) < 1:
+            raise ValueError(f"n_components must be >= 1, not {n_components!r}")
+        self._dtype_code, self._host_dtype = _lib.dtype_code(precision)
+        if self._dtype_code == _lib.KMVP_BF16:
+            raise NotImplementedError("MI355XSpectral needs float16, float32 or float64")
+        if ridge is not None and operator != "kernel":
+            raise ValueError("ridge goes with operator='kernel' only")
+        if ridge is not None:
+            ridge = np.array(ridge, dtype=np.float64)
+            if ridge.ndim > 1 or not np.isfinite(ridge).all():
+                raise ValueError("ridge must be a finite number or a one-dimensional array of one value per point")
+        self.kernel, self.dimension, self.precision = kernel, int(dimension), precision
+        self.n_components, self.operator = int(n_components), operator
+        self._round = _lib.input_rounding(precision)  # float16: rounded points, float32 arithmetic
+        self.tol = float(tol) if tol is not None else (1e-10 if self._dtype_code == _lib.KMVP_F64 else 1e-4)
+        self.maxit = None if maxit is None else int(maxit)
+        self.seed, self.ridge, self.device = seed, ridge, device
+        self._ctx = self._transform_ctx = None
+        self.eigenvalues = self.eigenvectors = self.residuals = self.degree = None
+        self.steps, self.converged = 0, False
+        self.name = f"MI355XSpectral({_precision_name(precision)}, {kernel}, {operator}, n_components={self.n_components})"
+
+    def _as_device_points(self, points, what):
+        p = np.asarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != self.dimension:
+            raise ValueError(f"{what} has shape {p.shape}, expected (N, {self.dimension})")
+        if self._round is not None:
+            p = p.astype(self._round)
+        return np.ascontiguousarray(p, dtype=self._host_dtype)
+
+    # -- untimed -------------------------------------------------------------------
+    def prepare_data(self, *, points):
+        x = self._as_device_points(points, "points")
+        self.N, self.D = x.shape
+        if self.n_components > self.N:
+            raise ValueError(f"n_components = {self.n_components} for {self.N} points")
+        if self.ridge is not None and self.ridge.ndim == 1 and self.ridge.size != self.N:
+            raise ValueError(f"ridge has {self.ridge.size} values, the point cloud has {self.N} points")
+        self._x = x  # the points as the device holds them
+        if self._ctx is None:
+            self._ctx = _lib.Context(self.device)
+        self._ctx.set_points(x, None, self._dtype_code)
+        if self.ridge is not None:  # (kmvp_set_points cleared the library's diagonal)
+            if self.ridge.ndim == 1:
+                self._ctx.set_solver_diagonal(np.ascontiguousarray(self.ridge), 0.0)
+            else:
+                self._ctx.set_solver_diagonal(None, float(self.ridge))
+        self.eigenvalues = self.eigenvectors = self.residuals = self.degree = None
+
+    # -- timed ---------------------------------------------------------------------
+    def fit(self):
+        """Whatever the product builds from the points alone (kmvp_fit)."""
+        if self._ctx is None:
+            raise RuntimeError("MI355XSpectral.fit() needs prepare_data() first")
+        self._ctx.fit(self.kernel)
+
+    def set_query_arguments(self, tol=None, maxit=None):
+        if tol is not None:
+            self.tol = float(tol)
+        if maxit is not None:
+            self.maxit = int(maxit)
+
+    def query(self, v0=None):
+        """Runs the Lanczos process from ``v0`` (N values; default: a standard normal draw from ``seed``).  Synchronous."""
+        if self._ctx is None:
+            raise RuntimeError("MI355XSpectral.query() needs prepare_data() first")
+        if v0 is None:
+            v0 = np.random.RandomState(self.seed).standard_normal(self.N)
+        maxit = min(self.N, SPECTRAL_MAX_STEPS) if self.maxit is None else self.maxit
+        r = self._ctx.eigsh(self.kernel, self.n_components, self.operator, v0, self.tol, maxit)
+        self.eigenvalues, self.eigenvectors, self.residuals = r["eigenvalues"], r["eigenvectors"], r["resid"]
+        self.steps, self.converged = r["steps"], r["converged"]
+        self._eigsh_ms = self._ctx.last_total_ms
+        self.degree = r.get("degree")
+        if self.operator == "centered":
+            # the column sums of K, for transform(): one density product on the same context
+            self._ctx.set_signal(None)
+            self._ctx.run(self.kernel, False)
+            self.degree = self._ctx.get_result(self.N, 1)[:, 0]
+
+    # -- results -------------------------------------------------------------------
+    def _need_solution(self, method):
+        if self.eigenvalues is None:
+            raise RuntimeError(f"MI355XSpectral.{method}: no solution yet -- call query() after prepare_data() first")
+
+    def get_eigenvalues(self):
+        """(n_components,) float64, descending: the Ritz values."""
+        self._need_solution("get_eigenvalues")
+        return self.eigenvalues
+
+    def get_eigenvectors(self):
+        """(N, n_components) float64: unit columns, each with its component of largest magnitude positive."""
+        self._need_solution("get_eigenvectors")
+        return self.eigenvectors
+
+    def get_residuals(self):
+        """(n_components,) float64: |A x_i - theta_i x_i| / (theta_1 |x_i|) from one more application of A."""
+        self._need_solution("get_residuals")
+        return self.residuals
+
+    def get_degree(self):
+        """(N,) float64: the row sums K 1 (operator "normalized": what the library scaled by; "centered": what
+        transform() centres with); None for operator "kernel"."""
+        self._need_solution("get_degree")
+        return self.degree
+
+    def get_embedding(self):
+        """(N, n_components) float64.  "kernel" and "centered": X sqrt(max(theta, 0)), the convention of
+        sklearn.decomposition.KernelPCA.fit_transform.  "normalized": the rows of X scaled to unit length (Ng, Jordan and
+        Weiss); a row of zeros stays as it is."""
+        self._need_solution("get_embedding")
+        X = self.eigenvectors
+        if self.operator != "normalized":
+            return X * np.sqrt(np.maximum(self.eigenvalues, 0.0))
+        norms = np.sqrt(np.sum(X * X, axis=1, keepdims=True))
+        return X / np.where(norms > 0, norms, 1.0)
+
+    def transform(self, points):
+        """(M, n_components) float64: the embedding of new points, K(x, Y) (X theta^-1/2) with the library's own product
+        -- for "centered" with K(x, Y) centred as sklearn's KernelCenterer does it, from the row means K(x, Y) 1 / N of
+        the new points, the stored column means of the training matrix and its total mean.  Columns with theta <= 0 are
+        zero.  Not defined for "normalized"."""
+        self._need_solution("transform")
+        if self.operator == "normalized":
+            raise NotImplementedError("MI355XSpectral.transform is for operator 'kernel' and 'centered': the normalised "
+                                      "embedding has no out-of-sample form here")
+        x = self._as_device_points(points, "points")
+        theta = self.eigenvalues
+        scale = np.where(theta > 0, 1.0 / np.sqrt(np.where(theta > 0, theta, 1.0)), 0.0)
+        A = self.eigenvectors * scale  # (N, k)
+        signal = np.concatenate([A, np.ones((self.N, 1))], axis=1) if self.operator == "centered" else A
+        if self._transform_ctx is None:  # a context of its own: the solver's keeps the square problem
+            self._transform_ctx = _lib.Context(self.device)
+        self._transform_ctx.set_points(self._x, x, self._dtype_code)
+        self._transform_ctx.set_signal(np.ascontiguousarray(signal, dtype=self._host_dtype))
+        self._transform_ctx.run(self.kernel, False)
+        out = self._transform_ctx.get_result(x.shape[0], signal.shape[1])
+        if self.operator != "centered":
+            return out
+        k = self.n_components
+        col_mean = self.degree / self.N                  # (1/N) sum_i K(y_i, y_j)
+        total = float(np.sum(self.degree)) / self.N ** 2
+        row_mean = out[:, k:] / self.N                   # (1/N) sum_j K(x, y_j)
+        ones_A = np.sum(A, axis=0)                       # 1' A (zero up to rounding: the eigenvectors are centred)
+        return out[:, :k] - row_mean * ones_A - col_mean @ A + total * ones_A
+
+    def get_memory_usage(self):
+        """Device kB held by the contexts."""
+        return sum(ctx.device_bytes for ctx in (self._ctx, self._transform_ctx) if ctx is not None) / 1024
+
+    def get_additional(self):
+        extra = {"steps": self.steps, "converged": bool(self.converged), "tol": self.tol,
+                 "worst_residual": float("nan") if self.residuals is None else float(np.max(self.residuals))}
+        if self._ctx is not None:
+            extra.update(device_total_ms=getattr(self, "_eigsh_ms", 0.0), device_bytes=self._ctx.device_bytes)
+        return extra
+
+    def done(self):
+        for ctx in (self._ctx, self._transform_ctx):
+            if ctx is not None:
+                ctx.close()
+        self._ctx = self._transform_ctx = None
+
+    def __del__(self):
+        try:
+            self.done()
+        except Exception:
+            pass
+
+
 MEANSHIFT_MAX_D = NEAREST_MAX_D
 
 

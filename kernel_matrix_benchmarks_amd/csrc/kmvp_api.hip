@@ -286,7 +286,18 @@ int kmvp_matern52_lanczos_quadrature(kmvp_ctx* c, const void* z, int P, double r
   return cg_lanczos(c, K_MATERN52, z, P, rtol, maxit, logquad, invquad, steps, x, alpha, beta);
 }
 
-#define KMVP_LANCZOS_PRECOND_ENTRY(NAME, K)                                                                                  \
+#define KMVP_EIGSH_ENTRY(NAME, K)                                                                                          \
+  int kmvp_##NAME##_eigsh(kmvp_ctx* c, int k, int op, const double* v0, double tol, int maxit, double* eigenvalues,        \
+                          double* eigenvectors, double* resid, int* steps, double* alpha, double* beta, double* degree) { \
+    KMVP_NOT_BATCHED(c, "the eigen-solver");                                                                              \
+    return eigsh_solve(c, K, k, op, v0, tol, maxit, eigenvalues, eigenvectors, resid, steps, alpha, beta, degree);        \
+  }
+KMVP_EIGSH_ENTRY(gaussian, K_GAUSSIAN)
+KMVP_EIGSH_ENTRY(absexp, K_ABSEXP)
+KMVP_EIGSH_ENTRY(matern32, K_MATERN32)
+KMVP_EIGSH_ENTRY(matern52, K_MATERN52)
+
+#define KMVP_LANCZOS_PRECOND_ENTRY(NAME, K)                                                                                 \
   int kmvp_##NAME##_lanczos_quadrature_precond(kmvp_ctx* c, const double* g, const double* h, int P, double rtol, int maxit,  \
                                                double* logdet_p, double* logquad, double* invquad, double* wnorm2,           \
                                                int* steps, double* x, double* pz, double* alpha, double* beta) {             \

@@ -3,6 +3,7 @@
 //   kmvp_api.hip      the extern "C" surface of include/kmvp.h
 //   kmvp_product.hip  layouts, launch geometry, the pair-loop paths and the policy that picks one
 //   kmvp_solvers.hip  conjugate gradients, MINRES and the Lanczos quadrature on the product
+//   kmvp_eigsh.hip    the top-k eigenpairs by Lanczos with full reorthogonalisation on the same operator
 //   kmvp_sinkhorn.hip the Sinkhorn iteration of entropic optimal transport on the log-sum-exp
 //   kmvp_kmeans.hip   Lloyd's k-means on the arg-K-min at K = 1
 //   kmvp_meanshift.hip Gaussian mean-shift on the gradient of the log-sum-exp
@@ -313,6 +314,31 @@ int cg_lanczos(kmvp_ctx* c, int kernel, const void* z_host, int P, double rtol, 
 int cg_lanczos_precond(kmvp_ctx* c, int kernel, const double* g_host, const double* h_host, int P, double rtol, int maxit,
                        double* logdet_p, double* logquad, double* invquad, double* wnorm2, int* steps, double* x_out,
                        double* pz_out, double* alpha_out, double* beta_out);
+// One solve's scratch block: `nvec` Krylov vectors of N x E doubles, the dot products' partial sums, then
+// the device-resident iteration's state, with its stop word at `stop` and the iteration count after it, then `extra`
+// doubles of the solver's own (cg_lanczos: the coefficient history).
+struct Krylov {
+  int64_t m = 0;  // length of the Krylov vectors: all points
+  int E = 0;
+  size_t n = 0;  // m * E
+  size_t stop = 0;
+  double *vecs = nullptr, *partial = nullptr, *state = nullptr;
+  double* vec(int i) const { return vecs + (size_t)i * n; }
+};
+// However a solve ends, the product is synchronous again and no signal is left behind: b_raw held the
+// right-hand side and the Krylov vectors, not what kmvp_set_signal uploaded.
+struct SolveGuard {
+  kmvp_ctx* c;
+  ~SolveGuard() { c->async_product = false; c->have_signal = false; }
+};
+// What the eigen-solver (kmvp_eigsh.hip) shares with the solvers: the shape check (targets == sources, sharded or not) and
+// the operator, K applied to the device-resident (N, k.E) float64 block v, the result in c->out (of `k` it reads E and n).
+int solver_shape(kmvp_ctx* c);
+int cg_apply(kmvp_ctx* c, int kernel, const double* v, const Krylov& k);
+
+// kmvp_eigsh.hip: kmvp_<kernel>_eigsh, the device-resident Lanczos process with full reorthogonalisation
+int eigsh_solve(kmvp_ctx* c, int kernel, int k, int op, const double* v0, double tol, int maxit, double* eigenvalues,
+                double* eigenvectors, double* resid, int* steps, double* alpha_out, double* beta_out, double* degree_out);
 
 // kmvp_sinkhorn.hip: kmvp_<kernel>_sinkhorn, the device-resident Sinkhorn iteration on lowd_lse_kernel
 int sinkhorn_solve(kmvp_ctx* c, int kernel, const double* log_a, const double* log_b, double tol, int maxit, double* u,

@@ -21,7 +21,7 @@ constexpr int CG_BLOCKS = 256;
 // The system matrix is K(y, y) on ALL points.  Single GPU: x == y (x_or_null = NULL).  Sharded:
 // every rank holds all points as targets and its slice of them as sources
 // (same_points_global, N == M_total), and a communicator is attached.
-static int solver_shape(kmvp_ctx* c) {
+int solver_shape(kmvp_ctx* c) {
   if (c->same_points && c->world == 1) return KMVP_OK;
   if (c->world > 1 && !c->exchanges()) return fail(c, KMVP_E_INVALID, "sharded solver without kmvp_comm_init");
   const bool sharded_square = c->opt_same_global && c->N == c->m_total && c->j_offset + c->M <= c->m_total &&
@@ -179,17 +179,7 @@ __global__ void cg_update_p_kernel(double* __restrict__ p, const double* __restr
 // ------------------------------------------------------------------------------------
 // host side shared by both solvers
 
-// One solve's scratch block: `nvec` Krylov vectors of N x E doubles, the dot products' partial sums, then
-// the device-resident iteration's state, with its stop word at `stop` and the iteration count after it, then `extra`
-// doubles of the solver's own (cg_lanczos: the coefficient history).
-struct Krylov {
-  int64_t m = 0;  // length of the Krylov vectors: all points
-  int E = 0;
-  size_t n = 0;  // m * E
-  size_t stop = 0;
-  double *vecs = nullptr, *partial = nullptr, *state = nullptr;
-  double* vec(int i) const { return vecs + (size_t)i * n; }
-};
+// (Krylov, the solve's scratch block, and SolveGuard: kmvp_ctx.hpp, shared with the eigen-solver.)
 
 // The checks both solvers make, the device, and the scratch layout.
 static int solver_begin(kmvp_ctx* c, const void* a_host, int E, double rtol, int maxit, const double* out_b, int nvec,
@@ -213,13 +203,6 @@ static int solver_begin(kmvp_ctx* c, const void* a_host, int E, double rtol, int
   return KMVP_OK;
 }
 
-// However a solve ends, the product is synchronous again and no signal is left behind: b_raw held the
-// right-hand side and the Krylov vectors, not what kmvp_set_signal uploaded.
-struct SolveGuard {
-  kmvp_ctx* c;
-  ~SolveGuard() { c->async_product = false; c->have_signal = false; }
-};
-
 // out = sum over the CG_BLOCKS partials of u . v per column
 static int cg_dots(kmvp_ctx* c, const double* u, const double* v, const Krylov& k, std::vector<double>& out) {
   const int E = k.E;
@@ -241,7 +224,7 @@ static int cg_dots(kmvp_ctx* c, const double* u, const double* v, const Krylov& 
 // and run_product() ends with the all-reduce of the (N,E) sums, so every rank continues with
 // bitwise the same vectors.  The solver's diagonal is NOT applied here: the first consumer of c->out adds it, once, on
 // the full vector.
-static int cg_apply(kmvp_ctx* c, int kernel, const double* v, const Krylov& k) {
+int cg_apply(kmvp_ctx* c, int kernel, const double* v, const Krylov& k) {
   const int64_t n = c->M * k.E;  // this rank's sources
   v += (size_t)c->j_offset * k.E;
   int rc = ensure(c, c->b_raw, k.n * elem_size(c->dtype));  // also holds the right-hand side
