@@ -160,6 +160,14 @@ int kmvp_matern52_norm(kmvp_ctx* ctx);
  * The targets are independent variables, also with same_points: this is the derivative in the first argument (a
  * caller who wants the total derivative of a symmetric sum adds the transpose term).  Density estimation (b == NULL)
  * means b = 1, E = 1.  Row normalisation is not differentiated.
+ * Non-finite inputs, the same rules for kmvp_<kernel>_dscale below:
+ *  - a NaN target coordinate makes that row NaN in every component, and touches no other row;
+ *  - a pair whose squared distance overflows the working precision although x - y is finite contributes exactly 0;
+ *  - a SOURCE coordinate that is NaN or +-inf is not screened (it would cost every pair a select): the components of
+ *    that axis, G[:, :, d], are non-finite in EVERY row, wherever in the array the source sits.  The other components
+ *    either hold the sum over the other sources or are non-finite too (float32 Gaussian, exp(-r) and 1/r on a NaN).
+ *    Filter such sources before kmvp_set_points; the products, by contrast, count a source at infinity as 0;
+ *  - a NaN signal entry b[j, e] makes column e non-finite in every row and leaves the other columns alone.
  * Synchronous like the products; the result is read with kmvp_get_result as (N, E D) float64 row-major, d fastest.
  * float32 and float64 contexts, D <= 8, E <= 4 (lowd_grad_kernel, difference form: as accurate far from the origin as
  * near it); KMVP_E_UNSUPPORTED beyond that and for bfloat16 contexts.  Honours "segments", "chunk" and "partial_shard";
@@ -184,9 +192,10 @@ int kmvp_matern52_grad(kmvp_ctx* ctx);
  *   kmvp_matern52_dscale   h_d = (5/3) (1 + t) e^-t D_d^2,  t = sqrt(5) r
  * There is no inverse-distance entry: that kernel is not a covariance, and its derivative is the kernel itself.
  * A pair whose squared distance overflows the working precision contributes exactly 0 as long as x - y itself is
- * finite.  A NaN target coordinate makes that row of H NaN (the Gaussian: every component; the others: at least the
- * components of the NaN axes) and no other row.  Density estimation (b == NULL) means b = 1, E = 1.  Row normalisation
- * is not differentiated.
+ * finite.  A NaN target coordinate makes that row of H NaN in every component, and no other row; a NaN or +-inf source
+ * coordinate makes H[:, :, d] of its axis non-finite in every row; a NaN signal entry its column: the rules stated for
+ * kmvp_<kernel>_grad above.  Density estimation (b == NULL) means b = 1, E = 1.  Row normalisation is not
+ * differentiated.
  * Synchronous like the products; the result is read with kmvp_get_result as (N, E D) float64 row-major, d fastest.
  * float32 and float64 contexts, D <= 8, E <= 4 (lowd_dscale_kernel, difference form on the product's own packed
  * layouts: as accurate far from the origin as near it); KMVP_E_UNSUPPORTED beyond that and for bfloat16 contexts.

@@ -130,6 +130,7 @@ LowdArgs<real> lowd_geometry(int64_t N, int64_t M, int opt_segments, int opt_chu
   a.chunk = (int)round_up(opt_chunk > 8 ? opt_chunk : 8, LOWD_BATCH);
   a.j_offset = j_offset;
   a.m_total = m_total;
+  a.m = M;
   return a;
 }
 

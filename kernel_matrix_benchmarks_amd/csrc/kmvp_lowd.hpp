@@ -61,6 +61,7 @@ struct LowdArgs {
   int chunk;         // sources per fp32 chunk
   int64_t j_offset;  // global index of source 0 (sharding)
   int64_t m_total;   // global number of sources (inverse-distance zero pattern)
+  int64_t m;         // sources: the records from m on are pad records (lowd_grad_kernel, lowd_dscale_kernel)
 };
 
 __device__ __forceinline__ float kexp2(float v) { return __builtin_amdgcn_exp2f(v); }

@@ -22,10 +22,14 @@
 // Pairs that must contribute exactly 0:
 //  * pad records (y = +inf: x - y = -inf is not finite, so both factors would fail).  They only exist among the
 //    last 2 U records of the array: only those batches pay for the selects that zero w AND x - y (GUARD).  The select
-//    is on s == inf, not on s < inf as the gradient's, so that a NaN target stays NaN in a guarded batch too;
+//    is on the record's index (j >= M), as the gradient's: a source of the caller's is never taken for a pad record;
 //  * exp(-r) at s = 0: the true limit (x_d - y_d)^2 / r -> 0, no convention; but rsq(0) = inf, so the select of
 //    grad_interact (w for the positive NORMAL s only) is needed all the same.  It also covers s = inf, where
 //    r = s rsq(s) = inf * 0 is NaN.
+//
+// Non-finite inputs: the gradient's rules (kmvp_lowd_grad.hpp, include/kmvp.h) -- a NaN target coordinate makes its row
+// NaN in every component (nan_target, when the row is written); a NaN or +-inf source coordinate is not screened and
+// makes the components of its axis non-finite in every row, wherever in the array the source sits.
 #pragma once
 #include "kmvp_lowd_grad.hpp"
 
@@ -34,7 +38,8 @@ namespace kmvp {
 // One (target, source) interaction.
 template <int KERNEL, int D, int E, int SIG, bool GUARD, typename real>
 __device__ __forceinline__ void dscale_interact(const real (&x)[D], real (&acc)[GradLayout<D, E, SIG>::NC],
-                                                const real* __restrict__ r, const double* __restrict__ tab) {
+                                                const real* __restrict__ r, int64_t j_local, int64_t m,
+                                                const double* __restrict__ tab) {
   static_assert(KERNEL != K_INVDIST, "no length-scale derivative for 1/r");
   real df[D];
   df[0] = x[0] - r[0];
@@ -48,7 +53,7 @@ __device__ __forceinline__ void dscale_interact(const real (&x)[D], real (&acc)[
   if constexpr (KERNEL == K_ABSEXP) w = positive_normal(s) ? w : (real)0;
   if constexpr (GUARD) {
     // a pad record: w = 0 is not enough, 0 * (x - y) = 0 * -inf is NaN -- the differences go to 0 with it
-    const bool pad = s == (real)INFINITY;
+    const bool pad = j_local >= m;
     w = pad ? (real)0 : w;
 #pragma unroll
     for (int d = 0; d < D; ++d) df[d] = pad ? (real)0 : df[d];
@@ -94,8 +99,12 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_dscale_kernel(const LowdAr
   const int64_t i = i0 + lane;                                     // < n_pad by construction; pad targets are 0
 
   real x[D];
+  bool x_nan = false;  // nan_target (kmvp_lowd.hpp)
 #pragma unroll
-  for (int d = 0; d < D; ++d) x[d] = a.xs[(int64_t)d * a.n_pad + i];
+  for (int d = 0; d < D; ++d) {
+    x[d] = a.xs[(int64_t)d * a.n_pad + i];
+    x_nan = x_nan || (x[d] != x[d]);
+  }
   // pad records: the array is rounded up to two batches, so they sit among its last 2 U records
   const int64_t pad_from = a.m_pad - 2 * U;
 
@@ -160,10 +169,12 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_dscale_kernel(const LowdAr
       const int64_t j = jt + jj;
       if (j + U > pad_from) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) dscale_interact<KERNEL, D, E, SIG, true, real>(x, acc, lrec + (jj + u) * R, exp_tab);
+        for (int u = 0; u < U; ++u)
+          dscale_interact<KERNEL, D, E, SIG, true, real>(x, acc, lrec + (jj + u) * R, j + u, a.m, exp_tab);
       } else {
 #pragma unroll
-        for (int u = 0; u < U; ++u) dscale_interact<KERNEL, D, E, SIG, false, real>(x, acc, lrec + (jj + u) * R, exp_tab);
+        for (int u = 0; u < U; ++u)
+          dscale_interact<KERNEL, D, E, SIG, false, real>(x, acc, lrec + (jj + u) * R, j + u, a.m, exp_tab);
       }
     }
     since_fold += LDS_TILE;
@@ -181,7 +192,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_dscale_kernel(const LowdAr
     double v;
     if constexpr (F32) v = accd[c];
     else v = (double)acc[c];
-    a.part[((int64_t)seg * NC + c) * a.n_pad + i] = -grad_constant<KERNEL>() * v;
+    a.part[((int64_t)seg * NC + c) * a.n_pad + i] = nan_target(x_nan, -grad_constant<KERNEL>() * v);
   }
 }
 

@@ -16,13 +16,21 @@
 //
 // Pairs that must contribute exactly 0 although x - y is not finite or w is not:
 //  * pad records (y = +inf: the product's k is 0 there, but 0 * (x - y) = 0 * -inf is NaN).  They only exist among
-//    the last 2 U records of the array, so only those batches pay for the selects on s that zero w AND x - y (GUARD);
+//    the last 2 U records of the array, so only those batches pay for the selects that zero w AND x - y (GUARD).  The
+//    select is on the record's INDEX (j >= M), not on s: a source of the caller's is never taken for a pad record, and
+//    a NaN squared distance stays NaN, wherever in the array the source sits;
 //  * 1/r: the pairs of the reference's flat-index zero rule, in the batches that can hold one (GUARD, as the
 //    product's CHECK_DIAG).  A coincident pair that is NOT zeroed gives inf * 0: that row is NaN in every component,
 //    exactly the rows where the product is inf;
 //  * exp(-r) at s = 0 (not differentiable; 0 is the symmetric subgradient, and the own pair of same_points must
 //    vanish): rsq(0) = inf.  One v_cmp_class per pair keeps w for the positive NORMAL s only (x - y is 0 or tiny
 //    there; a denormal s, r < 1.1e-19 in float32, is flushed by the hardware's rsq: it counts as coincident).
+//
+// Non-finite inputs (include/kmvp.h): a NaN target coordinate makes its row NaN in every component and touches no other
+// row -- the row is restored when it is written (nan_target, kmvp_lowd.hpp: the clamps of kexp_neg_f64 and of the Matern
+// exponents turn a NaN s into w = 0, which would leave the components of the other axes finite).  A source coordinate
+// that is NaN or +-inf is NOT screened (it would cost the unguarded pair loop a select): w (x_d - y_d) is 0 * inf or
+// NaN in the components of that axis, in every row, the same in a guarded batch as in any other.
 #pragma once
 #include "kmvp_lowd.hpp"
 
@@ -62,7 +70,7 @@ struct GradLayout {
 // One (target, source) interaction.
 template <int KERNEL, int D, int E, int SIG, bool GUARD, typename real>
 __device__ __forceinline__ void grad_interact(const real (&x)[D], real (&acc)[GradLayout<D, E, SIG>::NC],
-                                              const real* __restrict__ r, int64_t jz, int64_t j_local,
+                                              const real* __restrict__ r, int64_t jz, int64_t j_local, int64_t m,
                                               const double* __restrict__ tab) {
   real df[D];
   df[0] = x[0] - r[0];
@@ -76,10 +84,10 @@ __device__ __forceinline__ void grad_interact(const real (&x)[D], real (&acc)[Gr
   if constexpr (KERNEL == K_ABSEXP) w = positive_normal(s) ? w : (real)0;
   if constexpr (GUARD) {
     // a pad record: w = 0 is not enough, 0 * (x - y) = 0 * -inf is NaN -- the differences go to 0 with it
-    const bool live = s < (real)INFINITY;
-    w = live ? w : (real)0;
+    const bool pad = j_local >= m;
+    w = pad ? (real)0 : w;
 #pragma unroll
-    for (int d = 0; d < D; ++d) df[d] = live ? df[d] : (real)0;
+    for (int d = 0; d < D; ++d) df[d] = pad ? (real)0 : df[d];
     if constexpr (KERNEL == K_INVDIST) w = (j_local == jz) ? (real)0 : w;
   }
   if constexpr (SIG == SIG_DENSITY) {
@@ -118,8 +126,12 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_grad_kernel(const LowdArgs
   const int64_t i = i0 + lane;                                     // < n_pad by construction; pad targets are 0
 
   real x[D];
+  bool x_nan = false;  // nan_target (kmvp_lowd.hpp)
 #pragma unroll
-  for (int d = 0; d < D; ++d) x[d] = a.xs[(int64_t)d * a.n_pad + i];
+  for (int d = 0; d < D; ++d) {
+    x[d] = a.xs[(int64_t)d * a.n_pad + i];
+    x_nan = x_nan || (x[d] != x[d]);
+  }
   // 1/r: the zero column of this target (bruteforce.py:13-14, as lowd_kernel) and the wave-uniform bounds of the
   // tile's zero columns (conservative when the mod wraps inside the tile: then every batch is guarded)
   int64_t jz = -1, jz_lo = 0, jz_hi = -1;
@@ -203,11 +215,11 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_grad_kernel(const LowdArgs
       if (guard) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          grad_interact<KERNEL, D, E, SIG, true, real>(x, acc, lrec + (jj + u) * R, jz, j + u, exp_tab);
+          grad_interact<KERNEL, D, E, SIG, true, real>(x, acc, lrec + (jj + u) * R, jz, j + u, a.m, exp_tab);
       } else {
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          grad_interact<KERNEL, D, E, SIG, false, real>(x, acc, lrec + (jj + u) * R, jz, j + u, exp_tab);
+          grad_interact<KERNEL, D, E, SIG, false, real>(x, acc, lrec + (jj + u) * R, jz, j + u, a.m, exp_tab);
       }
     }
     since_fold += LDS_TILE;
@@ -224,7 +236,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_grad_kernel(const LowdArgs
     double v;
     if constexpr (F32) v = accd[c];
     else v = (double)acc[c];
-    a.part[((int64_t)seg * NC + c) * a.n_pad + i] = grad_constant<KERNEL>() * v;
+    a.part[((int64_t)seg * NC + c) * a.n_pad + i] = nan_target(x_nan, grad_constant<KERNEL>() * v);
   }
 }
 
