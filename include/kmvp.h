@@ -782,6 +782,14 @@ int kmvp_comm_init_host(kmvp_ctx* ctx, kmvp_host_allreduce_fn fn, void* user, in
  *                      (default) and 1 = such a workgroup builds every source operand once and shares it through LDS,
  *                      wherever the kernel holds that body (eight target tiles per wavefront); 0 = never, every wavefront
  *                      builds its own.  The sums are the same bit for bit either way
+ *   "cell_tail"        cellmm16_kernel's one launch: 1 = where the workgroups of the list of whole groups do not fill whole
+ *                      rounds of resident workgroups (two per compute unit at eight target tiles per wavefront), the target
+ *                      blocks of the last, partial round take k times as many, k times shorter source segments, as many as
+ *                      run at once beside the leftover list (a third list, TAIL: csrc/kmvp_plan.hpp cell_tail_plan); 0 =
+ *                      never; -1 = automatic (default): as 1 at eight target tiles per wavefront from the sizes at which
+ *                      cellmm16_kernel is taken by itself (N >= 500000, M >= 100000).  Rows of the TAIL blocks see other
+ *                      segment cuts and agree with 0 to the cell form's accuracy; all other rows are the same bit for bit
+ *   "cell_tail_resident" the resident workgroups that plan assumes: 0 (default) = the device's; > 0 = this many (tests)
  *   "meanshift_compact" kmvp_gaussian_meanshift: -1 (default) and 1 = the list of active points is compacted after every
  *                      sweep, so the pair loop covers the points still moving; 0 = never, frozen points ride along and are
  *                      ignored.  The results are the same bit for bit either way: it exists to measure what compaction saves
@@ -826,6 +834,14 @@ const char* kmvp_last_dispatch_note(const kmvp_ctx* ctx);
  * Every pointer but info may be NULL: ask for the counts first. */
 int kmvp_cell_layout(kmvp_ctx* ctx, int64_t* info, double* sigma_b, int32_t* source_cell, int32_t* target_cell,
                      double* source_centres, int64_t source_cap, double* target_centres, int64_t target_cap);
+
+/* The lists of target tiles of the last product on cellmm_kernel / cellmm16_kernel (float32 cell form), as that product
+ * planned them: test infrastructure, read-only.  KMVP_E_INVALID unless such a product has run on the current points.
+ *   info[8]          [0], [1], [2] workgroups of target tiles (target blocks) of the MAIN, TAIL and REST list; [3], [4], [5]
+ *                    their source segments; [6] the resident workgroups the TAIL plan assumed ("cell_tail_resident"); [7] 1 =
+ *                    the lists ran in one launch
+ *   target_list [N]  the list whose workgroups computed the target's row: 0 MAIN, 1 REST, 2 TAIL; may be NULL */
+int kmvp_cell_lists(kmvp_ctx* ctx, int64_t* info, int32_t* target_list);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,7 @@ SYMBOLS = [
     ("kmvp_last_total_ms", _c.c_double, [_c.c_void_p]),
     ("kmvp_cell_layout", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_double), _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                     _c.c_int64, _c.c_void_p, _c.c_int64]),
+    ("kmvp_cell_lists", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     ("kmvp_last_kernel_name", _c.c_char_p, [_c.c_void_p]),
     ("kmvp_last_dispatch_note", _c.c_char_p, [_c.c_void_p]),
 ]
@@ -669,6 +670,18 @@ class Context:
         return {"source_cell": scell, "target_cell": tcell, "source_centres": scen[:ns], "target_centres": tcen[:nt],
                 "count_cut": bool(info[2]), "tiles_per_wavefront": int(info[3]), "tile_points": int(info[4]),
                 "image": int(info[5]), "main_tiles": int(info[6]), "rest_tiles": int(info[7]), "sigma_b": float(sigma.value)}
+
+    def cell_lists(self):
+        """The lists of target tiles of the last product on cellmm_kernel / cellmm16_kernel (include/kmvp.h kmvp_cell_lists),
+        read-only: a dict of blocks and segments (MAIN, TAIL, REST), resident, fused and target_list (N,) int32 (0 MAIN, 1
+        REST, 2 TAIL)."""
+        if not self._ctx:
+            raise ValueError("the context is closed")
+        info = np.zeros(8, dtype=np.int64)
+        lists = np.empty(self.N, dtype=np.int32)
+        self._check(self._lib.kmvp_cell_lists(self._ctx, info.ctypes.data, lists.ctypes.data))
+        return {"blocks": tuple(int(v) for v in info[0:3]), "segments": tuple(int(v) for v in info[3:6]),
+                "resident": int(info[6]), "fused": bool(info[7]), "target_list": lists}
 
 
 def comm_unique_id():

@@ -73,6 +73,7 @@ kmvp_ctx* kmvp_create(int device, int* status) {
   bool ok = hipSetDevice(device) == hipSuccess &&
             hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
   for (int i = 0; ok && i < 5; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
+  ok = ok && hipDeviceGetAttribute(&c->device_cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess;
   if (!ok) {
     fail(nullptr, KMVP_E_DEVICE, "cannot create stream/events on the device");
     if (status) *status = KMVP_E_DEVICE;
@@ -458,6 +459,12 @@ int kmvp_set_option(kmvp_ctx* c, const char* key, int64_t value) {
   } else if (k == "cell_balance") {
     if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "cell_balance must be -1 (automatic), 0 (never) or 1 (wherever count-cut cells apply)");
     c->opt_cell_balance = (int)value;
+  } else if (k == "cell_tail") {
+    if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "cell_tail must be -1 (automatic), 0 (never) or 1 (wherever the fused grid has a partial last round)");
+    c->opt_cell_tail = (int)value;
+  } else if (k == "cell_tail_resident") {
+    if (value < 0 || value > 65536) return fail(c, KMVP_E_INVALID, "cell_tail_resident must be 0 (the device's: two workgroups per compute unit) or a number of workgroups up to 65536");
+    c->opt_cell_tail_resident = (int)value;
   } else if (k == "cell_shared_build") {
     if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "cell_shared_build must be -1 (automatic), 0 (never) or 1 (wherever a workgroup is one-cell)");
     c->opt_cell_shared_build = (int)value;
@@ -502,6 +509,11 @@ int kmvp_cell_layout(kmvp_ctx* c, int64_t* info, double* sigma_b, int32_t* sourc
                      double* source_centres, int64_t source_cap, double* target_centres, int64_t target_cap) {
   if (!c) return KMVP_E_INVALID;
   return cell_layout_read(c, info, sigma_b, source_cell, target_cell, source_centres, source_cap, target_centres, target_cap);
+}
+
+int kmvp_cell_lists(kmvp_ctx* c, int64_t* info, int32_t* target_list) {
+  if (!c) return KMVP_E_INVALID;
+  return cell_lists_read(c, info, target_list);
 }
 const char* kmvp_last_kernel_name(const kmvp_ctx* c) { return c ? c->last_kernel_name : ""; }
 const char* kmvp_last_dispatch_note(const kmvp_ctx* c) { return c ? c->note.c_str() : ""; }

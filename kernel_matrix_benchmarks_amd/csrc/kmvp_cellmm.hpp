@@ -428,6 +428,9 @@ __device__ __forceinline__ void cellmm16_weight_sum(float bq, float wexp, float&
 #ifndef CMM16_NOFOLD
 #define CMM16_NOFOLD 0  // 1: timing only, wrong sums -- the fold and U compiled out, their inputs kept live (what the fold costs)
 #endif
+#ifndef CMM16_WHOLE_ROUNDS
+#define CMM16_WHOLE_ROUNDS 0  // 1: timing only, wrong sums -- the TAIL list is planned whatever the option says, and the fused launch ends
+#endif                        // with the MAIN list's whole rounds: neither TAIL nor REST is launched (what the last, partial round costs)
 #ifndef CMM16_BUILD_PROBE
 #define CMM16_BUILD_PROBE 0  // 1: timing only, wrong sums -- wave w builds the operand of every fourth tile only ((q & 3) == w) and
                              // reuses it for the three tiles between, their records still read: what three of four builds cost
@@ -752,30 +755,46 @@ __device__ __forceinline__ bool cellmm16_one_cell(const CellmmArgs& a, int bid) 
 // the partial sums.  The branch is uniform per workgroup, each body keeps its one site of accumulating MFMAs and its own
 // accumulators, and all share the one LDS array.  main_grid == gridDim.x: the main list alone (`rest` is not read).
 // a.shared_build != 0: the main list's one-cell workgroups (cellmm16_one_cell) run the shared-build body.
+// tail_grid != 0: the workgroups [main_grid, main_grid + tail_grid) run the TAIL list `tail` (cell_tail_split, kmvp_plan.hpp):
+// target blocks of the main list in more, shorter segments.  They are main-list workgroups in all but their arguments, so
+// they take the very calls below, on `tail` in place of `a` -- no further body, no further site of accumulating MFMAs.
 template <int TT>
 __global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(TT >= 8 ? 2 : 1)))
-cellmm16_kernel(const CellmmArgs a, const CellmmArgs rest, const int main_grid) {
+cellmm16_kernel(const CellmmArgs a, const CellmmArgs rest, const int main_grid, const CellmmArgs tail, const int tail_grid) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[cellmm16_lds_bytes(TT)];
+  // (the list's arguments are chosen field by field, scalar selects on kernel arguments: a pointer to one of two argument
+  // structs made the compiler copy them to scratch memory)
+  CellmmArgs m = a;
+  int bid = (int)blockIdx.x;
   if constexpr (TT > CELL_REST_TT) {
-    const FusedCellWork w = fused_cell_work((int64_t)blockIdx.x, (int64_t)main_grid);
-    if (w.list) {
+    const FusedCellWork w = fused_cell_work((int64_t)blockIdx.x, (int64_t)main_grid, (int64_t)tail_grid);
+    if (w.list == 1) {
       cellmm16_body<CELL_REST_TT, false>(rest, (int)w.local, lds);
       return;
     }
+    const bool t = w.list == 2;  // what cell_args() sets per list; the rest is common to all lists
+    m.part = t ? tail.part : a.part;
+    m.n_slots = t ? tail.n_slots : a.n_slots;
+    m.tile_base = t ? tail.tile_base : a.tile_base;
+    m.seg_stages = t ? tail.seg_stages : a.seg_stages;
+    m.segments = t ? tail.segments : a.segments;
+    m.tile_blocks = t ? tail.tile_blocks : a.tile_blocks;
+    bid = (int)w.local;
   }
   if constexpr (cellmm16_has_shared(TT)) {
-    if (a.shared_build && cellmm16_one_cell<TT>(a, (int)blockIdx.x)) {
-      cellmm16_body<TT, true>(a, (int)blockIdx.x, lds);
+    if (m.shared_build && cellmm16_one_cell<TT>(m, bid)) {
+      cellmm16_body<TT, true>(m, bid, lds);
       return;
     }
   }
-  cellmm16_body<TT, false>(a, (int)blockIdx.x, lds);
+  cellmm16_body<TT, false>(m, bid, lds);
 }
 
 // shape: 0 = cellmm_kernel (32x32x16), 1 = cellmm16_kernel (16x16x32)
 hipError_t launch_cellmm_gaussian(int TT, int shape, const CellmmArgs& args, dim3 grid, hipStream_t stream, const char** kernel_name);
-// cellmm16_kernel<TT> (TT > CELL_REST_TT) over both lists in one grid of main_grid + rest_grid workgroups
-hipError_t launch_cellmm16_fused(int TT, const CellmmArgs& main, const CellmmArgs& rest, int64_t main_grid, int64_t rest_grid,
-                                 hipStream_t stream, const char** kernel_name);
+// cellmm16_kernel<TT> (TT > CELL_REST_TT) over the lists in one grid of main_grid + tail_grid + rest_grid workgroups
+// (tail_grid == 0: no TAIL list, `tail` is not read)
+hipError_t launch_cellmm16_fused(int TT, const CellmmArgs& main, const CellmmArgs& rest, const CellmmArgs& tail, int64_t main_grid,
+                                 int64_t tail_grid, int64_t rest_grid, hipStream_t stream, const char** kernel_name);
 
 }  // namespace kmvp

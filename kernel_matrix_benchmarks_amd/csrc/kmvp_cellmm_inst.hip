@@ -22,10 +22,10 @@ hipError_t launch_cellmm_gaussian(int TT, int shape, const CellmmArgs& args, dim
   if (shape == 1) {  // one list alone: every workgroup is below main_grid
     const int all = (int)grid.x;
     switch (TT) {
-      case 1: cmm_launch(cellmm16_kernel<1>, args, grid, stream, args, all); break;
-      case 2: cmm_launch(cellmm16_kernel<2>, args, grid, stream, args, all); break;
-      case 4: cmm_launch(cellmm16_kernel<4>, args, grid, stream, args, all); break;
-      case 8: cmm_launch(cellmm16_kernel<8>, args, grid, stream, args, all); break;
+      case 1: cmm_launch(cellmm16_kernel<1>, args, grid, stream, args, all, args, 0); break;
+      case 2: cmm_launch(cellmm16_kernel<2>, args, grid, stream, args, all, args, 0); break;
+      case 4: cmm_launch(cellmm16_kernel<4>, args, grid, stream, args, all, args, 0); break;
+      case 8: cmm_launch(cellmm16_kernel<8>, args, grid, stream, args, all, args, 0); break;
       default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -40,14 +40,18 @@ hipError_t launch_cellmm_gaussian(int TT, int shape, const CellmmArgs& args, dim
   return hipGetLastError();
 }
 
-hipError_t launch_cellmm16_fused(int TT, const CellmmArgs& main, const CellmmArgs& rest, int64_t main_grid, int64_t rest_grid,
-                                 hipStream_t stream, const char** kernel_name) {
+hipError_t launch_cellmm16_fused(int TT, const CellmmArgs& main, const CellmmArgs& rest, const CellmmArgs& tail, int64_t main_grid,
+                                 int64_t tail_grid, int64_t rest_grid, hipStream_t stream, const char** kernel_name) {
   if (kernel_name) *kernel_name = "cellmm16_kernel";
-  if (main_grid + rest_grid > MAX_GRID) return hipErrorInvalidConfiguration;
-  const dim3 grid((unsigned)(main_grid + rest_grid));
+  if (main_grid + tail_grid + rest_grid > MAX_GRID) return hipErrorInvalidConfiguration;
+#if CMM16_WHOLE_ROUNDS
+  const dim3 grid((unsigned)main_grid);
+#else
+  const dim3 grid((unsigned)(main_grid + tail_grid + rest_grid));
+#endif
   switch (TT) {  // TT > CELL_REST_TT: the kernels that hold the second body
-    case 4: cmm_launch(cellmm16_kernel<4>, main, grid, stream, rest, (int)main_grid); break;
-    case 8: cmm_launch(cellmm16_kernel<8>, main, grid, stream, rest, (int)main_grid); break;
+    case 4: cmm_launch(cellmm16_kernel<4>, main, grid, stream, rest, (int)main_grid, tail, (int)tail_grid); break;
+    case 8: cmm_launch(cellmm16_kernel<8>, main, grid, stream, rest, (int)main_grid, tail, (int)tail_grid); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

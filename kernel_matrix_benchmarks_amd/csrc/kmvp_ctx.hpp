@@ -187,6 +187,10 @@ struct kmvp_ctx {
   int opt_cell_shared_build = -1;         // cellmm16_kernel's one-cell workgroups build each source operand once: -1 / 1 = where the kernel holds that body (cell_shared_build), 0 = never
   int opt_cell_balance = -1;              // float32 cell lists: lattice columns cut along z by point count: -1 = where it applies at the sizes cellmm16_kernel is taken by itself, 1 = wherever it applies (cell_balance_applies), 0 = never
   int opt_cell_fused = -1;                // cellmm16_kernel's two tile lists: -1 / 1 = one launch where it applies (fused_cell_grid), 0 = two launches
+  int opt_cell_tail = -1;                 // cellmm16_kernel's fused grid: the MAIN list's last, partial round in short segments (the TAIL list, cell_tail_split): -1 = automatic (cell_tail_taken), 0 = never, 1 = wherever it applies
+  int opt_cell_tail_resident = 0;         // resident workgroups the TAIL plan assumes: 0 = two per CU of the device; > 0 = this many (tests)
+  int device_cus = 0;                     // compute units of the device (kmvp_create)
+  int64_t cell_list_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the lists of the last product on cellmm_kernel / cellmm16_kernel: kmvp_cell_lists
   int opt_mfma_variant = -1;              // bf16 path: VAR of mfma_pipe_kernel (kmvp_mfma.hpp); -1 = by kernel
   int opt_meanshift_compact = -1;         // mean-shift: -1 / 1 = the active list is compacted after every sweep, 0 = never (frozen lanes ride along)
   int opt_same_global = 0;                // the targets ARE the (unsharded) sources although x was passed explicitly
@@ -303,6 +307,7 @@ int precond_read(kmvp_ctx* c, int* rank_built, int64_t* pivots, double* factor);
 // kmvp_product.hip: kmvp_cell_layout, the cell structures the last product on the cell form ran on, read back
 int cell_layout_read(kmvp_ctx* c, int64_t* info, double* sigma_b, int32_t* source_cell, int32_t* target_cell,
                      double* source_centres, int64_t source_cap, double* target_centres, int64_t target_cap);
+int cell_lists_read(kmvp_ctx* c, int64_t* info, int32_t* target_list);  // kmvp_cell_lists
 
 // kmvp_solvers.hip
 int cg_solve(kmvp_ctx* c, int kernel, const void* a_host, int E, double rtol, int maxit, double* out_b,

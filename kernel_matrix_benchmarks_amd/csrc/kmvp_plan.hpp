@@ -209,13 +209,33 @@ inline TileList cell_tiles_split(const unsigned* keys, int64_t n, int TT, int64_
 // each, so its own, finer split of the sources).  Each grid has its own segments and its own region
 // [segment][cols][slots] of the partial sums.  cell_kernel and cellmm_kernel run them as two launches, one after the
 // other; cellmm16_kernel as ONE launch, the REST grid behind the MAIN grid (fused_cell_grid below).
+//
+// A third list, r = 2 the TAIL, is empty unless cell_tail_split() (below) cuts it off the MAIN list: the MAIN list's last
+// workgroups of target tiles, in more and shorter segments.  In the tile list and in the sums the lists stand MAIN, TAIL,
+// REST (CELL_LIST_ORDER): the TAIL's tiles are the MAIN tiles they were, in place.
+constexpr int CELL_LISTS = 3;
+constexpr int CELL_LIST_ORDER[CELL_LISTS] = {0, 2, 1};  // the lists in the order of their tiles, slots and regions
 struct CellSplit {
-  int64_t m_stages, n_slots;  // source stages; target slots of both lists
-  int64_t blocks[2], slots[2], seg_stages[2];
-  int segments[2];
+  int64_t m_stages, n_slots;  // source stages; target slots of all lists
+  int64_t blocks[CELL_LISTS], slots[CELL_LISTS], seg_stages[CELL_LISTS];
+  int segments[CELL_LISTS];
   int64_t grid(int r) const { return blocks[r] * segments[r]; }
-  size_t region_offset(int cols, int r) const { return r ? (size_t)segments[0] * cols * slots[0] : 0; }  // in doubles
-  size_t part_doubles(int cols) const { return ((size_t)segments[0] * slots[0] + (size_t)segments[1] * slots[1]) * cols; }
+  // first slot of list r among the n_slots (its first tile is slot_base / CELL_TILE)
+  int64_t slot_base(int r) const {
+    int64_t at = 0;
+    for (int o = 0; o < CELL_LISTS && CELL_LIST_ORDER[o] != r; ++o) at += slots[CELL_LIST_ORDER[o]];
+    return at;
+  }
+  size_t region_offset(int cols, int r) const {  // in doubles
+    size_t at = 0;
+    for (int o = 0; o < CELL_LISTS && CELL_LIST_ORDER[o] != r; ++o) at += (size_t)segments[CELL_LIST_ORDER[o]] * cols * slots[CELL_LIST_ORDER[o]];
+    return at;
+  }
+  size_t part_doubles(int cols) const {
+    size_t n = 0;
+    for (int r = 0; r < CELL_LISTS; ++r) n += (size_t)segments[r] * slots[r] * cols;
+    return n;
+  }
 };
 
 // N targets in n_main / n_rest tiles; m_tiles source tiles in stages of stage_tiles; `main`: the rule of the main launch
@@ -243,6 +263,9 @@ inline CellSplit cell_split(int64_t N, int64_t m_tiles, int64_t n_main, int64_t 
     s.seg_stages[1] = (s.m_stages + seg - 1) / seg;
     s.segments[1] = (int)((s.m_stages + s.seg_stages[1] - 1) / s.seg_stages[1]);
   }
+  s.blocks[2] = s.slots[2] = 0;  // no TAIL list (cell_tail_split)
+  s.segments[2] = 0;
+  s.seg_stages[2] = 1;
   return s;
 }
 
@@ -259,12 +282,17 @@ inline CellSplit cell_split(int64_t N, int64_t m_tiles, int64_t n_main, int64_t 
 // the REST workgroups that share an XCD in the fused grid are those that shared one in their own launch, and the XCD
 // affinity of block_to_work() holds for them.
 // (constexpr: the kernel calls the very function the host tests hold to its properties)
+//
+// With a TAIL list (cell_tail_split below) the order is MAIN, TAIL, REST: list 2 stands between the two, tail_grid
+// workgroups of it.  main_grid and tail_grid are both multiples of 8 then, so the same holds for TAIL and REST alike.
 struct FusedCellWork {
   int list;
   int64_t local;
 };
-constexpr FusedCellWork fused_cell_work(int64_t bid, int64_t main_grid) {
-  return bid < main_grid ? FusedCellWork{0, bid} : FusedCellWork{1, bid - main_grid};
+constexpr FusedCellWork fused_cell_work(int64_t bid, int64_t main_grid, int64_t tail_grid = 0) {
+  return bid < main_grid               ? FusedCellWork{0, bid}
+         : bid < main_grid + tail_grid ? FusedCellWork{2, bid - main_grid}
+                                       : FusedCellWork{1, bid - main_grid - tail_grid};
 }
 
 // The fused grid of a split `s` with tt tiles per wavefront in the MAIN list.  opt_fused: the "cell_fused" option, -1 =
@@ -273,15 +301,101 @@ constexpr FusedCellWork fused_cell_work(int64_t bid, int64_t main_grid) {
 // empty while the REST list is not is a fused grid with main_grid = 0.  fused == false: the two grids are two launches.
 struct FusedCellGrid {
   bool fused;
-  int64_t main_grid, rest_grid, total;
+  int64_t main_grid, rest_grid, total, tail_grid;
 };
 inline FusedCellGrid fused_cell_grid(const CellSplit& s, int tt, int opt_fused) {
   FusedCellGrid g;
   g.main_grid = s.grid(0);
   g.rest_grid = s.grid(1);
-  g.total = g.main_grid + g.rest_grid;
+  g.tail_grid = s.grid(2);
+  g.total = g.main_grid + g.tail_grid + g.rest_grid;
   g.fused = opt_fused != 0 && tt > CELL_REST_TT && s.blocks[1] > 0 && g.total <= MAX_GRID;
   return g;
+}
+
+// ---- the last round of the fused grid in short segments (the TAIL list) -------------------------------------------------
+
+// The MAIN list's workgroups are equally long and come in rounds of R resident workgroups (two per CU at eight tiles per
+// wavefront).  B target blocks x S segments are seldom whole rounds: at the headline shape 978 x 8 = 7824 workgroups are
+// 15 rounds of 512 and 144 more, which run their full length with 368 of 512 slots idle.  So the blocks of the whole
+// rounds stay as they are, and the blocks left over are cut into k times as many segments, k times shorter, as many as
+// fit the chip at once together with the REST list behind them:
+//  * b_full, the largest count of blocks with b_full S a multiple of R (and of 8), keeps S segments;
+//  * the last b_tail = B - b_full blocks take `segments` = S k segments of whole stages, k the largest integer with
+//    b_tail S k + rest_grid <= R; capped at CELL_TAIL_MAX_SEGMENTS and at m_stages / min_seg (no segment shorter than the
+//    rule's minimum), then settled (settle_segments) -- a k whose settled count is no multiple of 8 or no longer fits
+//    gives way to k - 1;
+//  * no TAIL (b_tail == 0) without whole rounds (b_full == 0), without blocks left over, or when k < 2.
+// rest_grid: the slots of a round kept for the REST list -- cell_tail_split() passes its weight, not its number of
+// workgroups (cell_rest_weight).
+// The fused grid is MAIN (b_full S), TAIL (b_tail S k), REST: each part starts at a multiple of 8, so that a workgroup's
+// index in its own list and its index in the grid agree modulo 8 and block_to_work()'s XCD affinity holds for every list.
+// Every (target block, stage) pair is still taken exactly once; the TAIL blocks' sums see other segment cuts (more folds,
+// another order of the fp64 partial sums), all other rows are bit for bit what they were.  Order decides speed alone.
+constexpr int CELL_TAIL_MAX_SEGMENTS = 64;
+struct CellTail {
+  int64_t b_full, b_tail, seg_stages;
+  int segments;
+};
+inline CellTail cell_tail_plan(int64_t B, int S, int64_t R, int64_t m_stages, int64_t rest_grid, int64_t min_seg) {
+  const CellTail none = {B, 0, 1, 0};
+  if (B <= 0 || S <= 0 || R <= 0) return none;
+  int64_t gcd = R, t = S;
+  while (t) {
+    const int64_t u = gcd % t;
+    gcd = t;
+    t = u;
+  }
+  const int64_t q = R / gcd;  // blocks per smallest number of whole rounds
+  const int64_t b_full = B / q * q, b_tail = B - b_full;
+  if (b_full == 0 || b_tail == 0 || (b_full * S) % 8 != 0 || rest_grid >= R) return none;
+  const int64_t cap = std::min<int64_t>(CELL_TAIL_MAX_SEGMENTS, m_stages / std::max<int64_t>(min_seg, 1));
+  for (int64_t k = (R - rest_grid) / (b_tail * S); k >= 2; --k) {
+    const int64_t want = std::min<int64_t>(S * k, cap);
+    if (want <= S) break;
+    const int64_t seg = settle_segments(m_stages, (int)want);
+    if (seg % 8 == 0 && seg > S && seg <= cap && b_tail * seg + rest_grid <= R)
+      return {b_full, b_tail, (m_stages + seg - 1) / seg, (int)seg};
+  }
+  return none;
+}
+
+// Is the TAIL list taken?  opt: the "cell_tail" option, -1 = automatic, 0 = never, 1 = wherever it applies: a fused launch
+// (fused_cell_grid) with more than CELL_REST_TT tiles per wavefront.  Automatic: at eight tiles per wavefront, from the sizes
+// from which cellmm16_kernel is taken by itself (as cell_balance_taken: below them no result changes unless asked for).
+// KMVP_CELL_TAIL_AUTO=0 builds a library whose automatic is off (the arm it was measured against).
+#ifndef KMVP_CELL_TAIL_AUTO
+#define KMVP_CELL_TAIL_AUTO 1
+#endif
+constexpr bool CELL_TAIL_AUTO = KMVP_CELL_TAIL_AUTO != 0;
+constexpr int CELL_TAIL_AUTO_TT = 8;
+constexpr int64_t CELL_TAIL_AUTO_N = 500000, CELL_TAIL_AUTO_M = 100000;  // CELLMM16_AUTO_N, CELLMM16_AUTO_M (below)
+constexpr bool cell_tail_taken(int opt, int tt, bool fused, int64_t N, int64_t M) {
+  return fused && tt > CELL_REST_TT &&
+         (opt > 0 || (opt < 0 && CELL_TAIL_AUTO && tt == CELL_TAIL_AUTO_TT && N >= CELL_TAIL_AUTO_N && M >= CELL_TAIL_AUTO_M));
+}
+
+// The REST list beside the TAIL, in workgroups of the MAIN list's length.  Its own workgroups are many and short (headline
+// shape: 17 blocks x 94 segments = 1598 workgroups of 28 stages x 2 tiles per wavefront, against 327 stages x 8 tiles): by
+// their number they would never fit a round, by their work they are 35 of its 512 slots.
+inline int64_t cell_rest_weight(const CellSplit& s, int tt) {
+  const int64_t main_work = std::max<int64_t>(1, s.seg_stages[0] * tt);
+  return (s.grid(1) * s.seg_stages[1] * CELL_REST_TT + main_work - 1) / main_work;
+}
+
+// Cuts the TAIL list off the MAIN list of a split `s` (tt tiles per wavefront in both); `resident`: R.  Returns whether
+// there is one.  The TAIL's tiles, slots and region of the partial sums follow the MAIN list's (CELL_LIST_ORDER).
+inline bool cell_tail_split(CellSplit& s, int tt, int64_t resident, int64_t min_seg) {
+  const CellTail t = cell_tail_plan(s.blocks[0], s.segments[0], resident, s.m_stages, cell_rest_weight(s, tt), min_seg);
+  if (t.b_tail == 0) return false;
+  const int64_t block_slots = (int64_t)tt * WAVES_PER_BLOCK * CELL_TILE;
+  s.blocks[0] = t.b_full;
+  s.slots[0] = t.b_full * block_slots;
+  s.blocks[2] = t.b_tail;
+  s.slots[2] = t.b_tail * block_slots;
+  s.segments[2] = t.segments;
+  s.seg_stages[2] = t.seg_stages;
+  return true;
 }
 
 // ---- one-cell workgroups (cellmm16_kernel's shared operand build) -------------------------------------------------------
@@ -406,6 +520,7 @@ constexpr bool cell_balance_applies(int D, bool f32, int tt, int cap) {
   return D == 3 && f32 && tt == CELL_SHARED_TT && cap >= CELL_BALANCE_MIN_CAP;
 }
 constexpr int64_t CELLMM16_AUTO_N = 500000, CELLMM16_AUTO_M = 100000;  // from here cellmm16_kernel is taken by itself (at TT = 8)
+static_assert(CELL_TAIL_AUTO_N == CELLMM16_AUTO_N && CELL_TAIL_AUTO_M == CELLMM16_AUTO_M, "one size rule");
 constexpr bool cell_balance_taken(int opt, bool applies, int64_t N, int64_t M) {
   return opt != 0 && applies && (opt > 0 || (N >= CELLMM16_AUTO_N && M >= CELLMM16_AUTO_M));
 }

@@ -1521,12 +1521,17 @@ template <class Args>
 void cell_args(const kmvp_ctx* c, const CellSplit& s, int cols, int r, Args& a) {
   a.part = cell_region(c, s, cols, r);
   a.n_slots = s.slots[r];
-  a.tile_base = r ? c->cell_n_main : 0;
+  a.tile_base = s.slot_base(r) / CELL_TILE;  // MAIN 0, TAIL behind the MAIN list's whole rounds, REST at cell_n_main
   a.seg_stages = s.seg_stages[r];
   a.segments = s.segments[r];
   a.tile_blocks = (int)s.blocks[r];
 }
-inline int cell_tt(const kmvp_ctx* c, int r) { return r ? CELL_REST_TT : c->cell_tt; }
+inline int cell_tt(const kmvp_ctx* c, int r) { return r == 1 ? CELL_REST_TT : c->cell_tt; }
+// resident workgroups of cellmm16_kernel<tt> on this device (the TAIL plan's R): two per CU at eight tiles per wavefront
+// (224 registers: two wavefronts per SIMD), four at four (118 registers); "cell_tail_resident" overrides it
+inline int64_t cell_tail_resident(const kmvp_ctx* c, int tt) {
+  return c->opt_cell_tail_resident > 0 ? c->opt_cell_tail_resident : (int64_t)c->device_cus * (tt >= 8 ? 2 : 4);
+}
 
 // The targets of the float32 cell kernels (cell_kernel, cellmm_kernel): coordinates in tile order (xs), tile centres
 // (cell_tmeta), the slot of every target (cell_slot)
@@ -1585,7 +1590,7 @@ int run_product_cell(kmvp_ctx* c, int sig) {
   a.chunk_stages = std::max(1, c->opt_chunk / (CELL_TILE * CELL_STAGE_TILES));
   HIP_TRY(c, mark(c, 0));
   hipError_t le = hipSuccess;
-  for (int r = 0; r < 2 && le == hipSuccess; ++r)
+  for (int r = 0; r < CELL_LISTS && le == hipSuccess; ++r)  // (no TAIL list here: a launch per list)
     if (s.blocks[r] > 0) {
       cell_args(c, s, NE, r, a);
       le = launch_cell_gaussian(sig, cell_tt(c, r), a, dim3((unsigned)s.grid(r)), c->stream, &c->last_kernel_name);
@@ -1597,11 +1602,11 @@ int run_product_cell(kmvp_ctx* c, int sig) {
   // ---- epilogue: segments -> sums in the caller's order, [all-reduce over the source shards], normalise
   if ((rc = ensure(c, c->sums, (size_t)NE * N * sizeof(double)))) return rc;
   if ((rc = ensure(c, c->cell_sums, (size_t)NE * n_slots * sizeof(double)))) return rc;
-  for (int r = 0; r < 2; ++r)
+  for (int r = 0; r < CELL_LISTS; ++r)
     if (s.blocks[r] > 0)
       hipLaunchKernelGGL(reduce_region_kernel, dim3(blocks_for((int64_t)NE * s.slots[r])), dim3(256), 0, c->stream,
                          (const double*)cell_region(c, s, NE, r), (double*)c->cell_sums.p, s.slots[r], NE, s.segments[r], n_slots,
-                         r ? s.slots[0] : (int64_t)0);
+                         s.slot_base(r));
   hipLaunchKernelGGL(gather_cells_kernel, dim3(blocks_for((int64_t)NE * N)), dim3(256), 0, c->stream,
                      (const double*)c->cell_sums.p, (const int*)c->cell_slot.p, (double*)c->sums.p, N, n_slots, NE);
   HIP_TRY(c, hipGetLastError());
@@ -1642,11 +1647,30 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
   rule.min_seg = 2;
   rule.l2_seg_bytes = 3 << 20;
   rule.target_blocks = 7168;
-  const CellSplit s = cell_plan(c, CMM_STAGE_TILES, rule);
+  CellSplit s = cell_plan(c, CMM_STAGE_TILES, rule);
   const int64_t m_stages = s.m_stages, n_slots = s.n_slots;
   int rc;
   CellGrid grid;
   cell_load_grid(c, grid);
+  // MFMA shape: 16x16x32 (cellmm16_kernel) sustains more under the power limit, but issues twice the MFMAs per flop:
+  // 1e6 points 27.7 -> 26.6 ms, 5e5 equal, 2e5 (smaller cells' tile groups) 1.73 -> 1.96 ms (tools/cellmm_shapes.py).  What
+  // counts is how full the TARGET cells are, not the pair count: one of eight ranks' share of config 2 (1e6 targets x 125 000
+  // sources) gains 3 % as well (3.72 -> 3.60 ms, tools/c2_shard.py --shape)
+  const int shape = c->opt_cellmm_shape >= 0 ? c->opt_cellmm_shape : ((TT >= 8 && c->N >= CELLMM16_AUTO_N && c->M >= CELLMM16_AUTO_M) ? 1 : 0);
+  FusedCellGrid fg = fused_cell_grid(s, TT, c->opt_cell_fused);
+  if (shape != 1) fg.fused = false;  // cellmm_kernel keeps its two launches
+  // the fused grid's last, partial round of MAIN workgroups in short segments: the TAIL list (cell_tail_split, kmvp_plan.hpp)
+  const int64_t resident = cell_tail_resident(c, TT);
+  if ((CMM16_WHOLE_ROUNDS || cell_tail_taken(c->opt_cell_tail, TT, fg.fused, c->N, c->M)) && fg.fused &&
+      cell_tail_split(s, TT, resident, small_problem(N) ? 1 : rule.min_seg)) {
+    fg = fused_cell_grid(s, TT, 1);
+    c->note = std::string(c->note.empty() ? "" : c->note + "; ") + "tail list: the last " + std::to_string(s.blocks[2]) +
+              " target blocks in " + std::to_string(s.segments[2]) + " segments (cell_tail)";
+  }
+  {
+    const int64_t info[8] = {s.blocks[0], s.blocks[2], s.blocks[1], s.segments[0], s.segments[2], s.segments[1], resident, fg.fused ? 1 : 0};
+    memcpy(c->cell_list_info, info, sizeof info);
+  }
 
   const PackKey key = {LAYOUT_CELLMM, K_GAUSSIAN, TT};
   // the image holds ONE column's signal: it can be reused only by single-column products
@@ -1671,13 +1695,6 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
   if ((rc = ensure(c, c->part, s.part_doubles(1) * sizeof(double)))) return rc;
   if ((rc = ensure(c, c->sums, (size_t)NE * N * sizeof(double)))) return rc;
   if ((rc = ensure(c, c->cell_sums, (size_t)NE * n_slots * sizeof(double)))) return rc;
-  // MFMA shape: 16x16x32 (cellmm16_kernel) sustains more under the power limit, but issues twice the MFMAs per flop:
-  // 1e6 points 27.7 -> 26.6 ms, 5e5 equal, 2e5 (smaller cells' tile groups) 1.73 -> 1.96 ms (tools/cellmm_shapes.py).  What
-  // counts is how full the TARGET cells are, not the pair count: one of eight ranks' share of config 2 (1e6 targets x 125 000
-  // sources) gains 3 % as well (3.72 -> 3.60 ms, tools/c2_shard.py --shape)
-  const int shape = c->opt_cellmm_shape >= 0 ? c->opt_cellmm_shape : ((TT >= 8 && c->N >= CELLMM16_AUTO_N && c->M >= CELLMM16_AUTO_M) ? 1 : 0);
-  FusedCellGrid fg = fused_cell_grid(s, TT, c->opt_cell_fused);
-  if (shape != 1) fg.fused = false;  // cellmm_kernel keeps its two launches
   CellmmArgs a;
   a.xd = (const float*)c->xs.p;
   a.tmeta = (const float*)c->cell_tmeta.p;
@@ -1701,16 +1718,17 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
       HIP_TRY(c, hipGetLastError());
       if (NE == 1) HIP_TRY(c, mark(c, 0));
     }
-    // cellmm16_kernel takes both lists in ONE launch, the REST list's workgroups behind the MAIN list's (fused_cell_grid,
-    // kmvp_plan.hpp); otherwise the MAIN list, then the REST list, a launch each
+    // cellmm16_kernel takes all lists in ONE launch, the MAIN list's workgroups, then the TAIL list's (if any), then the REST
+    // list's (fused_cell_grid, kmvp_plan.hpp); otherwise the MAIN list, then the REST list, a launch each
     hipError_t le = hipSuccess;
     if (fg.fused) {
-      CellmmArgs ar = a;
+      CellmmArgs ar = a, at = a;
       cell_args(c, s, 1, 0, a);
       cell_args(c, s, 1, 1, ar);
-      le = launch_cellmm16_fused(TT, a, ar, fg.main_grid, fg.rest_grid, c->stream, &c->last_kernel_name);
+      cell_args(c, s, 1, 2, at);
+      le = launch_cellmm16_fused(TT, a, ar, at, fg.main_grid, fg.tail_grid, fg.rest_grid, c->stream, &c->last_kernel_name);
     } else {
-      for (int r = 0; r < 2 && le == hipSuccess; ++r)
+      for (int r = 0; r < CELL_LISTS && le == hipSuccess; ++r)
         if (s.blocks[r] > 0) {
           cell_args(c, s, 1, r, a);
           le = launch_cellmm_gaussian(cell_tt(c, r), shape, a, dim3((unsigned)s.grid(r)), c->stream, &c->last_kernel_name);
@@ -1721,10 +1739,10 @@ int run_product_cellmm(kmvp_ctx* c, int sig) {
     if (NE == 1) HIP_TRY(c, mark(c, 1));
     // segments -> this column's sums in cell order (each launch's region with its own number of segments)
     double* col_sums = (double*)c->cell_sums.p + (size_t)col * n_slots;
-    for (int r = 0; r < 2; ++r)
+    for (int r = 0; r < CELL_LISTS; ++r)
       if (s.blocks[r] > 0)
         hipLaunchKernelGGL(reduce_segments_kernel, dim3(blocks_for(s.slots[r])), dim3(256), 0, c->stream,
-                           (const double*)cell_region(c, s, 1, r), col_sums + (r ? s.slots[0] : 0), s.slots[r], s.segments[r], 0);
+                           (const double*)cell_region(c, s, 1, r), col_sums + s.slot_base(r), s.slots[r], s.segments[r], 0);
     HIP_TRY(c, hipGetLastError());
   }
   if (NE > 1) HIP_TRY(c, mark(c, 1));  // several columns: the "kernel" time covers every column's pack + pair loop
@@ -2199,6 +2217,24 @@ int cell_layout_read(kmvp_ctx* c, int64_t* info, double* sigma_b, int32_t* sourc
   if (target_cell) memcpy(target_cell, tcell.data(), (size_t)N * sizeof(int32_t));
   if (source_centres) memcpy(source_centres, scen.data(), scen.size() * sizeof(double));
   if (target_centres) memcpy(target_centres, tcen.data(), tcen.size() * sizeof(double));
+  return KMVP_OK;
+}
+
+// kmvp_cell_lists: the lists of target tiles of the last product on cellmm_kernel / cellmm16_kernel and the list of every
+// target's slot.  Read-only.
+int cell_lists_read(kmvp_ctx* c, int64_t* info, int32_t* target_list) {
+  if (!info) return fail(c, KMVP_E_INVALID, "kmvp_cell_lists: info is NULL");
+  if (!c->have_points || c->cell_state != 1 || c->cell_ver != c->points_ver || c->packed_points_ver != c->points_ver ||
+      c->packed_layout != LAYOUT_CELLMM)
+    return fail(c, KMVP_E_INVALID, "kmvp_cell_lists: no product on cellmm_kernel / cellmm16_kernel has run on the current points");
+  memcpy(info, c->cell_list_info, sizeof c->cell_list_info);
+  if (!target_list) return KMVP_OK;
+  std::vector<int> slot((size_t)c->N);
+  HIP_TRY(c, hipMemcpyAsync(slot.data(), c->cell_slot.p, (size_t)c->N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const int64_t block_slots = (int64_t)c->cell_tt * WAVES_PER_BLOCK * CELL_TILE;
+  const int64_t main_end = info[0] * block_slots, tail_end = main_end + info[1] * block_slots;
+  for (int64_t i = 0; i < c->N; ++i) target_list[i] = slot[(size_t)i] < main_end ? 0 : (slot[(size_t)i] < tail_end ? 2 : 1);
   return KMVP_OK;
 }
 
