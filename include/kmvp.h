@@ -345,8 +345,9 @@ int kmvp_nearest(kmvp_ctx* ctx, int K, int exclude_self, int64_t* out_idx, doubl
  *    batch stands among them, alone (B = 1) and run to run.
  *  - everything else returns KMVP_E_UNSUPPORTED with a message that names the batches: kmvp_invdist[_norm] (its flat-index
  *    zero rule has no per-batch definition), kmvp_expdot[_norm], the gradients, the length-scale derivatives, the
- *    log-sum-exp and its gradient, the solvers, the Lanczos quadratures, Sinkhorn, k-means, mean-shift, and kmvp_nearest
- *    with exclude_self != 0.  So do the products and kmvp_nearest themselves on a bfloat16 context, at D > 8, with E > 4
+ *    log-sum-exp and its gradient, the solvers, the Lanczos quadratures, kmvp_<kernel>_sinkhorn, k-means, mean-shift, and
+ *    kmvp_nearest with exclude_self != 0.  Sinkhorn on batches has an entry of its own, kmvp_<kernel>_sinkhorn_batched (one
+ *    transport problem per batch); the plain entry keeps refusing.  So do the products and kmvp_nearest themselves on a bfloat16 context, at D > 8, with E > 4
  *    signal columns (normalised rows included: the denominator rides along as lowd_kernel's does), with an explicit
  *    "fast_sqdists" of 1 .. 4, with a communicator attached and on a source slice (M < M_total).
  *  - kmvp_last_kernel_name is "lowd_batch_kernel" or "lowd_batch_knn_kernel" (csrc/kmvp_lowd_batch.hpp: lowd_kernel's
@@ -560,6 +561,51 @@ int kmvp_gaussian_sinkhorn(kmvp_ctx* ctx, const double* log_a_or_null, const dou
                            double* u, double* v, int* iters, double* err);
 int kmvp_absexp_sinkhorn(kmvp_ctx* ctx, const double* log_a_or_null, const double* log_b_or_null, double tol, int maxit,
                          double* u, double* v, int* iters, double* err);
+
+/* Batched Sinkhorn (an extension: where the device-resident solvers and the batched clouds meet): one entropic transport
+ * problem per batch of kmvp_set_batches, all B of them in ONE device-resident solve -- a Sinkhorn loss on a minibatch of
+ * cloud pairs.  Called after kmvp_set_points and kmvp_set_batches.  Batch b is the problem between the targets
+ * [x_offsets[b], x_offsets[b + 1]) and the sources [y_offsets[b], y_offsets[b + 1]) with the cost, the temperature and the
+ * dimensionless potentials of kmvp_<kernel>_sinkhorn.
+ *     log_a (N), log_b (M)   log-weights, concatenated over the batches as the points are; NULL: uniform WITHIN each batch
+ *                            (-log n_b, -log m_b)
+ *     u (N, in: u_0, out), v (M, out)   concatenated likewise
+ *     iters, err, status     B values each
+ * Within every batch the iteration is exactly the one documented above (v_k = T2(u_{k-1}); ut = T1(v_k); err_k = sum over
+ * the batch's targets of a_i |exp(u_{k-1,i} - ut_i) - 1|; the commit u_k = ut only while the batch runs), and every batch has
+ * its own clock: it stops at the first k with err_b <= tol (status 1), on a non-finite potential or error of its own
+ * (status 2), or at k == maxit (status 3).  A stopped batch takes no further update: (u, v, iters[b], err[b]) of a batch
+ * ALWAYS describe one and the same plan -- (u_{k-1}, v_k) of the k at which it stopped.  A batch that is empty on both sides
+ * has iters 0, err 0, status 1.  The conventions of the plain entry hold per batch (points of mass 0, what makes a
+ * potential non-finite, fp64 potentials and log-weights rounded only into the signal slot of a record).
+ * Returns KMVP_OK if and only if every batch has status 1; otherwise KMVP_E_NOT_CONVERGED with everything written.
+ * Guarantees
+ *  - bitwise reproducible run to run: fixed summation order, no atomics.  A batch's error is the sum, in ascending order,
+ *    of its tiles' (64 targets') sums, each formed in a fixed tree.
+ *  - a batch's (u, v, iters, err, status) are bit for bit what this entry returns for that batch alone (B = 1), the same
+ *    wherever the batch stands among the others, whatever the others hold (batches that turn non-finite or run to maxit
+ *    included), whenever the others stop, and with "sinkhorn_retire" 0 or 1.
+ *  - bitwise equality with kmvp_<kernel>_sinkhorn on the same clouds is NOT promised: that entry folds at LDS tiles,
+ *    merges segments and sums its error per block of 256.  The two agree to the accumulation bound of the log-sum-exp.
+ *  - a product, batched product, kmvp_nearest, log-sum-exp or plain Sinkhorn on the same context returns the same bits
+ *    before and after a batched solve: both directions' layouts (target image of x with records of y; target image of y
+ *    with records of x, the batches' plan with the offsets swapped), the tile tables and the state live in buffers of the
+ *    solver's own, packed once per (kmvp_set_points, kmvp_set_batches).
+ * Per iteration: lowd_batch_lse_kernel twice (kmvp_last_kernel_name; csrc/kmvp_lowd_batch_lse.hpp: lowd_batch_kernel's
+ * scalar-cache feed with lowd_lse_kernel's arithmetic, one source range per wavefront, every row finished by its own lane),
+ * each with a finish kernel, then the per-batch verdicts, the commit and the retirement of stopped batches' tiles, all on
+ * the device; two doubles (batches still running, iteration count) cross to the host per iteration.
+ * kmvp_last_dispatch_note is "", kmvp_last_kernel_ms and kmvp_last_total_ms both cover the whole solve.  "chunk" is honoured;
+ * "segments", "feed" and "targets_per_lane" are accepted and ignored, as for the batched product: a batch is never cut into
+ * segments, so a batch with few targets and very many sources runs on few waves.
+ * KMVP_E_INVALID: batches are not set (the message names kmvp_set_batches), tol < 0 or NaN, maxit < 1, a NULL u, v, iters,
+ * err or status, a batch with points on one side only (the message names it).  KMVP_E_UNSUPPORTED, each with a message that
+ * names the batches: a bfloat16 context, D > 8, an explicit "fast_sqdists" of 1 .. 4, an attached communicator, a source
+ * slice (M < M_total). */
+int kmvp_gaussian_sinkhorn_batched(kmvp_ctx* ctx, const double* log_a_or_null, const double* log_b_or_null, double tol,
+                                   int maxit, double* u, double* v, int* iters, double* err, int* status);
+int kmvp_absexp_sinkhorn_batched(kmvp_ctx* ctx, const double* log_a_or_null, const double* log_b_or_null, double tol,
+                                 int maxit, double* u, double* v, int* iters, double* err, int* status);
 
 /* Regularised systems (an extension: no reference method stands behind it -- the reference's lstsq solves the bare
  * K b = a; this is the `alpha` / nugget / noise term of kernel ridge regression, Kriging and Gaussian processes).
@@ -793,6 +839,10 @@ int kmvp_comm_init_host(kmvp_ctx* ctx, kmvp_host_allreduce_fn fn, void* user, in
  *   "meanshift_compact" kmvp_gaussian_meanshift: -1 (default) and 1 = the list of active points is compacted after every
  *                      sweep, so the pair loop covers the points still moving; 0 = never, frozen points ride along and are
  *                      ignored.  The results are the same bit for bit either way: it exists to measure what compaction saves
+ *   "sinkhorn_retire"  kmvp_<kernel>_sinkhorn_batched: -1 (default) and 1 = the tiles of a stopped batch are retired (their source
+ *                      range set to empty), so the pair loop covers the batches still running; 0 = never, stopped batches ride
+ *                      along and are ignored.  The results are the same bit for bit either way: it exists to measure what
+ *                      retirement saves
  *   "mfma_variant"     bf16 path, software-pipelined kernel: -1 = by kernel (default: exp(-r) 4, others 0), 0 = plain,
  *                      1 = denominators on the matrix pipe (one more accumulator tile per target tile), 4 = loop rotated by one
  *                      transcendental stage, 5 = both (csrc/kmvp_mfma.hpp, mfma_pipe_kernel VAR) */

@@ -87,6 +87,8 @@ SYMBOLS = [
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_absexp_sinkhorn", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p,
                                         _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
+    ("kmvp_gaussian_sinkhorn_batched", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int] + [_c.c_void_p] * 5),
+    ("kmvp_absexp_sinkhorn_batched", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int] + [_c.c_void_p] * 5),
     ("kmvp_set_solver_diagonal", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_double]),
     ("kmvp_set_solver_preconditioner", _c.c_int, [_c.c_void_p, _c.c_int]),
     ("kmvp_get_solver_preconditioner", _c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int), _c.c_void_p, _c.c_void_p]),
@@ -181,6 +183,17 @@ def batch_offsets(offsets, what, total=None):
     return a
 
 
+def _vector(a, n, what):
+    """None, or ``a`` as n contiguous float64 values: the library reads n doubles from the pointer, so a shorter array
+    must never reach it."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != (n,):
+        raise ValueError(f"{what} has shape {a.shape}, expected ({n},)")
+    return a
+
+
 class Context:
     """Owns one kmvp_ctx (one GPU).  Thin, typed wrappers; all errors raise KmvpError."""
 
@@ -216,6 +229,7 @@ class Context:
         if x is not None and x.shape[1] != D:
             raise ValueError(f"target points have {x.shape[1]} coordinates, source points {D}")
         self.M, self.N, self.D = M, N, D
+        self.B = 0  # (kmvp_set_points switches the batches off)
         self._check(self._lib.kmvp_set_points(
             self._ctx, y.ctypes.data, M, None if x is None else x.ctypes.data, N, D, dtype_code_,
             int(j_offset), int(M if M_total is None else M_total)))
@@ -227,6 +241,7 @@ class Context:
             if x_offsets is not None:
                 raise ValueError("target offsets without source offsets")
             self._check(self._lib.kmvp_set_batches(self._ctx, 0, None, None))
+            self.B = 0
             return
         # the library reads B + 1 values from each pointer: arrays of another length must never reach it
         y_offsets = batch_offsets(y_offsets, "source_batches")
@@ -236,6 +251,7 @@ class Context:
                 raise ValueError(f"target_batches has {x_offsets.size} offsets, source_batches {y_offsets.size}: both hold B + 1")
         self._check(self._lib.kmvp_set_batches(self._ctx, y_offsets.size - 1, y_offsets.ctypes.data,
                                                None if x_offsets is None else x_offsets.ctypes.data))
+        self.B = y_offsets.size - 1  # (a refused call raised above and left the previous setting)
 
     def fit(self, kernel):
         self._check(self._lib.kmvp_fit(self._ctx, FIT_CODES[kernel]))
@@ -490,15 +506,7 @@ class Context:
         if entry is None:
             raise NotImplementedError(f"no Sinkhorn iteration for kernel {kernel}")
 
-        def vector(a, n, what):
-            # the library reads n doubles from the pointer: a shorter array must never reach it
-            if a is None:
-                return None
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.shape != (n,):
-                raise ValueError(f"{what} has shape {a.shape}, expected ({n},)")
-            return a
-
+        vector = _vector
         N, M = getattr(self, "N", 0), getattr(self, "M", 0)
         log_a, log_b = vector(log_a, N, "log_a"), vector(log_b, M, "log_b")
         u = np.zeros(N, dtype=np.float64) if u0 is None else vector(u0, N, "u0").copy()
@@ -510,6 +518,31 @@ class Context:
         if rc not in (0, 6):
             self._check(rc)
         return u, v, iters.value, err.value, rc == 0
+
+    def sinkhorn_batched(self, kernel, log_a, log_b, tol, maxit, u0=None):
+        """One Sinkhorn solve per batch of set_batches (include/kmvp.h kmvp_<kernel>_sinkhorn_batched): log_a (N) / log_b (M)
+        float64 log-weights concatenated over the batches or None (uniform within each batch), u0 (N) the starting
+        potential or None (zeros).  Returns (u, v, iterations, marginal errors, status) with B values in each of the
+        last three (status 1 converged, 2 non-finite, 3 maxit); raises on every return but OK and NOT_CONVERGED."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_sinkhorn_batched,
+            "absolute-exponential": self._lib.kmvp_absexp_sinkhorn_batched,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no Sinkhorn iteration for kernel {kernel}")
+        N, M, B = getattr(self, "N", 0), getattr(self, "M", 0), getattr(self, "B", 0)
+        # the library reads N (M) doubles from the pointers and writes B values: a shorter array must never reach it
+        log_a, log_b = _vector(log_a, N, "log_a"), _vector(log_b, M, "log_b")
+        u = np.zeros(N, dtype=np.float64) if u0 is None else _vector(u0, N, "u0").copy()
+        v = np.zeros(M, dtype=np.float64)
+        iters = np.zeros(max(B, 1), dtype=np.int32)
+        err = np.zeros(max(B, 1), dtype=np.float64)
+        status = np.zeros(max(B, 1), dtype=np.int32)
+        rc = entry(self._ctx, None if log_a is None else log_a.ctypes.data, None if log_b is None else log_b.ctypes.data,
+                   float(tol), int(maxit), u.ctypes.data, v.ctypes.data, iters.ctypes.data, err.ctypes.data, status.ctypes.data)
+        if rc not in (0, 6):
+            self._check(rc)
+        return u, v, iters[:B].astype(np.int64), err[:B], status[:B].astype(np.int64)
 
     def kmeans(self, C, centroids0, weights, tol, maxit):
         """Lloyd's k-means on the TARGETS of set_points (include/kmvp.h kmvp_kmeans): centroids0 (C, D) float64 initial

@@ -1034,7 +1034,14 @@ class MI355XSinkhorn:
     Same call order as MI355XSolver: prepare_data, fit, query, then get_potentials / dual_value / barycentric_map /
     get_additional, done.  The temperature is applied by scaling the points (by 1 / sqrt(eps) or 1 / eps); the library
     works on the dimensionless potentials u = f / eps, v = g / eps.  ``options``: device, segments, chunk, fast_sqdists
-    (only None / False run: the difference form)."""
+    (only None / False run: the difference form).
+
+    Batched clouds: prepare_data(..., source_batches=, target_batches=) takes B + 1 offsets into the concatenated sources
+    and targets, as MI355XProduct.prepare_data, and query() then solves one transport problem per batch in one
+    device-resident solve (kmvp_<kernel>_sinkhorn_batched; the pair loop is lowd_batch_lse_kernel).  Weights are
+    concatenated like the points and handled per batch (None: uniform within each batch; the masses are compared per
+    batch); get_potentials() returns the concatenated (f, g), dual_value() one value per batch, get_additional() per-batch
+    iterations, marginal_error and converged.  barycentric_map() is not built for batches."""
 
     def __init__(self, *, kernel, dimension, eps, precision=np.float32, tol=1e-6, maxit=1000, device=0, segments=0,
                  chunk=0, fast_sqdists=None):
@@ -1052,6 +1059,7 @@ class MI355XSinkhorn:
         # the points are multiplied by this before they are cast to the working precision
         self.scale = 1.0 / np.sqrt(self.eps) if kernel == "gaussian" else 1.0 / self.eps
         self._ctx = None
+        self._batches = None
         self.u = self.v = None
         self.iterations, self.marginal_error, self.converged = 0, float("nan"), False
         self.name = f"MI355XSinkhorn({_precision_name(precision)}, eps={self.eps:g})"
@@ -1069,7 +1077,8 @@ class MI355XSinkhorn:
             return w, np.log(w)  # a weight of 0 is a point of mass 0: log weight -inf
 
     # -- untimed -------------------------------------------------------------------
-    def prepare_data(self, *, source_points, target_points, same_points=False, source_weights=None, target_weights=None):
+    def prepare_data(self, *, source_points, target_points, same_points=False, source_weights=None, target_weights=None,
+                     source_batches=None, target_batches=None):
         self.same_points = bool(same_points)
         if source_points is None or (target_points is None and not self.same_points):
             raise ValueError("source_points and target_points are both needed (target_points may be None only with "
@@ -1086,11 +1095,24 @@ class MI355XSinkhorn:
             if x.ndim != 2 or x.shape[1] != self.D:
                 raise ValueError(f"target_points has shape {x.shape}, expected (N, {self.D})")
             self.N = x.shape[0]
+        self._batches = self._check_batches(source_batches, target_batches)
         self.b, self._log_b = self._log_weights(source_weights, self.M, "source_weights")
         self.a, self._log_a = self._log_weights(target_weights, self.N, "target_weights")
-        ma, mb = float(np.sum(self.a)), float(np.sum(self.b))
-        if not abs(ma - mb) <= SINKHORN_MASS_RTOL * max(ma, mb):
-            raise ValueError(f"the total masses differ: target_weights sum to {ma!r}, source_weights to {mb!r}")
+        if self._batches is None:
+            ma, mb = float(np.sum(self.a)), float(np.sum(self.b))
+            if not abs(ma - mb) <= SINKHORN_MASS_RTOL * max(ma, mb):
+                raise ValueError(f"the total masses differ: target_weights sum to {ma!r}, source_weights to {mb!r}")
+        else:
+            yb, xb = self._batches
+            for k in range(yb.size - 1):
+                # the unbatched rule within every batch: uniform weights sum to one, given ones are compared
+                if source_weights is None:
+                    self.b[yb[k]:yb[k + 1]] = 1.0 / max(int(yb[k + 1] - yb[k]), 1)
+                if target_weights is None:
+                    self.a[xb[k]:xb[k + 1]] = 1.0 / max(int(xb[k + 1] - xb[k]), 1)
+                ma, mb = float(np.sum(self.a[xb[k]:xb[k + 1]])), float(np.sum(self.b[yb[k]:yb[k + 1]]))
+                if not abs(ma - mb) <= SINKHORN_MASS_RTOL * max(ma, mb):
+                    raise ValueError(f"the total masses differ in batch {k}: target_weights sum to {ma!r}, source_weights to {mb!r}")
         self._y, self._x = y, (y if x is None else x)  # the scaled points as the device holds them
         if self._ctx is None:
             self._ctx = _lib.Context(self.device)
@@ -1101,7 +1123,27 @@ class MI355XSinkhorn:
                 code = {"centred": 2, "cells": 3, "cells-valu": 4}.get(self.fast_sqdists, int(bool(self.fast_sqdists)))
                 self._ctx.set_option("fast_sqdists", code)
         self._ctx.set_points(y, x, self._dtype_code)
+        if self._batches is not None:
+            self._ctx.set_batches(self._batches[0], None if self.same_points and target_batches is None else self._batches[1])
         self.u = self.v = None
+
+    def _check_batches(self, source_batches, target_batches):
+        """(source offsets, target offsets) of batched clouds, or None without batches; everything the host can decide is
+        refused here, before any device call."""
+        if source_batches is None and target_batches is None:
+            return None
+        if source_batches is None:
+            raise ValueError("target_batches needs source_batches")
+        if target_batches is None and not self.same_points:
+            raise ValueError("target_batches=None needs same_points=True (the sources' offsets then serve both)")
+        yb = _lib.batch_offsets(source_batches, "source_batches", self.M)
+        xb = yb if target_batches is None else _lib.batch_offsets(target_batches, "target_batches", self.N)
+        if xb.size != yb.size:
+            raise ValueError(f"target_batches has {xb.size} offsets, source_batches {yb.size}: both hold B + 1")
+        one_sided = np.nonzero((np.diff(yb) == 0) != (np.diff(xb) == 0))[0]
+        if one_sided.size:
+            raise ValueError(f"batch {int(one_sided[0])} has points on one side only")
+        return yb, xb
 
     # -- timed ---------------------------------------------------------------------
     def fit(self):
@@ -1112,6 +1154,11 @@ class MI355XSinkhorn:
         at a larger eps) or from zero.  Synchronous.  Not converged (maxit reached, or a non-finite potential) is a
         result, reported by get_additional()["converged"]; every other failure raises."""
         u0 = None if warm_start is None else np.asarray(warm_start, dtype=np.float64).reshape(-1) / self.eps
+        if self._batches is not None:  # one solve per batch: iterations, marginal_error and converged hold B values
+            self.u, self.v, self.iterations, self.marginal_error, status = self._ctx.sinkhorn_batched(
+                self.kernel, self._log_a, self._log_b, self.tol, self.maxit, u0)
+            self.converged = status == 1
+            return
         self.u, self.v, self.iterations, self.marginal_error, self.converged = self._ctx.sinkhorn(
             self.kernel, self._log_a, self._log_b, self.tol, self.maxit, u0)
 
@@ -1134,14 +1181,21 @@ class MI355XSinkhorn:
 
     def dual_value(self):
         """<a, f> + <b, g>: the dual objective at the returned potentials (the plan's mass term cancels when its
-        marginals are met)."""
+        marginals are met).  Batched clouds: an array of B values, one per batch."""
         f, g = self.get_potentials()
+        if self._batches is not None:
+            yb, xb = self._batches
+            return np.array([np.dot(self.a[xb[k]:xb[k + 1]], f[xb[k]:xb[k + 1]]) + np.dot(self.b[yb[k]:yb[k + 1]], g[yb[k]:yb[k + 1]])
+                             for k in range(yb.size - 1)], dtype=np.float64)
         return float(np.dot(self.a, f) + np.dot(self.b, g))
 
     def barycentric_map(self):
         """(N, D): sum_j pi_ij y_j / sum_j pi_ij in the caller's coordinates -- where the plan sends x_i on average.
         Gaussian only: G = grad_x L = -2 (x - barycentre) of the log-sum-exp with the signal v + log b
         (kmvp_gaussian_logsumexp_grad on the same context)."""
+        if self._batches is not None:
+            raise NotImplementedError("MI355XSinkhorn.barycentric_map is not built for batched clouds (the batched gradient of "
+                                      "the log-sum-exp is not built).")
         if self.kernel != "gaussian":
             raise NotImplementedError("MI355XSinkhorn.barycentric_map is built for kernel='gaussian' only.")
         self._need_solution("barycentric_map")
@@ -1155,7 +1209,11 @@ class MI355XSinkhorn:
         return 0.0 if self._ctx is None else self._ctx.device_bytes / 1024
 
     def get_additional(self):
-        extra = {"iterations": self.iterations, "marginal_error": self.marginal_error, "converged": bool(self.converged)}
+        if self._batches is not None:
+            extra = {"iterations": np.asarray(self.iterations), "marginal_error": np.asarray(self.marginal_error),
+                     "converged": np.asarray(self.converged, dtype=bool)}
+        else:
+            extra = {"iterations": self.iterations, "marginal_error": self.marginal_error, "converged": bool(self.converged)}
         if self._ctx is not None:
             extra.update(device_kernel_ms=self._ctx.last_kernel_ms, device_total_ms=self._ctx.last_total_ms,
                          device_kernel=self._ctx.last_kernel_name, device_bytes=self._ctx.device_bytes)

@@ -91,7 +91,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
                     &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     release(*b);
   for (int i = 0; i < 5; ++i)
@@ -322,6 +322,16 @@ int kmvp_absexp_sinkhorn(kmvp_ctx* c, const double* log_a, const double* log_b, 
   return sinkhorn_solve(c, K_ABSEXP, log_a, log_b, tol, maxit, u, v, iters, err);
 }
 
+// (not refused while batches are set: these entries are the batches' own Sinkhorn; kmvp_sinkhorn_batched.hip)
+int kmvp_gaussian_sinkhorn_batched(kmvp_ctx* c, const double* log_a, const double* log_b, double tol, int maxit, double* u,
+                                   double* v, int* iters, double* err, int* status) {
+  return sinkhorn_batched_solve(c, K_GAUSSIAN, log_a, log_b, tol, maxit, u, v, iters, err, status);
+}
+int kmvp_absexp_sinkhorn_batched(kmvp_ctx* c, const double* log_a, const double* log_b, double tol, int maxit, double* u,
+                                 double* v, int* iters, double* err, int* status) {
+  return sinkhorn_batched_solve(c, K_ABSEXP, log_a, log_b, tol, maxit, u, v, iters, err, status);
+}
+
 int kmvp_set_solver_diagonal(kmvp_ctx* c, const double* d, int64_t n, double ridge) {
   if (!c) return KMVP_E_INVALID;
   if (!std::isfinite(ridge)) return fail(c, KMVP_E_INVALID, "solver diagonal: ridge is not finite");
@@ -483,6 +493,9 @@ int kmvp_set_option(kmvp_ctx* c, const char* key, int64_t value) {
   } else if (k == "meanshift_compact") {
     if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "meanshift_compact must be -1 (default), 0 or 1");
     c->opt_meanshift_compact = (int)value;
+  } else if (k == "sinkhorn_retire") {
+    if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "sinkhorn_retire must be -1 (default), 0 or 1");
+    c->opt_sinkhorn_retire = (int)value;
   } else if (k == "chunk") {
     if (value < 8 || value > (1 << 24)) return fail(c, KMVP_E_INVALID, "chunk out of range");
     c->opt_chunk = (int)value;
@@ -497,7 +510,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
                           &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     t += b->cap;
   return (int64_t)t;

@@ -89,24 +89,6 @@ __global__ void batch_ones_kernel(const BatchTile* __restrict__ tiles, double* _
   if (l < t.live) out[t.i0 + l] = t.len > 0 ? 1.0 : __builtin_nan("");
 }
 
-// What the batched entries are not built for, beyond their own arguments; `what` opens the message.
-int batched_unsupported(kmvp_ctx* c, const std::string& what) {
-  const std::string tail = std::string(" (batched clouds, kmvp_set_batches)") + OFF_HINT;
-  if (c->dtype == KMVP_BF16)
-    return fail(c, KMVP_E_UNSUPPORTED, what + ": the batches are built for float32 and float64 contexts, not for bfloat16" + tail);
-  if (c->D > LOWD_MAX_D)
-    return fail(c, KMVP_E_UNSUPPORTED, what + ": D = " + std::to_string(c->D) + " is beyond the batches' kernels' D <= " +
-                                           std::to_string(LOWD_MAX_D) + tail);
-  if (c->opt_fast >= 1)
-    return fail(c, KMVP_E_UNSUPPORTED, what + ": fast_sqdists = " + std::to_string(c->opt_fast) +
-                                           " asks for a matrix-core form that is not built for the batches (-1 or 0: the difference form)" + tail);
-  if (c->exchanges())
-    return fail(c, KMVP_E_UNSUPPORTED, what + ": the batches are not built for a context with a communicator attached" + tail);
-  if (c->M < c->m_total)
-    return fail(c, KMVP_E_UNSUPPORTED, what + ": the batches are not built for a source slice (M < M_total)" + tail);
-  return KMVP_OK;
-}
-
 template <typename real>
 int run_product_batched_t(kmvp_ctx* c, int kernel, int sig) {
   const int D = c->D;
@@ -151,6 +133,24 @@ int run_nearest_batched_t(kmvp_ctx* c, int K, double* cand) {
 }
 
 }  // namespace
+
+// What the batched entries are not built for, beyond their own arguments; `what` opens the message.
+int batched_unsupported(kmvp_ctx* c, const std::string& what) {
+  const std::string tail = std::string(" (batched clouds, kmvp_set_batches)") + OFF_HINT;
+  if (c->dtype == KMVP_BF16)
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": the batches are built for float32 and float64 contexts, not for bfloat16" + tail);
+  if (c->D > LOWD_MAX_D)
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": D = " + std::to_string(c->D) + " is beyond the batches' kernels' D <= " +
+                                           std::to_string(LOWD_MAX_D) + tail);
+  if (c->opt_fast >= 1)
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": fast_sqdists = " + std::to_string(c->opt_fast) +
+                                           " asks for a matrix-core form that is not built for the batches (-1 or 0: the difference form)" + tail);
+  if (c->exchanges())
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": the batches are not built for a context with a communicator attached" + tail);
+  if (c->M < c->m_total)
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": the batches are not built for a source slice (M < M_total)" + tail);
+  return KMVP_OK;
+}
 
 int batches_refuse(kmvp_ctx* c, const char* what) {
   if (!c || !c->bt_on) return KMVP_OK;
@@ -200,6 +200,8 @@ int set_batches(kmvp_ctx* c, int B, const int64_t* y_off, const int64_t* x_off) 
   c->bt_n_pad = p.n_pad;
   c->bt_m_alloc = p.m_alloc;
   c->bt_B = B;
+  c->bt_y_off.assign(y_off, y_off + B + 1);
+  c->bt_x_off.assign(x_off, x_off + B + 1);
   ++c->bt_ver;
   c->bt_on = true;
   return KMVP_OK;

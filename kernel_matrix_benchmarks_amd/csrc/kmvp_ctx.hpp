@@ -170,6 +170,11 @@ struct kmvp_ctx {
   int bt_rec_R = 0;                                // bt_rec_R reals
   uint64_t bt_sig_ver = 0;      // signal version the records' signal slots hold (0: none), of
   int bt_sig_EB = -1;           // bt_sig_EB columns
+  std::vector<int64_t> bt_y_off, bt_x_off;  // the accepted offsets (B + 1 each): the batched Sinkhorn plans its second direction from them
+  // batched Sinkhorn (kmvp_sinkhorn_batched.hip): both directions' plans (tile tables in a pristine and a working copy,
+  // tile-to-batch maps, tile ranges, index maps), their target images and records, and the fp64 state
+  DevBuf skb_plan, skb_xs, skb_rec, skb_state;
+  uint64_t skb_points_ver = 0, skb_bt_ver = 0;  // points / plan version the layouts were built and packed from (0: none)
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
   int packed_layout = -1;  // LAYOUT_* of the path that owns xs / rec right now
@@ -193,7 +198,8 @@ struct kmvp_ctx {
   int64_t cell_list_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the lists of the last product on cellmm_kernel / cellmm16_kernel: kmvp_cell_lists
   int opt_mfma_variant = -1;              // bf16 path: VAR of mfma_pipe_kernel (kmvp_mfma.hpp); -1 = by kernel
   int opt_meanshift_compact = -1;         // mean-shift: -1 / 1 = the active list is compacted after every sweep, 0 = never (frozen lanes ride along)
-  int opt_same_global = 0;                // the targets ARE the (unsharded) sources although x was passed explicitly
+  int opt_sinkhorn_retire = -1;           // batched Sinkhorn: -1 / 1 = the tiles of stopped batches are retired (len = 0), 0 = never (stopped batches ride along)
+  int opt_same_global = 0;               // the targets ARE the (unsharded) sources although x was passed explicitly
   int opt_partial = 0;                    // a source slice (M < M_total) may run WITHOUT a communicator: the caller sums the shards
   uint64_t perm_ver = 0;                  // points version the Morton order belongs to
   uint64_t cell_ver = 0;                  // points version the cell structures belong to
@@ -360,6 +366,13 @@ int set_batches(kmvp_ctx* c, int B, const int64_t* y_offsets, const int64_t* x_o
 int run_product_batched(kmvp_ctx* c, int kernel, bool normalise);
 int run_nearest_batched(kmvp_ctx* c, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);
 int batches_refuse(kmvp_ctx* c, const char* what);
+// What the batched entries are not built for, beyond their own arguments (bfloat16, D > 8, an explicit fast_sqdists, a
+// communicator, a source slice): KMVP_E_UNSUPPORTED with a message that `what` opens, else KMVP_OK.
+int batched_unsupported(kmvp_ctx* c, const std::string& what);
+
+// kmvp_sinkhorn_batched.hip: kmvp_<kernel>_sinkhorn_batched, one Sinkhorn solve per batch on lowd_batch_lse_kernel
+int sinkhorn_batched_solve(kmvp_ctx* c, int kernel, const double* log_a, const double* log_b, double tol, int maxit, double* u,
+                           double* v, int* iters, double* err, int* status);
 
 // kmvp_meanshift.hip: kmvp_gaussian_meanshift, the device-resident mean-shift iteration on lowd_lse_grad_kernel
 int meanshift_solve(kmvp_ctx* c, double tol, int maxit, double* modes, int* iters, double* step2, int* sweeps,

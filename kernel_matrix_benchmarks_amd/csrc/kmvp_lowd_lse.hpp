@@ -71,6 +71,12 @@ __device__ __forceinline__ float lse_scale(float v, float d) { return ldexpf(v, 
 __device__ __forceinline__ double lse_scale(double v, float d) { return ldexp(v, (int)fmaxf(d, -300.0f)); }
 __device__ __forceinline__ double lse_scale(double v, double d) { return ldexp(v, (int)fmax(d, -4000.0)); }
 
+// The finished value from a sum at the scale 2^-k and its exponent k (the `kexp` convention above; k = -m):
+// (log2(sum) - k) ln 2, and exactly -inf for k = +inf (no live term).  finish_lse_kernel and lowd_batch_lse_kernel.
+__device__ __forceinline__ double lse_value(double sum, double k) {
+  return (k < 1.0e300) ? (log2(sum) - k) * 0.6931471805599453 : -(double)INFINITY;
+}
+
 // The logits u[e] of one (target, source) pair, in log2 units.
 template <int KERNEL, int D, int E, int SIG, typename real>
 __device__ __forceinline__ void lse_logits(const real (&x)[D], const real* __restrict__ r,

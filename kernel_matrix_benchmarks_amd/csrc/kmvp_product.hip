@@ -16,6 +16,7 @@
 #include "kmvp_fastmm_pack.hpp"
 #include "kmvp_cfastmm_pack.hpp"
 #include "kmvp_mfma_pack.hpp"
+#include "kmvp_lowd_lse.hpp"
 
 namespace kmvp {
 namespace {
@@ -637,7 +638,7 @@ __global__ void finish_lse_kernel(const double* __restrict__ sums, const double*
   if (q >= n * NC) return;
   const int64_t i = q / NC, e = q % NC;
   const double k = kshift[e * n_pad + i];
-  out[q] = (k < 1.0e300) ? (log2(sums[e * n_pad + i]) - k) * 0.6931471805599453 : -(double)INFINITY;
+  out[q] = lse_value(sums[e * n_pad + i], k);
 }
 
 // Tail of the log-sum-exp: c->sums / c->kshift hold [NC][n_pad] sums and exponents.  Sharded: the canonical unpadded layout
