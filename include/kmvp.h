@@ -360,6 +360,60 @@ int kmvp_nearest(kmvp_ctx* ctx, int K, int exclude_self, int64_t* out_idx, doubl
  * bookkeeping is not touched. */
 int kmvp_set_batches(kmvp_ctx* ctx, int B, const int64_t* y_offsets, const int64_t* x_offsets_or_null);
 
+/* Cutoff-radius products and neighbour counts on a cell list (an extension: short-range sums -- a Gaussian or Matern at a
+ * length scale far below the cloud's size, SPH and molecular sums, densities with a fixed support, DBSCAN's core-point
+ * counts, PyTorch3D's ball_query, KeOps' block-sparse ranges).  The caller knows a radius R beyond which a pair contributes
+ * nothing; the work is O(N * neighbours), not O(N * M).  For targets x (N,D), sources y (M,D) in the working precision
+ * `real`:
+ *     r2   = (real)(R * R), R * R formed in double
+ *     s_ij = the family's squared distance in the working precision: one subtraction, one square, D - 1 fmas (the value
+ *            kmvp_nearest compares)
+ *     the pair (i, j) is INSIDE iff s_ij <= r2: a pair at exactly r2 is inside, a NaN s is outside.
+ *   kmvp_<kernel>_cutoff(ctx, R, normalise)   a[i, e] = sum_{j inside} k(s_ij) b[j, e] for the Gaussian, exp(-r) and the two
+ *     Matern kernels, in the three signal modes of the plain product: the product, normalised rows (normalise != 0: divided
+ *     by sum_{j inside} k) and density estimation (kmvp_set_signal(NULL)).  Read with kmvp_get_result as (N, E) float64.
+ *     A target with no source inside gets 0, and NaN = 0 / 0 when normalised: the plain entry's M = 0 answer.  Normalised
+ *     density estimation is v / v -- 1 where a source is inside and the sum did not flush to 0, NaN otherwise -- and runs
+ *     the pair loop.
+ *   kmvp_radius_count(ctx, R, exclude_self, counts)   counts[i] (N int64, caller-owned) = the number of sources inside.
+ *     Needs kmvp_set_points only.  exclude_self != 0 is for targets == sources (x_or_null == NULL) only: a target whose
+ *     coordinates are all finite counts itself once and has 1 subtracted; duplicates of it still count.
+ *   kmvp_cutoff_info(ctx, out[8])   the plan the last of these calls ran on: [0], [1], [2] cells per axis (1 for unused
+ *     axes); [3] wave tiles of 64 target slots that own a target; [4] source runs of all tiles; [5] records walked, the sum
+ *     over the tiles of live lanes x the records of its runs; [6] padded source records; [7] host milliseconds the last
+ *     plan build took, rounded (the plan is cached: 0 builds since do not reset it).  KMVP_E_INVALID before any such call.
+ * Non-finite coordinates
+ *  - a source with a NaN or infinite coordinate is never inside;
+ *  - a target with an infinite coordinate has nothing inside: a row of 0 (NaN when normalised), count 0;
+ *  - a target with a NaN coordinate gets a NaN row (the family's rule) and count -1.  Neither disturbs any other row.
+ * Signals must be finite.  An outside pair that the walk meets is removed by setting k to 0 -- one select per pair -- and
+ * 0 * b is added: a non-finite b[j, e] therefore reaches column e of every row whose walk meets source j (its cell or a
+ * neighbouring one), inside the radius or not.
+ * How: both clouds are counting-sorted on the host into cells of side h = "cutoff_cell_factor" * R * (1 + 2^-16) -- larger
+ * where that would give more than 2^20 cells along an axis or more than 2 (N + M) cells -- and every wave tile of up to 64
+ * targets of one row of cells walks the records of the 3^(D-1) neighbouring rows between its first cell - 1 and its last
+ * cell + 1 (csrc/kmvp_cutoff_plan.hpp; kernels lowd_cutoff_kernel / lowd_cutoff_count_kernel, csrc/kmvp_lowd_cutoff.hpp:
+ * lowd_batch_kernel's scalar-cache feed with several source ranges per wavefront).  The plan is cached on (points, R,
+ * factor); target image, records, tables and maps live in buffers of the feature's own, so every other entry returns the
+ * same bits before and after these calls.  float32 sums fold into float64 every "chunk" walked records and at the end of
+ * every range; float64 keeps one chain.
+ *  - bitwise reproducible run to run for the same points, radius and options.  The products depend on the grid (hence on
+ *    "cutoff_cell_factor") in their float32 rounding: it decides where the chain is folded.  The counts do not.
+ *  - kmvp_last_kernel_name is "lowd_cutoff_kernel" / "lowd_cutoff_count_kernel"; kmvp_last_kernel_ms is the pair loop,
+ *    kmvp_last_total_ms includes the plan build's uploads and the packs.
+ * KMVP_E_INVALID: a radius that is not finite or not > 0, no points set, no signal set (the products), a NULL counts with
+ * N > 0, exclude_self when the targets are not the sources.  KMVP_E_UNSUPPORTED with a message that names the cutoff and
+ * the cause: D > 3, E > 4 signal columns, a bfloat16 context, an attached communicator, a source slice (M < M_total), and
+ * while batches are set (kmvp_set_batches).  float16 data: a float32 context of float16-rounded points, as everywhere.
+ * Not built: K nearest within a radius, gradients / log-sum-exp / solvers with a cutoff, compactly supported kernels,
+ * D > 3, source shards, batches combined with a cutoff, a device-side plan build, caller-supplied block-sparse ranges. */
+int kmvp_gaussian_cutoff(kmvp_ctx* ctx, double radius, int normalise);
+int kmvp_absexp_cutoff(kmvp_ctx* ctx, double radius, int normalise);
+int kmvp_matern32_cutoff(kmvp_ctx* ctx, double radius, int normalise);
+int kmvp_matern52_cutoff(kmvp_ctx* ctx, double radius, int normalise);
+int kmvp_radius_count(kmvp_ctx* ctx, double radius, int exclude_self, int64_t* counts);
+int kmvp_cutoff_info(kmvp_ctx* ctx, int64_t out[8]);
+
 /* Lloyd's k-means, resident on the device (an extension: the solver on top of the arg-K-min at K = 1, as the Krylov
  * solvers are on top of the product and Sinkhorn on top of the log-sum-exp).  Kernel-independent, like kmvp_nearest.  The
  * points are the TARGETS of the context -- x (N,D), or the cloud itself when x_or_null == NULL; the context's sources and
@@ -847,6 +901,11 @@ int kmvp_comm_init_host(kmvp_ctx* ctx, kmvp_host_allreduce_fn fn, void* user, in
  *                      1 = denominators on the matrix pipe (one more accumulator tile per target tile), 4 = loop rotated by one
  *                      transcendental stage, 5 = both (csrc/kmvp_mfma.hpp, mfma_pipe_kernel VAR) */
 int kmvp_set_option(kmvp_ctx* ctx, const char* key, int64_t value);
+/* Options whose value is a real number:
+ *   "cutoff_cell_factor"  the side of the cutoff entries' cells in units of the radius: a finite double >= 1, default 1.
+ *                      Larger cells are always correct (counts are identical, products agree to their float32 rounding)
+ *                      and walk more pairs: it is there to test and to measure */
+int kmvp_set_option_double(kmvp_ctx* ctx, const char* key, double value);
 
 /* BaseAlgorithm.get_memory_usage / get_additional (base.py:35-46): bytes of device
  * memory the ctx holds, and HIP-event timings of the last compute call:

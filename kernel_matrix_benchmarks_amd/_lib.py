@@ -56,6 +56,12 @@ SYMBOLS = [
     ("kmvp_absexp_logsumexp_grad", _c.c_int, [_c.c_void_p]),
     ("kmvp_nearest", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     ("kmvp_set_batches", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    ("kmvp_gaussian_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
+    ("kmvp_absexp_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
+    ("kmvp_matern32_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
+    ("kmvp_matern52_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
+    ("kmvp_radius_count", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p]),
+    ("kmvp_cutoff_info", _c.c_int, [_c.c_void_p, _c.c_void_p]),
     ("kmvp_kmeans", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
                                _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
     ("kmvp_gaussian_meanshift", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -100,6 +106,7 @@ SYMBOLS = [
     ("kmvp_comm_rank", _c.c_int, [_c.c_void_p]),
     ("kmvp_last_allreduce_ms", _c.c_double, [_c.c_void_p]),
     ("kmvp_set_option", _c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_int64]),
+    ("kmvp_set_option_double", _c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_double]),
     ("kmvp_device_bytes", _c.c_int64, [_c.c_void_p]),
     ("kmvp_last_kernel_ms", _c.c_double, [_c.c_void_p]),
     ("kmvp_last_total_ms", _c.c_double, [_c.c_void_p]),
@@ -114,6 +121,9 @@ HOST_ALLREDUCE_FN = _c.CFUNCTYPE(_c.c_int, _c.c_void_p, _c.POINTER(_c.c_double),
 OP_SUM, OP_MIN = 0, 1
 # kernel codes of kmvp_fit (include/kmvp.h)
 FIT_CODES = {"gaussian": 0, "absolute-exponential": 1, "inverse-distance": 2, "matern-3/2": 3, "matern-5/2": 4}
+
+# options whose value is a real number (include/kmvp.h kmvp_set_option_double)
+REAL_OPTIONS = ("cutoff_cell_factor",)
 
 # enum kmvp_eig_operator (include/kmvp.h)
 EIG_OPERATORS = {"kernel": 0, "centered": 1, "normalized": 2}
@@ -341,6 +351,35 @@ class Context:
         sqdist = np.empty((N, max(K, 0)), dtype=np.float64)
         self._check(self._lib.kmvp_nearest(self._ctx, K, 1 if exclude_self else 0, idx.ctypes.data, sqdist.ctypes.data))
         return idx, sqdist
+
+    def run_cutoff(self, kernel, radius, normalize_rows=False):
+        """The product over the sources within ``radius`` of every target (include/kmvp.h kmvp_<kernel>_cutoff): a pair is
+        inside iff its squared distance in the working precision is <= radius^2.  Read it with get_result(N, E)."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_cutoff,
+            "absolute-exponential": self._lib.kmvp_absexp_cutoff,
+            "matern-3/2": self._lib.kmvp_matern32_cutoff,
+            "matern-5/2": self._lib.kmvp_matern52_cutoff,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no cutoff-radius product for kernel {kernel}")
+        self._check(entry(self._ctx, float(radius), 1 if normalize_rows else 0))
+
+    def radius_count(self, radius, exclude_self=False):
+        """The number of sources within ``radius`` of every target (include/kmvp.h kmvp_radius_count): (N,) int64, -1 for a
+        target with a NaN coordinate.  exclude_self (targets = sources only) leaves a point's own pair out."""
+        # the library writes N values through the pointer: the array is sized here, from the points it was given
+        counts = np.zeros(int(getattr(self, "N", 0)), dtype=np.int64)
+        self._check(self._lib.kmvp_radius_count(self._ctx, float(radius), 1 if exclude_self else 0, counts.ctypes.data))
+        return counts
+
+    def cutoff_info(self):
+        """The plan of the last cutoff call (include/kmvp.h kmvp_cutoff_info): a dict of cells (3 per-axis counts),
+        tiles, runs, walked (records walked, summed over the tiles as live lanes x records), records (padded) and plan_ms."""
+        info = np.zeros(8, dtype=np.int64)
+        self._check(self._lib.kmvp_cutoff_info(self._ctx, info.ctypes.data))
+        return {"cells": tuple(int(v) for v in info[:3]), "tiles": int(info[3]), "runs": int(info[4]), "walked": int(info[5]),
+                "records": int(info[6]), "plan_ms": int(info[7])}
 
     def get_result(self, N, E):
         out = np.empty((N, E), dtype=np.float64)
@@ -663,6 +702,9 @@ class Context:
         return float(self._lib.kmvp_last_allreduce_ms(self._ctx))
 
     def set_option(self, key, value):
+        if key in REAL_OPTIONS:
+            self._check(self._lib.kmvp_set_option_double(self._ctx, key.encode(), float(value)))
+            return
         self._check(self._lib.kmvp_set_option(self._ctx, key.encode(), int(value)))
 
     @property

@@ -63,6 +63,8 @@ BATCHED_KERNELS = ("gaussian", "absolute-exponential", "matern-3/2", "matern-5/2
 LOGSUMEXP_MAX_D, LOGSUMEXP_MAX_E = 8, 4
 # lowd_knn_kernel: K nearest neighbours, at the gradient's dimensions; K + 1 candidates are collected with exclude_self
 NEAREST_MAX_D, NEAREST_MAX_K = 8, 16
+CUTOFF_KERNELS = BATCHED_KERNELS  # kmvp_<kernel>_cutoff
+CUTOFF_MAX_D = 3                  # the cutoff entries' cell list
 EXPDOT_NATIVE_MAX_D = 64
 EXPDOT_NATIVE_MAX_D_BF16 = 141  # 16 * 9 k-steps - 3 operand columns (kmvp_mfma.hpp MFMA_DOT_AUG)
 # largest spread max_j |y_j|^2/2 - min_j |y_j|^2/2 the identity route accepts: the smallest weight is exp(-spread);
@@ -455,6 +457,49 @@ class MI355XProduct(BaseProduct):
         """(idx (N, k) int64, sqdist (N, k) float64), C-contiguous: the result of the last query_nearest()."""
         return self._nearest
 
+    def _check_cutoff_supported(self, method):
+        """What the cutoff-radius entries are not built for, refused before the library is called."""
+        what = None
+        if self._ctx is None:
+            raise RuntimeError(f"{method}() needs prepare_data() first")
+        if self._dtype_code == _lib.KMVP_BF16:
+            what = "precision='bfloat16' (float16, float32 and float64 only)"
+        elif self._dot and not self._dot_native:
+            what = "kernel='exp-dot' through the Gaussian identity (the context holds rescaled points)"
+        elif self.D > CUTOFF_MAX_D:
+            what = f"D = {self.D} > {CUTOFF_MAX_D}"
+        elif self.comm is not None and self.comm.world > 1:
+            what = "sources sharded over ranks (comm=)"
+        if what is not None:
+            raise NotImplementedError(f"MI355XProduct.{method} doesn't support {what}.")
+
+    def query_cutoff(self, radius):
+        """The product over the sources within ``radius`` of every target (include/kmvp.h kmvp_<kernel>_cutoff), on a cell
+        list: O(N x neighbours) instead of O(N M).  A pair is inside iff its squared distance in the working precision is
+        <= radius^2; a target with nothing inside gets 0 (NaN with normalize_rows).  Honours normalize_rows and density
+        estimation; read the result with get_result().  The timed part, like query().  Synchronous."""
+        self._check_cutoff_supported("query_cutoff")
+        if self.kernel not in CUTOFF_KERNELS:
+            raise NotImplementedError(f"MI355XProduct.query_cutoff doesn't support kernel={self.kernel!r} (gaussian, "
+                                      "absolute-exponential, matern-3/2 and matern-5/2 only).")
+        self._ctx.run_cutoff(self.kernel, radius, self.normalize_rows)
+        self._cutoff_info = self._ctx.cutoff_info()
+        self.res = None
+
+    def query_radius_count(self, radius, exclude_self=False):
+        """The number of sources within ``radius`` of every target (include/kmvp.h kmvp_radius_count): DBSCAN's core-point
+        test, ball_query's lengths.  exclude_self (same_points only) leaves a point's own pair out.  Needs prepare_data()
+        only: no signal is read, and the plugin's kernel function does not enter.  Synchronous."""
+        self._check_cutoff_supported("query_radius_count")
+        if exclude_self and not self.same_points:
+            raise ValueError("exclude_self needs same_points=True")
+        self._radius_count = self._ctx.radius_count(radius, exclude_self)
+        self._cutoff_info = self._ctx.cutoff_info()
+
+    def get_radius_count(self):
+        """(N,) int64, -1 for a target with a NaN coordinate: the result of the last query_radius_count()."""
+        return self._radius_count
+
     # -- bookkeeping ---------------------------------------------------------------
     def set_query_arguments(self, **kwargs):
         for key, value in kwargs.items():
@@ -484,7 +529,7 @@ class MI355XProduct(BaseProduct):
     def get_additional(self):
         if self._ctx is None:
             return {}
-        return {
+        extra = {
             "device_kernel_ms": self._ctx.last_kernel_ms,
             "device_total_ms": self._ctx.last_total_ms,
             "device_kernel": self._ctx.last_kernel_name,
@@ -496,6 +541,9 @@ class MI355XProduct(BaseProduct):
             # "" or why a faster form was not taken (too few points per grid cell, the radius rule, ...)
             "dispatch_note": self._ctx.last_dispatch_note or getattr(self, "_dot_note", ""),
         }
+        if self._ctx.last_kernel_name.startswith("lowd_cutoff"):  # the cell-list plan of the last cutoff call
+            extra.update({"cutoff_" + key: value for key, value in getattr(self, "_cutoff_info", {}).items()})
+        return extra
 
     def done(self):
         if self._ctx is not None:

@@ -91,7 +91,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
                     &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state, &c->ct_tiles, &c->ct_runs, &c->ct_tmap, &c->ct_smap, &c->ct_xs, &c->ct_rec,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     release(*b);
   for (int i = 0; i < 5; ++i)
@@ -213,6 +213,12 @@ int kmvp_nearest(kmvp_ctx* c, int K, int exclude_self, int64_t* out_idx, double*
   if (batched(c)) return run_nearest_batched(c, K, exclude_self, out_idx, out_sqdist);
   return run_nearest(c, K, exclude_self, out_idx, out_sqdist);
 }
+int kmvp_gaussian_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_GAUSSIAN, radius, normalise != 0); }
+int kmvp_absexp_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_ABSEXP, radius, normalise != 0); }
+int kmvp_matern32_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_MATERN32, radius, normalise != 0); }
+int kmvp_matern52_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_MATERN52, radius, normalise != 0); }
+int kmvp_radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts) { return radius_count(c, radius, exclude_self, counts); }
+int kmvp_cutoff_info(kmvp_ctx* c, int64_t* out) { return cutoff_info(c, out); }
 int kmvp_kmeans(kmvp_ctx* c, int C, const double* weights, double tol, int maxit, double* centroids, int64_t* labels,
                 double* cluster_weight, int* iters, double* inertia, double* shift) {
   KMVP_NOT_BATCHED(c, "k-means");
@@ -505,12 +511,24 @@ int kmvp_set_option(kmvp_ctx* c, const char* key, int64_t value) {
   return KMVP_OK;
 }
 
+int kmvp_set_option_double(kmvp_ctx* c, const char* key, double value) {
+  if (!c || !key) return KMVP_E_INVALID;
+  const std::string k(key);
+  if (k == "cutoff_cell_factor") {
+    if (!(value >= 1.0) || !std::isfinite(value)) return fail(c, KMVP_E_INVALID, "cutoff_cell_factor must be a finite number >= 1");
+    c->opt_cutoff_factor = value;
+  } else {
+    return fail(c, KMVP_E_INVALID, "unknown real-valued option " + k);
+  }
+  return KMVP_OK;
+}
+
 int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   if (!c) return 0;
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
                           &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state, &c->ct_tiles, &c->ct_runs, &c->ct_tmap, &c->ct_smap, &c->ct_xs, &c->ct_rec,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     t += b->cap;
   return (int64_t)t;

@@ -9,6 +9,7 @@
 //   kmvp_meanshift.hip Gaussian mean-shift on the gradient of the log-sum-exp
 //   kmvp_batch.hip    batched clouds: block-diagonal products and nearest neighbours on layouts of their own
 //   kmvp_precond.hip  the pivoted-Cholesky preconditioner of conjugate gradients: build, apply, read-back
+//   kmvp_cutoff.hip   cutoff-radius products and neighbour counts on a cell list, on layouts of their own
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -175,6 +176,19 @@ struct kmvp_ctx {
   // tile-to-batch maps, tile ranges, index maps), their target images and records, and the fp64 state
   DevBuf skb_plan, skb_xs, skb_rec, skb_state;
   uint64_t skb_points_ver = 0, skb_bt_ver = 0;  // points / plan version the layouts were built and packed from (0: none)
+  // cutoff radius (kmvp_<kernel>_cutoff, kmvp_radius_count; kmvp_cutoff.hip): the cell-list plan's tile and run tables and
+  // its two index maps, and layouts of their own -- the target image over the padded slots and the source records
+  DevBuf ct_tiles, ct_runs, ct_tmap, ct_smap, ct_xs, ct_rec;
+  double opt_cutoff_factor = 1.0;  // "cutoff_cell_factor": the cells' side in units of the radius (>= 1)
+  uint64_t ct_ver = 0;             // counts the plans built
+  uint64_t ct_plan_points_ver = 0, ct_radius_bits = 0;  // what the plan in ct_* was built for (ct_plan_points_ver 0: none),
+  double ct_factor = 0.0;                               // with this factor
+  int64_t ct_n_pad = 0, ct_m_alloc = 0;  // target slots and records of the plan
+  uint64_t ct_xs_ver = 0, ct_rec_ver = 0;  // plan version ct_xs / the coordinates in ct_rec were packed from (0: none), the
+  int ct_rec_R = 0;                        // records laid out for ct_rec_R reals
+  uint64_t ct_sig_ver = 0;      // signal version the records' signal slots hold (0: none), of
+  int ct_sig_EB = -1;           // ct_sig_EB columns
+  int64_t ct_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kmvp_cutoff_info
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
   int packed_layout = -1;  // LAYOUT_* of the path that owns xs / rec right now
@@ -373,6 +387,12 @@ int batched_unsupported(kmvp_ctx* c, const std::string& what);
 // kmvp_sinkhorn_batched.hip: kmvp_<kernel>_sinkhorn_batched, one Sinkhorn solve per batch on lowd_batch_lse_kernel
 int sinkhorn_batched_solve(kmvp_ctx* c, int kernel, const double* log_a, const double* log_b, double tol, int maxit, double* u,
                            double* v, int* iters, double* err, int* status);
+
+// kmvp_cutoff.hip: kmvp_<kernel>_cutoff, kmvp_radius_count and kmvp_cutoff_info -- the cell-list plan
+// (kmvp_cutoff_plan.hpp), the gather-packed layouts, lowd_cutoff_kernel / lowd_cutoff_count_kernel
+int run_cutoff(kmvp_ctx* c, int kernel, double radius, bool normalise);
+int radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts);
+int cutoff_info(kmvp_ctx* c, int64_t* out);
 
 // kmvp_meanshift.hip: kmvp_gaussian_meanshift, the device-resident mean-shift iteration on lowd_lse_grad_kernel
 int meanshift_solve(kmvp_ctx* c, double tol, int maxit, double* modes, int* iters, double* step2, int* sweeps,

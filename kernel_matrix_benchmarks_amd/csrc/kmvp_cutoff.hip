@@ -1,0 +1,272 @@
+// Cutoff-radius products and neighbour counts (include/kmvp.h kmvp_<kernel>_cutoff, kmvp_radius_count, kmvp_cutoff_info).
+//   cutoff_prepare   copies the points back, widens them exactly to double, builds the cell-list plan
+//                    (kmvp_cutoff_plan.hpp) and uploads its two tables and two maps -- once per (points, radius, factor)
+//   pack_cutoff      the gather-packs of the batched clouds (kmvp_lowd_batch.hpp) through the plan's maps
+//   run_cutoff       the truncated product on lowd_cutoff_kernel
+//   radius_count     the neighbour counts on lowd_cutoff_count_kernel
+// Target image, records, tables and maps live in buffers of their own (ct_*): the product's pack bookkeeping
+// (points_stale, record_packed), its xs / rec buffers and the batches' bt_* are never touched, so every other entry
+// returns the same bits whatever ran in between.  The coordinates are packed once per plan and record length; a new
+// signal rewrites the records' signal slots only.
+#include <chrono>
+
+#include "kmvp_ctx.hpp"
+#include "kmvp_lowd_batch.hpp"
+#include "kmvp_lowd_cutoff.hpp"
+
+namespace kmvp {
+
+namespace {
+
+// What the cutoff entries are not built for, beyond their own arguments; `what` opens the message.
+int cutoff_unsupported(kmvp_ctx* c, const std::string& what) {
+  const std::string tail = " (cutoff radius: kmvp_<kernel>_cutoff, kmvp_radius_count)";
+  if (c->dtype == KMVP_BF16)
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": the cutoff is built for float32 and float64 contexts, not for bfloat16" + tail);
+  if (c->D > CUTOFF_MAX_D)
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": D = " + std::to_string(c->D) + " is beyond the cutoff's cell list, D <= " +
+                                           std::to_string(CUTOFF_MAX_D) + tail);
+  if (c->exchanges())
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": the cutoff is not built for a context with a communicator attached" + tail);
+  if (c->M < c->m_total)
+    return fail(c, KMVP_E_UNSUPPORTED, what + ": the cutoff is not built for a source slice (M < M_total)" + tail);
+  return batches_refuse(c, (what + " with a cutoff radius").c_str());
+}
+
+template <typename real>
+void widen(const std::vector<real>& in, std::vector<double>& out) {
+  out.resize(in.size());
+  for (size_t i = 0; i < in.size(); ++i) out[i] = (double)in[i];
+}
+
+// The plan for (points, radius, factor), built and uploaded unless the context holds it.
+template <typename real>
+int cutoff_prepare(kmvp_ctx* c, double radius) {
+  uint64_t bits;
+  memcpy(&bits, &radius, sizeof(bits));
+  if (c->ct_plan_points_ver == c->points_ver && c->ct_radius_bits == bits && c->ct_factor == c->opt_cutoff_factor) return KMVP_OK;
+  const int D = c->D;
+  std::vector<real> yh((size_t)c->M * D), xh(c->same_points ? 0 : (size_t)c->N * D);
+  if (!yh.empty()) HIP_TRY(c, hipMemcpyAsync(yh.data(), c->y_raw.p, yh.size() * sizeof(real), hipMemcpyDeviceToHost, c->stream));
+  if (!xh.empty()) HIP_TRY(c, hipMemcpyAsync(xh.data(), c->x_raw.p, xh.size() * sizeof(real), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<double> yd, xd;
+  widen(yh, yd);
+  widen(xh, xd);
+  CutoffPlan p;
+  if (!cutoff_plan_build(yd.data(), c->M, c->same_points ? yd.data() : xd.data(), c->N, D, radius, c->opt_cutoff_factor, p))
+    return fail(c, KMVP_E_UNSUPPORTED, "cutoff radius: 2^31 sources or more (the pair loop counts positions within a run in 32 bits)");
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (p.n_pad / (CUTOFF_TILE * CUTOFF_WAVES) > MAX_GRID) return fail(c, KMVP_E_UNSUPPORTED, "cutoff radius: launch grid too large");
+  c->ct_plan_points_ver = 0;  // (a device failure from here on leaves no plan behind)
+  int rc;
+  if ((rc = ensure(c, c->ct_tiles, p.tiles.size() * sizeof(CutoffTile)))) return rc;
+  if ((rc = ensure(c, c->ct_runs, p.runs.size() * sizeof(CutoffRun)))) return rc;
+  if ((rc = ensure(c, c->ct_tmap, p.tmap.size() * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(c, c->ct_smap, p.smap.size() * sizeof(int64_t)))) return rc;
+  if (!p.tiles.empty())
+    HIP_TRY(c, hipMemcpyAsync(c->ct_tiles.p, p.tiles.data(), p.tiles.size() * sizeof(CutoffTile), hipMemcpyHostToDevice, c->stream));
+  if (!p.runs.empty())
+    HIP_TRY(c, hipMemcpyAsync(c->ct_runs.p, p.runs.data(), p.runs.size() * sizeof(CutoffRun), hipMemcpyHostToDevice, c->stream));
+  if (!p.tmap.empty())
+    HIP_TRY(c, hipMemcpyAsync(c->ct_tmap.p, p.tmap.data(), p.tmap.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->ct_smap.p, p.smap.data(), p.smap.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the plan's vectors are only read during the call
+  c->ct_n_pad = p.n_pad;
+  c->ct_m_alloc = p.m_alloc;
+  const int64_t info[8] = {p.g[0], p.g[1], p.g[2], p.live_tiles, (int64_t)p.runs.size(), p.walked, p.m_pad, (int64_t)std::llround(ms)};
+  memcpy(c->ct_info, info, sizeof(info));
+  ++c->ct_ver;
+  c->ct_plan_points_ver = c->points_ver;
+  c->ct_radius_bits = bits;
+  c->ct_factor = c->opt_cutoff_factor;
+  return KMVP_OK;
+}
+
+// Packs whatever of the cutoff layouts is stale for records of R reals with EB signal columns (0: the density layout).
+template <typename real>
+int pack_cutoff(kmvp_ctx* c, int R, int EB) {
+  const int D = c->D;
+  int rc;
+  const real* x_raw = (const real*)(c->same_points ? c->y_raw.p : c->x_raw.p);
+  if (c->ct_xs_ver != c->ct_ver) {
+    if ((rc = ensure(c, c->ct_xs, (size_t)D * c->ct_n_pad * sizeof(real)))) return rc;
+    if (c->ct_n_pad > 0) {
+      hipLaunchKernelGGL((batch_pack_targets_kernel<real>), dim3(blocks_for(c->ct_n_pad)), dim3(256), 0, c->stream, x_raw,
+                         (const int64_t*)c->ct_tmap.p, (real*)c->ct_xs.p, c->ct_n_pad, D);
+      HIP_TRY(c, hipGetLastError());
+    }
+    c->ct_xs_ver = c->ct_ver;
+  }
+  if (c->ct_rec_ver != c->ct_ver || c->ct_rec_R != R) {
+    if ((rc = ensure(c, c->ct_rec, (size_t)c->ct_m_alloc * R * sizeof(real)))) return rc;
+    hipLaunchKernelGGL((batch_pack_sources_kernel<real>), dim3(blocks_for(c->ct_m_alloc)), dim3(256), 0, c->stream,
+                       (const real*)c->y_raw.p, (const int64_t*)c->ct_smap.p, (real*)c->ct_rec.p, c->ct_m_alloc, D, R);
+    HIP_TRY(c, hipGetLastError());
+    c->ct_rec_ver = c->ct_ver;
+    c->ct_rec_R = R;
+    c->ct_sig_ver = 0;  // the signal slots were zeroed
+    c->ct_sig_EB = 0;
+  }
+  if (EB > 0 && (c->ct_sig_ver != c->signal_ver || c->ct_sig_EB != EB)) {
+    hipLaunchKernelGGL((batch_pack_signal_kernel<real>), dim3(blocks_for(c->ct_m_alloc)), dim3(256), 0, c->stream,
+                       (const real*)c->b_raw.p, (const int64_t*)c->ct_smap.p, (real*)c->ct_rec.p, c->ct_m_alloc, D, EB, R);
+    HIP_TRY(c, hipGetLastError());
+    c->ct_sig_ver = c->signal_ver;
+    c->ct_sig_EB = EB;
+  }
+  return KMVP_OK;
+}
+
+template <typename real>
+LowdCutoffArgs<real> cutoff_args(const kmvp_ctx* c, double radius) {
+  LowdCutoffArgs<real> a;
+  a.xs = (const real*)c->ct_xs.p;
+  a.rec = (const real*)c->ct_rec.p;
+  a.tiles = (const CutoffTile*)c->ct_tiles.p;
+  a.runs = (const CutoffRun*)c->ct_runs.p;
+  a.tmap = (const int64_t*)c->ct_tmap.p;
+  a.out = nullptr;
+  a.counts = nullptr;
+  a.n_pad = c->ct_n_pad;
+  a.r2 = (real)(radius * radius);
+  a.chunk = (int)round_up(c->opt_chunk > 8 ? c->opt_chunk : 8, LOWD_BATCH);  // lowd_geometry's rule
+  a.self_norm = 0;
+  a.exclude_self = 0;
+  return a;
+}
+
+inline hipError_t launch_cutoff(int kernel, int D, int E, int sig, const LowdCutoffArgs<float>& a, dim3 grid, hipStream_t s,
+                                const char** name) {
+  return launch_lowd_cutoff_f32(kernel, D, E, sig, a, grid, s, name);
+}
+inline hipError_t launch_cutoff(int kernel, int D, int E, int sig, const LowdCutoffArgs<double>& a, dim3 grid, hipStream_t s,
+                                const char** name) {
+  return launch_lowd_cutoff_f64(kernel, D, E, sig, a, grid, s, name);
+}
+inline hipError_t launch_cutoff_count(int D, const LowdCutoffArgs<float>& a, dim3 grid, hipStream_t s, const char** name) {
+  return launch_lowd_cutoff_count_f32(D, a, grid, s, name);
+}
+inline hipError_t launch_cutoff_count(int D, const LowdCutoffArgs<double>& a, dim3 grid, hipStream_t s, const char** name) {
+  return launch_lowd_cutoff_count_f64(D, a, grid, s, name);
+}
+
+template <typename real>
+int run_cutoff_t(kmvp_ctx* c, int kernel, double radius, bool normalise) {
+  const int D = c->D;
+  const int sig = c->density ? SIG_DENSITY : (normalise ? SIG_NORM : SIG_PRODUCT);
+  const int E = c->density ? 1 : c->E;
+  const int EB = c->density ? 0 : E;
+  const int R = (D + EB + 3) / 4 * 4;
+  int rc;
+  HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
+  if ((rc = cutoff_prepare<real>(c, radius))) return rc;
+  if ((rc = pack_cutoff<real>(c, R, EB))) return rc;
+  if ((rc = ensure(c, c->out, (size_t)c->N * E * sizeof(double)))) return rc;
+  LowdCutoffArgs<real> a = cutoff_args<real>(c, radius);
+  a.out = (double*)c->out.p;
+  a.self_norm = c->density && normalise;
+  HIP_TRY(c, hipEventRecord(c->ev[3], c->stream));
+  hipError_t le = launch_cutoff(kernel, D, E, sig, a, dim3((unsigned)(c->ct_n_pad / (CUTOFF_TILE * CUTOFF_WAVES))), c->stream,
+                                &c->last_kernel_name);
+  if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "cutoff radius: no kernel instantiated for this (kernel, D, E)");
+  HIP_TRY(c, le);
+  HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_kernel_ms, c->ev[3], c->ev[1]));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
+  c->out_n = c->N;
+  c->out_e = E;
+  return KMVP_OK;
+}
+
+template <typename real>
+int radius_count_t(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts) {
+  const int D = c->D;
+  const int R = (D + 3) / 4 * 4;  // density layout: no signal columns
+  int rc;
+  HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
+  if ((rc = cutoff_prepare<real>(c, radius))) return rc;
+  if ((rc = pack_cutoff<real>(c, R, 0))) return rc;
+  // counts in c->knn: scratch of the context that no entry expects to survive a call
+  if ((rc = ensure(c, c->knn, (size_t)c->N * sizeof(int64_t)))) return rc;
+  LowdCutoffArgs<real> a = cutoff_args<real>(c, radius);
+  a.counts = (int64_t*)c->knn.p;
+  a.exclude_self = exclude_self != 0;
+  HIP_TRY(c, hipEventRecord(c->ev[3], c->stream));
+  hipError_t le = launch_cutoff_count(D, a, dim3((unsigned)(c->ct_n_pad / (CUTOFF_TILE * CUTOFF_WAVES))), c->stream, &c->last_kernel_name);
+  if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "cutoff radius: no count kernel instantiated for this D");
+  HIP_TRY(c, le);
+  HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
+  HIP_TRY(c, hipMemcpyAsync(counts, c->knn.p, (size_t)c->N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_kernel_ms, c->ev[3], c->ev[1]));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
+  return KMVP_OK;
+}
+
+int radius_checked(kmvp_ctx* c, double radius) {
+  if (!std::isfinite(radius) || !(radius > 0.0)) return fail(c, KMVP_E_INVALID, "cutoff radius: the radius must be finite and > 0");
+  return KMVP_OK;
+}
+
+}  // namespace
+
+int run_cutoff(kmvp_ctx* c, int kernel, double radius, bool normalise) {
+  if (!c) return KMVP_E_INVALID;
+  c->note.clear();
+  int rc;
+  if ((rc = radius_checked(c, radius))) return rc;
+  if (!c->have_points) return fail(c, KMVP_E_INVALID, "cutoff radius: kmvp_set_points has not been called");
+  if (!c->have_signal) return fail(c, KMVP_E_INVALID, "cutoff radius: kmvp_set_signal has not been called");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = cutoff_unsupported(c, "product"))) return rc;
+  const int E = c->density ? 1 : c->E;
+  if (E > LOWD_MAX_E)
+    return fail(c, KMVP_E_UNSUPPORTED, "product: E = " + std::to_string(E) + " signal columns are beyond the cutoff's kernels' E <= " +
+                                           std::to_string(LOWD_MAX_E) + " (cutoff radius: run it per block of columns)");
+  c->last_kernel_ms = c->last_total_ms = c->last_allreduce_ms = 0.f;
+  if (c->N == 0) {
+    if ((rc = c->dtype == KMVP_F64 ? cutoff_prepare<double>(c, radius) : cutoff_prepare<float>(c, radius))) return rc;
+    if ((rc = ensure(c, c->out, 16))) return rc;
+    c->out_n = 0;
+    c->out_e = E;
+    c->last_kernel_name = "none";
+    return KMVP_OK;
+  }
+  return c->dtype == KMVP_F64 ? run_cutoff_t<double>(c, kernel, radius, normalise) : run_cutoff_t<float>(c, kernel, radius, normalise);
+}
+
+int radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts) {
+  if (!c) return KMVP_E_INVALID;
+  c->note.clear();
+  int rc;
+  if ((rc = radius_checked(c, radius))) return rc;
+  if (!c->have_points) return fail(c, KMVP_E_INVALID, "cutoff radius: kmvp_set_points has not been called");
+  if (exclude_self && !c->same_points)
+    return fail(c, KMVP_E_INVALID, "cutoff radius: exclude_self needs the targets to be the sources (x == NULL at kmvp_set_points)");
+  if (c->N > 0 && !counts) return fail(c, KMVP_E_INVALID, "cutoff radius: a NULL output");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = cutoff_unsupported(c, "neighbour count"))) return rc;
+  c->last_kernel_ms = c->last_total_ms = c->last_allreduce_ms = 0.f;
+  if (c->N == 0) {
+    if ((rc = c->dtype == KMVP_F64 ? cutoff_prepare<double>(c, radius) : cutoff_prepare<float>(c, radius))) return rc;
+    c->last_kernel_name = "none";
+    return KMVP_OK;
+  }
+  return c->dtype == KMVP_F64 ? radius_count_t<double>(c, radius, exclude_self, counts)
+                              : radius_count_t<float>(c, radius, exclude_self, counts);
+}
+
+int cutoff_info(kmvp_ctx* c, int64_t* out) {
+  if (!c) return KMVP_E_INVALID;
+  if (!out) return fail(c, KMVP_E_INVALID, "cutoff radius: a NULL output");
+  if (c->ct_ver == 0) return fail(c, KMVP_E_INVALID, "cutoff radius: no cutoff call has built a plan on this context");
+  memcpy(out, c->ct_info, sizeof(c->ct_info));
+  return KMVP_OK;
+}
+
+}  // namespace kmvp
