@@ -85,7 +85,7 @@ int kmvp_set_points(kmvp_ctx* ctx, const void* y, int64_t M, const void* x_or_nu
  * there, timed as build_time).  Nothing of the matrix is ever built here; what CAN be built from the
  * points alone is: for the Gaussian on clouds that qualify for the cell form (fast_sqdists 3 / auto),
  * the grid, the cell order (radix sort) and the tile lists.  kernel: 0 gaussian, 1 absexp, 2 invdist, 3 matern32,
- * 4 matern52 (accepted; nothing is built for them).
+ * 4 matern52, 7 wendland_c2, 8 wendland_c4 (3, 4, 7, 8: accepted, nothing is built for them; 5 and 6 are not codes).
  * Optional: the first query does the same work when fit was not called. */
 int kmvp_fit(kmvp_ctx* ctx, int kernel);
 
@@ -405,14 +405,50 @@ int kmvp_set_batches(kmvp_ctx* ctx, int B, const int64_t* y_offsets, const int64
  * N > 0, exclude_self when the targets are not the sources.  KMVP_E_UNSUPPORTED with a message that names the cutoff and
  * the cause: D > 3, E > 4 signal columns, a bfloat16 context, an attached communicator, a source slice (M < M_total), and
  * while batches are set (kmvp_set_batches).  float16 data: a float32 context of float16-rounded points, as everywhere.
- * Not built: K nearest within a radius, gradients / log-sum-exp / solvers with a cutoff, compactly supported kernels,
- * D > 3, source shards, batches combined with a cutoff, a device-side plan build, caller-supplied block-sparse ranges. */
+ * Not built: K nearest within a radius, gradients / log-sum-exp with a cutoff, solvers with a cutoff for the four
+ * truncated kernels (a truncated Gaussian or Matern matrix is in general not positive definite), D > 3, source shards,
+ * batches combined with a cutoff, a device-side plan build, caller-supplied block-sparse ranges. */
 int kmvp_gaussian_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_absexp_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_matern32_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_matern52_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_radius_count(kmvp_ctx* ctx, double radius, int exclude_self, int64_t* counts);
 int kmvp_cutoff_info(kmvp_ctx* ctx, int64_t out[8]);
+
+/* Wendland's compactly supported kernels (an extension: the reference has none) -- the cutoff WITHOUT a truncation error,
+ * and the library's first sparse operator for conjugate gradients.  With the support radius R, t = |x - y| / R and
+ * u = max(1 - t, 0):
+ *     wendland_c2   k = u^4 (4 t + 1)                    C^2, positive definite on R^D for D <= 3
+ *     wendland_c4   k = u^6 (35 t^2 + 18 t + 3) / 3      C^4, positive definite on R^D for D <= 3
+ * k(0) = 1 and k vanishes identically from t = 1 on, so the sum over the sources inside R IS the full product: there is no
+ * plain (all-pairs) entry.  kmvp_fit accepts the kernel codes 7 (C2) and 8 (C4) and builds nothing.
+ * Arithmetic per pair in the working precision `real` (csrc/kmvp_lowd_cutoff.hpp), after the cutoff's own s and r2:
+ *     q = s * iR2, iR2 = (real)(1 / (R R)) formed in double;  t = sqrt(q), the square root exp(-r) uses in this precision;
+ *     u = max(1 - t, 0);  u2 = u u;  C2: k = (u2 u2) fma(4, t, 1);  C4: k = ((u2 u2) u2) fma(t, fma(t, 35/3, 6), 1);
+ *     k = s <= r2 ? k : 0.
+ * k is continuous and 0 at t = 1: a pair that rounding puts on the other side of s <= r2 changes a sum by O(u^4), of the
+ * order of (D 2^-24)^4 resp. (D 2^-53)^4 -- these kernels need no "inside set" in their definition.
+ *   kmvp_wendland_<c>_cutoff(ctx, R, normalise)   every mode, convention, refusal and non-finite rule of
+ *     kmvp_<kernel>_cutoff above (product, normalised rows, density, kmvp_cutoff_info, the plan cache on (points, R, factor));
+ *     kmvp_last_kernel_name is "lowd_cutoff_kernel".
+ *   kmvp_wendland_<c>_cg_solve(ctx, R, a, E, rtol, maxit, out_b, iters, resid)   (K + the solver's diagonal) b = a on the cloud
+ *     given with x_or_null == NULL: kmvp_<kernel>_cg_solve's driver, stop test, residual replacement, graph replay, verdict
+ *     and outputs (see there), with the cutoff product as the operator.  Before the first iteration the plan is built (or
+ *     found cached) and the target image and the source coordinates are packed; every application of the operator is two
+ *     launches -- the E signal slots of the records written in the working precision straight from the float64 Krylov
+ *     vector, and the pair loop.  kmvp_set_solver_diagonal (ridge, per point) is honoured.  The cutoff's buffers stay its
+ *     own: every other entry returns the same bits before and after.  No signal is left behind (as after every solve).
+ *     KMVP_E_INVALID: a bad radius, targets that are not the sources, the solver's own argument checks.
+ *     KMVP_E_UNSUPPORTED, naming the cause: E > 4, whatever kmvp_<kernel>_cutoff refuses (D > 3, bfloat16, a communicator,
+ *     a source slice, batches), and a preconditioner of rank > 0 (its column kernel knows no Wendland function).
+ * Not built: MINRES, the Lanczos quadrature, eigsh, the preconditioner, gradients, source shards and batches with these
+ * kernels. */
+int kmvp_wendland_c2_cutoff(kmvp_ctx* ctx, double radius, int normalise);
+int kmvp_wendland_c4_cutoff(kmvp_ctx* ctx, double radius, int normalise);
+int kmvp_wendland_c2_cg_solve(kmvp_ctx* ctx, double radius, const void* a, int E, double rtol, int maxit, double* out_b,
+                              int* iters, double* resid);
+int kmvp_wendland_c4_cg_solve(kmvp_ctx* ctx, double radius, const void* a, int E, double rtol, int maxit, double* out_b,
+                              int* iters, double* resid);
 
 /* Lloyd's k-means, resident on the device (an extension: the solver on top of the arg-K-min at K = 1, as the Krylov
  * solvers are on top of the product and Sinkhorn on top of the log-sum-exp).  Kernel-independent, like kmvp_nearest.  The

@@ -60,6 +60,8 @@ SYMBOLS = [
     ("kmvp_absexp_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
     ("kmvp_matern32_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
     ("kmvp_matern52_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
+    ("kmvp_wendland_c2_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
+    ("kmvp_wendland_c4_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
     ("kmvp_radius_count", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p]),
     ("kmvp_cutoff_info", _c.c_int, [_c.c_void_p, _c.c_void_p]),
     ("kmvp_kmeans", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
@@ -75,6 +77,10 @@ SYMBOLS = [
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_matern52_cg_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                           _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
+    ("kmvp_wendland_c2_cg_solve", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
+                                             _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
+    ("kmvp_wendland_c4_cg_solve", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
+                                             _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_invdist_minres_solve", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int,
                                              _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     ("kmvp_gaussian_lanczos_quadrature", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_int] + [_c.c_void_p] * 6),
@@ -120,7 +126,10 @@ SYMBOLS = [
 HOST_ALLREDUCE_FN = _c.CFUNCTYPE(_c.c_int, _c.c_void_p, _c.POINTER(_c.c_double), _c.c_int64, _c.c_int)
 OP_SUM, OP_MIN = 0, 1
 # kernel codes of kmvp_fit (include/kmvp.h)
-FIT_CODES = {"gaussian": 0, "absolute-exponential": 1, "inverse-distance": 2, "matern-3/2": 3, "matern-5/2": 4}
+FIT_CODES = {"gaussian": 0, "absolute-exponential": 1, "inverse-distance": 2, "matern-3/2": 3, "matern-5/2": 4,
+             "wendland-c2": 7, "wendland-c4": 8}
+# Wendland's compactly supported kernels (include/kmvp.h kmvp_wendland_<c>_cutoff): the cutoff entries and a CG solve only
+WENDLAND = ("wendland-c2", "wendland-c4")
 
 # options whose value is a real number (include/kmvp.h kmvp_set_option_double)
 REAL_OPTIONS = ("cutoff_cell_factor",)
@@ -277,6 +286,8 @@ class Context:
             self._check(self._lib.kmvp_set_signal(self._ctx, b.ctypes.data, b.shape[1]))
 
     def run(self, kernel, normalize_rows):
+        if kernel in WENDLAND:
+            raise NotImplementedError(f"kernel {kernel} has no plain (all-pairs) product: its support is the radius, use run_cutoff")
         entry = {
             ("gaussian", False): self._lib.kmvp_gaussian,
             ("gaussian", True): self._lib.kmvp_gaussian_norm,
@@ -360,6 +371,8 @@ class Context:
             "absolute-exponential": self._lib.kmvp_absexp_cutoff,
             "matern-3/2": self._lib.kmvp_matern32_cutoff,
             "matern-5/2": self._lib.kmvp_matern52_cutoff,
+            "wendland-c2": self._lib.kmvp_wendland_c2_cutoff,
+            "wendland-c4": self._lib.kmvp_wendland_c4_cutoff,
         }.get(kernel)
         if entry is None:
             raise NotImplementedError(f"no cutoff-radius product for kernel {kernel}")
@@ -386,16 +399,22 @@ class Context:
         self._check(self._lib.kmvp_get_result(self._ctx, out.ctypes.data, out.size))
         return out
 
-    def cg_solve(self, kernel, a, rtol, maxit):
+    def cg_solve(self, kernel, a, rtol, maxit, support_radius=None):
+        """``support_radius``: the Wendland kernels' support radius (include/kmvp.h kmvp_wendland_<c>_cg_solve) -- required
+        for them, refused for every other kernel."""
         if a.ndim != 2 or a.shape[0] != getattr(self, "N", a.shape[0]):
             # the Krylov vectors have one row per point (all points are targets); the library reads N * E elements
             raise ValueError(f"target_signal has shape {a.shape}, the point cloud has {self.N} points")
+        if (kernel in WENDLAND) != (support_radius is not None):
+            raise ValueError(f"kernel {kernel}: support_radius is required for the Wendland kernels and refused for the others")
         entry = {
             "gaussian": self._lib.kmvp_gaussian_cg_solve,
             "absolute-exponential": self._lib.kmvp_absexp_cg_solve,
             "inverse-distance": self._lib.kmvp_invdist_minres_solve,  # indefinite: MINRES
             "matern-3/2": self._lib.kmvp_matern32_cg_solve,
             "matern-5/2": self._lib.kmvp_matern52_cg_solve,
+            "wendland-c2": self._lib.kmvp_wendland_c2_cg_solve,
+            "wendland-c4": self._lib.kmvp_wendland_c4_cg_solve,
         }.get(kernel)
         if entry is None:
             raise NotImplementedError(f"no solver for kernel {kernel}")
@@ -403,7 +422,8 @@ class Context:
         out = np.empty((M, E), dtype=np.float64)
         iters = ctypes.c_int(0)
         resid = ctypes.c_double(0.0)
-        rc = entry(self._ctx, a.ctypes.data, E, float(rtol), int(maxit), out.ctypes.data,
+        head = (self._ctx,) if support_radius is None else (self._ctx, float(support_radius))
+        rc = entry(*head, a.ctypes.data, E, float(rtol), int(maxit), out.ctypes.data,
                    ctypes.byref(iters), ctypes.byref(resid))
         if rc not in (0, 6):
             self._check(rc)

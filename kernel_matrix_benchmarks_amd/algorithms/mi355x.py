@@ -38,6 +38,12 @@ SUPPORTED_KERNELS = ("gaussian", "absolute-exponential", "inverse-distance", "ex
 # definition (the tests' matern_reference).  float16 / float32 / float64, difference form only: bfloat16 and an
 # explicit fast_sqdists are refused.
 MATERN_KERNELS = ("matern-3/2", "matern-5/2")
+# "wendland-c2", "wendland-c4": Wendland's compactly supported functions u^4 (4 t + 1) and u^6 (35 t^2 + 18 t + 3) / 3 of
+# t = |x - y| / R, u = max(1 - t, 0): positive definite for D <= 3, identically 0 beyond the support radius R.  An
+# extension -- the reference has no such kernel.  The support radius is an argument of the call, so the product runs
+# through MI355XProduct.query_cutoff(R) alone (it IS the full product) and the solve through
+# MI355XSolver(support_radius=R); float16 / float32 / float64, D <= 3.
+WENDLAND_KERNELS = ("wendland-c2", "wendland-c4")
 # "exp-dot": k(x, y) = exp(<x, y>), the transformer attention kernel the reference's README defines
 # (README.md:51-59) but its plugins do not implement (bruteforce.py:18-22 has the other three): parity
 # unpinned, checked against a direct numpy evaluation only (the tests' exp_dot_product).  Two routes:
@@ -100,7 +106,7 @@ class MI355XProduct(BaseProduct):
                  chunk=0, fast_tiles=0):
         super().__init__(kernel=kernel, dimension=dimension, normalize_rows=normalize_rows,
                          precision=precision)
-        if kernel not in SUPPORTED_KERNELS:
+        if kernel not in SUPPORTED_KERNELS + WENDLAND_KERNELS:
             # same failure mode as bruteforce.py:82-85
             raise NotImplementedError(f"MI355XProduct doesn't support kernel {kernel}.")
         self._dot = kernel == "exp-dot"
@@ -121,6 +127,13 @@ class MI355XProduct(BaseProduct):
         # None lets the library pick the cheapest form that is as accurate as the difference form.
         if fast_sqdists not in (None, False, True, "centred", "cells", "cells-valu"):
             raise ValueError("fast_sqdists must be None, False, True, 'centred', 'cells' or 'cells-valu'")
+        if kernel in WENDLAND_KERNELS:
+            if self._dtype_code == _lib.KMVP_BF16:
+                raise NotImplementedError(f"MI355XProduct doesn't support kernel {kernel} with precision='bfloat16' "
+                                          "(float16, float32 and float64 only).")
+            if fast_sqdists not in (None, False):
+                raise NotImplementedError(f"MI355XProduct doesn't support kernel {kernel} with fast_sqdists={fast_sqdists!r}: "
+                                          "the Wendland kernels run through query_cutoff alone (None or False).")
         if kernel in MATERN_KERNELS:
             # what the library has no kernel for (it would answer KMVP_E_UNSUPPORTED), refused before it is called
             if self._dtype_code == _lib.KMVP_BF16:
@@ -315,7 +328,14 @@ class MI355XProduct(BaseProduct):
         if not self._dot_native:  # (the native exp(<x,y>) path has nothing the points alone determine)
             self._ctx.fit(self._device_kernel_fn)
 
+    def _refuse_wendland(self, method):
+        """The Wendland kernels live in query_cutoff(R) alone: R is their support, and the call's argument."""
+        if self.kernel in WENDLAND_KERNELS:
+            raise NotImplementedError(f"MI355XProduct.{method} doesn't support kernel={self.kernel!r}: the kernel vanishes beyond "
+                                      "its support radius, which is an argument of query_cutoff(radius) -- use query_cutoff.")
+
     def query(self):
+        self._refuse_wendland("query")
         # synchronous: the device (and the all-reduce) is done when this returns
         self._ctx.run(self._device_kernel_fn, self.normalize_rows and (self._dot_native or not self._dot))
         self.res = None  # the result stays on the device until get_result()
@@ -323,6 +343,7 @@ class MI355XProduct(BaseProduct):
     def query_gradient(self):
         """G[i, e, :] = grad_{x_i} sum_j k(x_i, y_j) b[j, e] (include/kmvp.h kmvp_<kernel>_grad): the timed part, like
         query().  The targets are independent variables, also with same_points.  Synchronous."""
+        self._refuse_wendland("query_gradient")
         self._check_gradient_supported()
         self._ctx.run_grad(self.kernel)
         self.res = None
@@ -352,6 +373,7 @@ class MI355XProduct(BaseProduct):
         kmvp_<kernel>_dscale): -w (x_{i,d} - y_{j,d})^2 with the gradient's weight w.  The length scales are the caller's
         scaling of the points; H.sum(axis=2) is the derivative in one isotropic length scale.  The timed part, like
         query().  Synchronous."""
+        self._refuse_wendland("query_scale_derivative")
         self._check_scale_derivative_supported()
         self._ctx.run_dscale(self.kernel)
         self.res = None
@@ -384,6 +406,7 @@ class MI355XProduct(BaseProduct):
         with the array given to prepare_query(source_signal=c) read as LOG-weights (density estimation: c = 0; c = -inf:
         weight 0); include/kmvp.h kmvp_<kernel>_logsumexp.  A temperature is the caller's scaling of the points and of
         c.  The timed part, like query().  Synchronous."""
+        self._refuse_wendland("query_logsumexp")
         self._check_logsumexp_supported()
         self._ctx.run_lse(self.kernel)
         self.res = None
@@ -416,6 +439,7 @@ class MI355XProduct(BaseProduct):
         prepare_query(source_signal=c) read as LOG-weights; include/kmvp.h kmvp_<kernel>_logsumexp_grad.  The targets
         are independent variables, also with same_points.  A (row, column) without a live term is NaN.  The timed part,
         like query().  Synchronous."""
+        self._refuse_wendland("query_logsumexp_gradient")
         self._check_logsumexp_supported("query_logsumexp_gradient")
         self._ctx.run_lse_grad(self.kernel)
         self.res = None
@@ -476,12 +500,12 @@ class MI355XProduct(BaseProduct):
     def query_cutoff(self, radius):
         """The product over the sources within ``radius`` of every target (include/kmvp.h kmvp_<kernel>_cutoff), on a cell
         list: O(N x neighbours) instead of O(N M).  A pair is inside iff its squared distance in the working precision is
-        <= radius^2; a target with nothing inside gets 0 (NaN with normalize_rows).  Honours normalize_rows and density
-        estimation; read the result with get_result().  The timed part, like query().  Synchronous."""
+        <= radius^2; a target with nothing inside gets 0 (NaN with normalize_rows).  For kernel="wendland-c2" / "wendland-c4"
+        ``radius`` is the support radius and nothing is truncated.  Honours normalize_rows and density estimation; read the result with get_result().  The timed part, like query().  Synchronous."""
         self._check_cutoff_supported("query_cutoff")
-        if self.kernel not in CUTOFF_KERNELS:
+        if self.kernel not in CUTOFF_KERNELS + WENDLAND_KERNELS:
             raise NotImplementedError(f"MI355XProduct.query_cutoff doesn't support kernel={self.kernel!r} (gaussian, "
-                                      "absolute-exponential, matern-3/2 and matern-5/2 only).")
+                                      "absolute-exponential, matern-3/2, matern-5/2, wendland-c2 and wendland-c4 only).")
         self._ctx.run_cutoff(self.kernel, radius, self.normalize_rows)
         self._cutoff_info = self._ctx.cutoff_info()
         self.res = None
@@ -630,11 +654,24 @@ class MI355XSolver(BaseSolver):
 
     def __init__(self, *, kernel, dimension, normalize_rows=False, precision=np.float64,
                  device=0, rtol=1e-6, maxit=10000, comm=None, refine=None, inner_rtol=1e-3, ridge=0.0,
-                 preconditioner_rank=0):
+                 preconditioner_rank=0, support_radius=None):
         super().__init__(kernel=kernel, dimension=dimension, normalize_rows=normalize_rows,
                          precision=precision)
-        if kernel not in SUPPORTED_KERNELS:
+        if kernel not in SUPPORTED_KERNELS + WENDLAND_KERNELS:
             raise NotImplementedError(f"MI355XSolver doesn't support kernel {kernel}.")
+        # kernel="wendland-c2" / "wendland-c4" (an extension): the sparse operator of kmvp_wendland_<c>_cg_solve, O(M x
+        # neighbours) per iteration; support_radius is the R of t = |x - y| / R
+        self._wendland = kernel in WENDLAND_KERNELS
+        if self._wendland:
+            if support_radius is None or not (np.isfinite(support_radius) and support_radius > 0):
+                raise ValueError(f"MI355XSolver(kernel={kernel!r}) needs support_radius, a finite number > 0")
+            what = ("refine" if refine else "comm (a sharded operator)" if comm is not None else
+                    "preconditioner_rank > 0 (the preconditioner knows no Wendland kernel)" if int(preconditioner_rank) > 0 else None)
+            if what:
+                raise NotImplementedError(f"MI355XSolver doesn't support kernel {kernel} with {what}.")
+        elif support_radius is not None:
+            raise ValueError(f"support_radius is for the Wendland kernels only, not for kernel {kernel}")
+        self.support_radius = None if support_radius is None else float(support_radius)
         # refine="float32" (float64 solves only, an extension: the reference has one dense lstsq): mixed-precision
         # iterative refinement -- the residual a - K x is formed with the FLOAT64 operator, the correction K d = r is
         # solved to `inner_rtol` by CG on the FLOAT32 operator (the matrix-core cell form: ~10x cheaper per product),
@@ -675,7 +712,7 @@ class MI355XSolver(BaseSolver):
         rank = int(rank)
         if rank < 0:
             raise ValueError("preconditioner_rank must be >= 0")
-        if rank > 0 and (self.method != "cg" or self._dot or self.refine):
+        if rank > 0 and (self.method != "cg" or self._dot or self.refine or self._wendland):
             what = "refine" if self.refine else f"kernel {self.kernel}"
             raise NotImplementedError(f"MI355XSolver(preconditioner_rank > 0) doesn't support {what}.")
         self.preconditioner_rank = rank
@@ -829,8 +866,9 @@ class MI355XSolver(BaseSolver):
         if self.refine:
             self._query_refined()
         else:
+            extra = dict(support_radius=self.support_radius) if self._wendland else {}
             self.res, self.iterations, self.residual, self.converged = self._ctx.cg_solve(
-                self._device_kernel_fn, self._a, self.rtol, self.maxit)
+                self._device_kernel_fn, self._a, self.rtol, self.maxit, **extra)
         if self._dot:
             # The iteration ran on the SCALED system G z = D^-1 a (z = D b, D = diag(exp(|x|^2/2))); where D varies a lot
             # its residual says little about K b = a.  The verdict is therefore taken on the unscaled system, from one
@@ -921,7 +959,7 @@ class MI355XSolver(BaseSolver):
         pivoted-Cholesky preconditioner and M = P^-1/2 A P^-1/2 (include/kmvp.h kmvp_<kernel>_lanczos_quadrature_precond).
         ``value`` is the exact log det P plus the mean of the per-probe w' log(M) w, ``stderr`` the latter's alone;
         ``trace_inverse`` from (P^-1 z)' A^-1 z.  Fewer iterations and a smaller standard error than without."""
-        what = (f"kernel {self.kernel}" if self.method != "cg" or self._dot else "refine" if self.refine else
+        what = (f"kernel {self.kernel}" if self.method != "cg" or self._dot or self._wendland else "refine" if self.refine else
                 "normalize_rows" if self.normalize_rows else None)
         if what:
             raise NotImplementedError(f"MI355XSolver.log_determinant doesn't support {what}.")
@@ -989,7 +1027,7 @@ class MI355XSolver(BaseSolver):
     def _likelihood_gradient_pieces(self, probes, seed, preconditioned=False):
         """The device's share of log_marginal_likelihood_gradient(): what assemble_likelihood_gradient() takes beside a and
         alpha, as a dict."""
-        what = (f"kernel {self.kernel}" if self.method != "cg" or self._dot else "refine" if self.refine else
+        what = (f"kernel {self.kernel}" if self.method != "cg" or self._dot or self._wendland else "refine" if self.refine else
                 "normalize_rows" if self.normalize_rows else None)
         if what:
             raise NotImplementedError(f"MI355XSolver.log_marginal_likelihood_gradient doesn't support {what}.")

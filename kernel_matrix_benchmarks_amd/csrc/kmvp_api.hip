@@ -146,8 +146,11 @@ int kmvp_set_points(kmvp_ctx* c, const void* y, int64_t M, const void* x_or_null
 int kmvp_fit(kmvp_ctx* c, int kernel) {
   if (!c) return KMVP_E_INVALID;
   if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
-  if (kernel < 0 || kernel > 4) return fail(c, KMVP_E_INVALID, "kernel must be 0, 1, 2, 3 or 4");
-  if (kernel > 2) return KMVP_OK;  // Matern 3/2, 5/2: the difference form has nothing the points alone determine
+  // 7, 8: Wendland C2, C4 (5 and 6 stay refused, as before these kernels existed)
+  if (kernel < 0 || kernel > 8 || kernel == 5 || kernel == 6) return fail(c, KMVP_E_INVALID, "kernel must be 0, 1, 2, 3, 4, 7 or 8");
+  // Matern 3/2, 5/2: the difference form has nothing the points alone determine; Wendland C2, C4: the cutoff's plan needs
+  // the radius as well
+  if (kernel > 2) return KMVP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   return prepare_points(c, kernel);
 }
@@ -217,6 +220,8 @@ int kmvp_gaussian_cutoff(kmvp_ctx* c, double radius, int normalise) { return run
 int kmvp_absexp_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_ABSEXP, radius, normalise != 0); }
 int kmvp_matern32_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_MATERN32, radius, normalise != 0); }
 int kmvp_matern52_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_MATERN52, radius, normalise != 0); }
+int kmvp_wendland_c2_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_WENDLAND_C2, radius, normalise != 0); }
+int kmvp_wendland_c4_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_WENDLAND_C4, radius, normalise != 0); }
 int kmvp_radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts) { return radius_count(c, radius, exclude_self, counts); }
 int kmvp_cutoff_info(kmvp_ctx* c, int64_t* out) { return cutoff_info(c, out); }
 int kmvp_kmeans(kmvp_ctx* c, int C, const double* weights, double tol, int maxit, double* centroids, int64_t* labels,
@@ -262,6 +267,15 @@ int kmvp_matern52_cg_solve(kmvp_ctx* c, const void* a, int E, double rtol, int m
                            int* iters, double* resid) {
   KMVP_NOT_BATCHED(c, "the solver");
   return cg_solve(c, K_MATERN52, a, E, rtol, maxit, out_b, iters, resid);
+}
+
+int kmvp_wendland_c2_cg_solve(kmvp_ctx* c, double radius, const void* a, int E, double rtol, int maxit, double* out_b, int* iters,
+                              double* resid) {
+  return wendland_cg_solve(c, K_WENDLAND_C2, radius, a, E, rtol, maxit, out_b, iters, resid);
+}
+int kmvp_wendland_c4_cg_solve(kmvp_ctx* c, double radius, const void* a, int E, double rtol, int maxit, double* out_b, int* iters,
+                              double* resid) {
+  return wendland_cg_solve(c, K_WENDLAND_C4, radius, a, E, rtol, maxit, out_b, iters, resid);
 }
 
 int kmvp_invdist_minres_solve(kmvp_ctx* c, const void* a, int E, double rtol, int maxit, double* out_b,

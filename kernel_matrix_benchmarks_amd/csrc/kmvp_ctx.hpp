@@ -189,6 +189,7 @@ struct kmvp_ctx {
   uint64_t ct_sig_ver = 0;      // signal version the records' signal slots hold (0: none), of
   int ct_sig_EB = -1;           // ct_sig_EB columns
   int64_t ct_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kmvp_cutoff_info
+  double ct_solve_radius = 0.0;  // kmvp_wendland_<c>_cg_solve: the support radius cg_apply's operator runs at (0: no such solve is running)
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
   int packed_layout = -1;  // LAYOUT_* of the path that owns xs / rec right now
@@ -393,6 +394,12 @@ int sinkhorn_batched_solve(kmvp_ctx* c, int kernel, const double* log_a, const d
 int run_cutoff(kmvp_ctx* c, int kernel, double radius, bool normalise);
 int radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts);
 int cutoff_info(kmvp_ctx* c, int64_t* out);
+// kmvp_wendland_<c>_cg_solve: the checks, the plan and the packed layouts, then cg_solve with cutoff_apply as its operator
+int wendland_cg_solve(kmvp_ctx* c, int kernel, double radius, const void* a_host, int E, double rtol, int maxit, double* out_b,
+                      int* iters, double* resid);
+// cg_apply's operator for the Wendland kernels: the E signal slots of the records straight from the float64 (M, E) vector v,
+// then the pair loop into c->out -- two launches.  While c->async_product is set: no event, no synchronisation, no host check.
+int cutoff_apply(kmvp_ctx* c, int kernel, const double* v, int E);
 
 // kmvp_meanshift.hip: kmvp_gaussian_meanshift, the device-resident mean-shift iteration on lowd_lse_grad_kernel
 int meanshift_solve(kmvp_ctx* c, double tol, int maxit, double* modes, int* iters, double* step2, int* sweeps,

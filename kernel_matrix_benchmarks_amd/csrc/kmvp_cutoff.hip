@@ -4,6 +4,8 @@
 //   pack_cutoff      the gather-packs of the batched clouds (kmvp_lowd_batch.hpp) through the plan's maps
 //   run_cutoff       the truncated product on lowd_cutoff_kernel
 //   radius_count     the neighbour counts on lowd_cutoff_count_kernel
+//   wendland_cg_solve / cutoff_apply   conjugate gradients (kmvp_solvers.hip cg_solve) with the Wendland cutoff product as
+//                    its operator: plan and packs once, then two launches per application
 // Target image, records, tables and maps live in buffers of their own (ct_*): the product's pack bookkeeping
 // (points_stale, record_packed), its xs / rec buffers and the batches' bt_* are never touched, so every other entry
 // returns the same bits whatever ran in between.  The coordinates are packed once per plan and record length; a new
@@ -134,16 +136,19 @@ LowdCutoffArgs<real> cutoff_args(const kmvp_ctx* c, double radius) {
   a.chunk = (int)round_up(c->opt_chunk > 8 ? c->opt_chunk : 8, LOWD_BATCH);  // lowd_geometry's rule
   a.self_norm = 0;
   a.exclude_self = 0;
+  a.iR2 = (real)(1.0 / (radius * radius));
   return a;
 }
 
 inline hipError_t launch_cutoff(int kernel, int D, int E, int sig, const LowdCutoffArgs<float>& a, dim3 grid, hipStream_t s,
                                 const char** name) {
-  return launch_lowd_cutoff_f32(kernel, D, E, sig, a, grid, s, name);
+  return is_wendland(kernel) ? launch_lowd_wendland_f32(kernel, D, E, sig, a, grid, s, name)
+                             : launch_lowd_cutoff_f32(kernel, D, E, sig, a, grid, s, name);
 }
 inline hipError_t launch_cutoff(int kernel, int D, int E, int sig, const LowdCutoffArgs<double>& a, dim3 grid, hipStream_t s,
                                 const char** name) {
-  return launch_lowd_cutoff_f64(kernel, D, E, sig, a, grid, s, name);
+  return is_wendland(kernel) ? launch_lowd_wendland_f64(kernel, D, E, sig, a, grid, s, name)
+                             : launch_lowd_cutoff_f64(kernel, D, E, sig, a, grid, s, name);
 }
 inline hipError_t launch_cutoff_count(int D, const LowdCutoffArgs<float>& a, dim3 grid, hipStream_t s, const char** name) {
   return launch_lowd_cutoff_count_f32(D, a, grid, s, name);
@@ -213,6 +218,59 @@ int radius_checked(kmvp_ctx* c, double radius) {
   return KMVP_OK;
 }
 
+// The solver's signal: the EB signal slots of the records in the working precision straight from the float64 (M, EB) vector
+// v through the plan's map, nothing else; pad records keep b = 0.  (cg_cast_kernel + batch_pack_signal_kernel in one.)
+template <typename real>
+__global__ void cutoff_signal_f64_kernel(const double* __restrict__ v, const int64_t* __restrict__ smap, real* __restrict__ rec,
+                                         int64_t m_alloc, int D, int EB, int R) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= m_alloc) return;
+  const int64_t j = smap[s];
+  real* r = rec + s * R;
+  for (int e = 0; e < EB; ++e) r[D + e] = j >= 0 ? (real)v[j * EB + e] : (real)0;
+}
+
+template <typename real>
+int cutoff_apply_t(kmvp_ctx* c, int kernel, const double* v, int E) {
+  const int D = c->D;
+  const int R = (D + E + 3) / 4 * 4;
+  const bool sync = !c->async_product;
+  if (sync) HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
+  hipLaunchKernelGGL((cutoff_signal_f64_kernel<real>), dim3(blocks_for(c->ct_m_alloc)), dim3(256), 0, c->stream, v,
+                     (const int64_t*)c->ct_smap.p, (real*)c->ct_rec.p, c->ct_m_alloc, D, E, R);
+  c->ct_sig_ver = 0;  // the signal slots hold a Krylov vector, no version of kmvp_set_signal's
+  c->ct_sig_EB = 0;
+  LowdCutoffArgs<real> a = cutoff_args<real>(c, c->ct_solve_radius);
+  a.out = (double*)c->out.p;
+  if (sync) HIP_TRY(c, hipEventRecord(c->ev[3], c->stream));
+  hipError_t le = launch_cutoff(kernel, D, E, SIG_PRODUCT, a, dim3((unsigned)(c->ct_n_pad / (CUTOFF_TILE * CUTOFF_WAVES))), c->stream,
+                                &c->last_kernel_name);
+  if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "cutoff radius: no kernel instantiated for this (kernel, D, E)");
+  HIP_TRY(c, le);
+  c->out_n = c->N;
+  c->out_e = E;
+  if (!sync) return KMVP_OK;
+  HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_kernel_ms, c->ev[3], c->ev[1]));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
+  return KMVP_OK;
+}
+
+// Everything an application needs that is not a launch: the plan, the target image, the coordinates of records laid out
+// for E signal columns, and c->out.
+template <typename real>
+int cutoff_solve_prepare(kmvp_ctx* c, double radius, int E) {
+  const int R = (c->D + E + 3) / 4 * 4;
+  int rc;
+  if ((rc = cutoff_prepare<real>(c, radius))) return rc;
+  if ((rc = pack_cutoff<real>(c, R, 0))) return rc;
+  if ((rc = ensure(c, c->out, std::max<size_t>((size_t)c->N * E * sizeof(double), 16)))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return KMVP_OK;
+}
+
 }  // namespace
 
 int run_cutoff(kmvp_ctx* c, int kernel, double radius, bool normalise) {
@@ -238,6 +296,44 @@ int run_cutoff(kmvp_ctx* c, int kernel, double radius, bool normalise) {
     return KMVP_OK;
   }
   return c->dtype == KMVP_F64 ? run_cutoff_t<double>(c, kernel, radius, normalise) : run_cutoff_t<float>(c, kernel, radius, normalise);
+}
+
+int cutoff_apply(kmvp_ctx* c, int kernel, const double* v, int E) {
+  if (!(c->ct_solve_radius > 0.0) || c->ct_plan_points_ver != c->points_ver)
+    return fail(c, KMVP_E_INVALID, "cutoff radius: the operator of a Wendland solve was applied outside kmvp_wendland_<c>_cg_solve");
+  if (c->N == 0) return KMVP_OK;
+  return c->dtype == KMVP_F64 ? cutoff_apply_t<double>(c, kernel, v, E) : cutoff_apply_t<float>(c, kernel, v, E);
+}
+
+int wendland_cg_solve(kmvp_ctx* c, int kernel, double radius, const void* a_host, int E, double rtol, int maxit, double* out_b,
+                      int* iters, double* resid) {
+  if (!c) return KMVP_E_INVALID;
+  c->note.clear();
+  int rc;
+  if (!c->have_points) return fail(c, KMVP_E_INVALID, "kmvp_set_points has not been called");
+  if ((rc = radius_checked(c, radius))) return rc;
+  if (!a_host || !out_b || E < 1 || maxit < 0 || !(rtol > 0)) return fail(c, KMVP_E_INVALID, "bad solver arguments");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = cutoff_unsupported(c, "solve"))) return rc;
+  if (!c->same_points)
+    return fail(c, KMVP_E_INVALID, "cutoff radius: the solver needs the targets to be the sources (x == NULL at kmvp_set_points)");
+  if (E > LOWD_MAX_E)
+    return fail(c, KMVP_E_UNSUPPORTED, "solve: E = " + std::to_string(E) + " right-hand sides are beyond the cutoff's kernels' E <= " +
+                                           std::to_string(LOWD_MAX_E) + " (cutoff radius: solve per block of columns)");
+  if (c->precond_rank > 0)
+    return fail(c, KMVP_E_UNSUPPORTED, "solve: the preconditioner is not built for the Wendland kernels (its column kernel knows none); "
+                                       "set rank 0 (cutoff radius: kmvp_wendland_<c>_cg_solve)");
+  c->last_kernel_ms = c->last_total_ms = c->last_allreduce_ms = 0.f;
+  // as cg_apply leaves the context for the other kernels: E columns, no density, the signal replaced
+  c->density = false;
+  c->E = E;
+  ++c->signal_ver;
+  if ((rc = c->dtype == KMVP_F64 ? cutoff_solve_prepare<double>(c, radius, E) : cutoff_solve_prepare<float>(c, radius, E))) return rc;
+  c->ct_solve_radius = radius;
+  rc = cg_solve(c, kernel, a_host, E, rtol, maxit, out_b, iters, resid);
+  c->ct_solve_radius = 0.0;
+  c->have_signal = false;  // (also where cg_solve returned before its own guard)
+  return rc;
 }
 
 int radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts) {

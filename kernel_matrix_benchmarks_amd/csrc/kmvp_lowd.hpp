@@ -35,7 +35,10 @@
 
 namespace kmvp {
 
-enum : int { K_GAUSSIAN = 0, K_ABSEXP = 1, K_INVDIST = 2, K_EXPDOT = 3, K_GAUSSIAN_SHIFTED = 4, K_MATERN32 = 5, K_MATERN52 = 6 };
+enum : int { K_GAUSSIAN = 0, K_ABSEXP = 1, K_INVDIST = 2, K_EXPDOT = 3, K_GAUSSIAN_SHIFTED = 4, K_MATERN32 = 5, K_MATERN52 = 6,
+             K_WENDLAND_C2 = 7, K_WENDLAND_C4 = 8 };
+// K_WENDLAND_C2 / K_WENDLAND_C4: Wendland's compactly supported functions; lowd_cutoff_kernel only (kmvp_lowd_cutoff.hpp)
+inline bool is_wendland(int kernel) { return kernel == K_WENDLAND_C2 || kernel == K_WENDLAND_C4; }
 // K_EXPDOT: host-side only (run_product) and the bf16 matrix-core kernels; K_GAUSSIAN_SHIFTED: the bf16 matrix-core kernels
 // only -- the Gaussian with exp(<x,y>)'s per-target running shift, taken when targets != sources (kmvp_mfma.hpp)
 // K_MATERN32 / K_MATERN52: the Matern covariances nu = 3/2, 5/2 at length scale 1 (include/kmvp.h), difference form only

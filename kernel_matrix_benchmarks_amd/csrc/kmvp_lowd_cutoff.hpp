@@ -13,6 +13,10 @@
 // (s = +inf).  float32 sums fold into fp64 every `chunk` walked records and at every run's end; float64 keeps one chain.
 // A lane writes its fp64 row to the caller's index, read from tmap; a NaN target coordinate gives a NaN row, count -1.
 //
+// K_WENDLAND_C2 / K_WENDLAND_C4 (include/kmvp.h kmvp_wendland_<c>_cutoff) take their value from wendland_value below in
+// place of kval: polynomials in t = sqrt(s) / R that vanish at t = 1, so the select removes nothing but rounding.  They
+// read no exp table, so those instantiations have neither the table nor its barrier.
+//
 // Reads past a run are the batched kernel's: the first prefetch is U records at the run's start, the loop's last round
 // prefetches the U records behind the run -- the next row's first records, or the spare batch at the array's end.  The plan
 // keeps rec0 + len + U <= m_alloc for every run (tests/test_host_cutoff_plan.py).  A tile without runs reads no record.
@@ -38,6 +42,7 @@ struct LowdCutoffArgs {
   int chunk;                // walked records per fp32 chunk, a multiple of 8
   int self_norm;            // density estimation with normalised rows: v / v
   int exclude_self;         // count: a finite target has its own pair subtracted
+  real iR2;                 // Wendland kernels: (real)(1 / (R R)), the quotient formed in double; no other kernel reads it
 };
 
 __device__ __forceinline__ CutoffTile cutoff_tile_of_wave(const CutoffTile* __restrict__ tiles, int64_t& slot0) {
@@ -47,12 +52,38 @@ __device__ __forceinline__ CutoffTile cutoff_tile_of_wave(const CutoffTile* __re
   return tiles[tile];
 }
 
+template <int KERNEL>
+constexpr bool KERNEL_IS_WENDLAND = KERNEL == K_WENDLAND_C2 || KERNEL == K_WENDLAND_C4;
+
+// Wendland's functions of t = sqrt(s iR2), u = max(1 - t, 0):  C2: u^4 (4 t + 1);  C4: u^6 (35 t^2 + 18 t + 3) / 3.
+// t is exp(-r)'s square root in each precision (kval<K_ABSEXP>): v_sqrt_f32, resp. v_rsq_f64 and one step with q = 0 and
+// q = inf passed through.  q = inf (a pad record, an overflowed s) gives u = 0 and 0 * inf = NaN, a NaN s a NaN: the caller's
+// select on s <= r2 removes both.  Per pair after s, float32: v_mul, v_sqrt, v_sub, v_max, 2 (3) v_mul, 1 (2) v_fma, v_mul.
+__device__ __forceinline__ float wendland_sqrt(float q) { return __builtin_amdgcn_sqrtf(q); }
+__device__ __forceinline__ double wendland_sqrt(double q) {
+  const double y0 = __builtin_amdgcn_rsq(q);
+  const double e = fma(-q * y0, y0, 1.0);
+  const double r = q * fma(y0 * e, fma(e, 0.375, 0.5), y0);
+  return (q == 0.0 || q == (double)INFINITY) ? q : r;
+}
+template <int KERNEL, typename real>
+__device__ __forceinline__ real wendland_value(real s, real iR2) {
+  const real q = s * iR2;
+  const real t = wendland_sqrt(q);
+  const real u = fmax((real)1 - t, (real)0);
+  const real u2 = u * u;
+  if constexpr (KERNEL == K_WENDLAND_C2) return (u2 * u2) * fma((real)4, t, (real)1);
+  else return ((u2 * u2) * u2) * fma(t, fma(t, (real)(35.0 / 3.0), (real)6), (real)1);
+}
+
 // One (target, source) pair: interact's arithmetic (kmvp_lowd.hpp) with the inside test between kval and the accumulation.
 template <int KERNEL, int D, int E, int SIG, typename real>
 __device__ __forceinline__ void cutoff_interact(const real (&x)[D], real (&acc)[RecLayout<D, E, SIG>::NE], const real* __restrict__ r,
-                                                real r2, const double* __restrict__ tab) {
+                                                real r2, real iR2, const double* __restrict__ tab) {
   const real s = knn_sqdist<D, real>(x, r);
-  real k = kval<KERNEL>(s, tab);
+  real k;
+  if constexpr (KERNEL_IS_WENDLAND<KERNEL>) k = wendland_value<KERNEL, real>(s, iR2);
+  else k = kval<KERNEL>(s, tab);
   k = s <= r2 ? k : (real)0;
   if constexpr (SIG == SIG_DENSITY) {
     acc[0] += k;
@@ -70,14 +101,16 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_cutoff_kernel(const LowdCu
   constexpr int NE = L::NE;
   constexpr int U = 4;  // records per SGPR batch; runs hold a whole number of 2 U
   constexpr bool F32 = sizeof(real) == 4;
+  constexpr bool TABLE = !F32 && !KERNEL_IS_WENDLAND<KERNEL>;
   static_assert(2 * U == CUTOFF_RECORDS, "two ping-pong batches per round");
 
   // fp64 only: table 2^(j/64) of kexp_neg_f64 -- the workgroup's only barrier, before any wave enters its loops
-  __shared__ double exp_tab_lds[F32 ? 1 : 64];
-  const double* exp_tab = exp_tab_lds;
-  if constexpr (!F32) {
+  const double* exp_tab = nullptr;
+  if constexpr (TABLE) {
+    __shared__ double exp_tab_lds[64];
     if (threadIdx.x < 64) exp_tab_lds[threadIdx.x] = exp2((double)threadIdx.x * (1.0 / 64.0));
     __syncthreads();
+    exp_tab = exp_tab_lds;
   }
 
   const int lane = threadIdx.x & 63;
@@ -105,9 +138,10 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_cutoff_kernel(const LowdCu
     }
   };
   const real r2 = a.r2;
+  const real iR2 = a.iR2;
   auto run_batch = [&](const real (&rb)[U * R]) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) cutoff_interact<KERNEL, D, E, SIG, real>(x, acc, rb + u * R, r2, exp_tab);
+    for (int u = 0; u < U; ++u) cutoff_interact<KERNEL, D, E, SIG, real>(x, acc, rb + u * R, r2, iR2, exp_tab);
   };
 
   for (int q = 0; q < t.nruns; ++q) {
@@ -205,11 +239,16 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_cutoff_count_kernel(const 
 }
 
 // kmvp_lowd_cutoff_inst.hip, one unit per precision: the Gaussian, exp(-r) and the two Matern kernels, D <= 3, E <= 4 in
-// the three signal modes; the count per D.  hipErrorInvalidValue where nothing is instantiated.
+// the three signal modes; the count per D.  kmvp_lowd_wendland_inst.hip, again one unit per precision: the two Wendland
+// kernels in the same shapes.  hipErrorInvalidValue where nothing is instantiated.
 hipError_t launch_lowd_cutoff_f32(int kernel, int D, int E, int sig, const LowdCutoffArgs<float>& args, dim3 grid, hipStream_t stream,
                                   const char** kernel_name);
 hipError_t launch_lowd_cutoff_f64(int kernel, int D, int E, int sig, const LowdCutoffArgs<double>& args, dim3 grid, hipStream_t stream,
                                   const char** kernel_name);
+hipError_t launch_lowd_wendland_f32(int kernel, int D, int E, int sig, const LowdCutoffArgs<float>& args, dim3 grid, hipStream_t stream,
+                                    const char** kernel_name);
+hipError_t launch_lowd_wendland_f64(int kernel, int D, int E, int sig, const LowdCutoffArgs<double>& args, dim3 grid, hipStream_t stream,
+                                    const char** kernel_name);
 hipError_t launch_lowd_cutoff_count_f32(int D, const LowdCutoffArgs<float>& args, dim3 grid, hipStream_t stream, const char** kernel_name);
 hipError_t launch_lowd_cutoff_count_f64(int D, const LowdCutoffArgs<double>& args, dim3 grid, hipStream_t stream, const char** kernel_name);
 

@@ -225,6 +225,9 @@ static int cg_dots(kmvp_ctx* c, const double* u, const double* v, const Krylov& 
 // bitwise the same vectors.  The solver's diagonal is NOT applied here: the first consumer of c->out adds it, once, on
 // the full vector.
 int cg_apply(kmvp_ctx* c, int kernel, const double* v, const Krylov& k) {
+  // the Wendland kernels (kmvp_wendland_<c>_cg_solve): the cutoff product on its own layouts, b_raw and the pack
+  // bookkeeping of the plain product untouched
+  if (is_wendland(kernel)) return cutoff_apply(c, kernel, v, k.E);
   const int64_t n = c->M * k.E;  // this rank's sources
   v += (size_t)c->j_offset * k.E;
   int rc = ensure(c, c->b_raw, k.n * elem_size(c->dtype));  // also holds the right-hand side
