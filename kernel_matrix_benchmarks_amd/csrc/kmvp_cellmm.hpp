@@ -451,6 +451,19 @@ static_assert(CMM_STAGE_TILES % WAVES_PER_BLOCK == 0 && CMM_STAGE_TILES <= 64, "
 constexpr bool cellmm16_has_shared(int TT) { return TT >= 8; }
 constexpr int cellmm16_lds_bytes(int TT) { return cellmm16_has_shared(TT) ? CMM16_SHARED_LDS_BYTES : 2 * CMM_STAGE_BYTES; }
 
+// A stage's tiles are walked in CELL RUNS.  `keys` holds the stage's cell keys, lane q tile q's, -1 in the pad tiles and in
+// the lanes behind the stage.  What a tile used to ask of its key -- pad? another cell? -- is fixed once the keys are in
+// the lanes, so it is asked once per stage and once per run, and the tile loop between holds a tile's work alone.
+//   cellmm16_live_tiles: the stage's source tiles.  Pad tiles only trail the last source tile (the packers guarantee it),
+//                        so the count of non-negative keys is the position of the first pad.
+//   cellmm16_run_end:    the end of the run of key `ks` that tile q starts: the first live tile behind q with another key.
+__device__ __forceinline__ int cellmm16_live_tiles(int keys) { return __builtin_popcountll(__ballot(keys >= 0)); }
+__device__ __forceinline__ int cellmm16_run_end(int keys, int ks, int q, int n_live) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long other = __ballot(lane > q && lane < n_live && keys != ks);
+  return other ? __builtin_ctzll(other) : n_live;
+}
+
 // The pair loop of one workgroup: `bid` is its index within the launch (list) that `a` describes, `lds` the workgroup's
 // LDS (cellmm16_lds_bytes).
 //
@@ -464,11 +477,19 @@ constexpr int cellmm16_lds_bytes(int TT) { return cellmm16_has_shared(TT) ? CMM1
 //     key) likewise, lane q holding tile q's, for stages s (consumed), s + 1 (built) and s + 2 (in flight);
 //   * while stage s is consumed from abuf[buf], stage s + 1 is built into abuf[buf ^ 1], which was last read before the
 //     previous barrier -- the discipline of `commit` above; one barrier per stage as before, and every wavefront of the
-//     workgroup passes the same barriers: the stage loop's bounds depend on the segment alone, the tile loop's early exit
-//     (pad tiles) leaves only the tile loop, and no barrier sits inside either;
+//     workgroup passes the same barriers: the stage loop's bounds depend on the segment alone, the walk over a stage's
+//     cell runs ends with the stage's live tiles, and no barrier sits inside either;
 //   * a consumer's tile is one ds_read_b128 (its lane's operand), one ds_read_b64 (its row's weight factors), the weight
 //     sum and the MFMAs.  Every lane sums the same weights in the same order through the same fmaf and feeds the MFMAs the
 //     same operand bits as in the staged body: the sums are the same bit for bit.
+//
+// Both bodies walk a stage in cell runs (cellmm16_live_tiles, cellmm16_run_end above): per run one v_readlane for its
+// key, new_cell() if that is not the cell in hand -- key_s is carried from stage to stage, so a stage that continues the
+// previous stage's cell does not fold --, one ballot for the run's end, and then the tile loop over [q, q_end).  That loop
+// is the body's single site of accumulating MFMAs and holds a tile's work alone: the reads, the pointer steps, the operand
+// build (staged body), the weight sum, the MFMAs, and the back edge as its only branch (3 scalar instructions per tile
+// where the per-tile key tests took 15 and a second taken branch).  The order of every addition, the folds and the
+// operand bits are those of the loop that tested every tile: the sums are the same bit for bit (tests/test_cellmm16_runs.py).
 template <int TT, bool SHARED>
 __device__ __forceinline__ void cellmm16_body(const CellmmArgs& a, int bid, unsigned char* lds) {
   static_assert(!CMM_BF16, "f16 operands only");
@@ -654,24 +675,28 @@ __device__ __forceinline__ void cellmm16_body(const CellmmArgs& a, int bid, unsi
       const unsigned char* p_ya = lds + buf * CMM16_ABUF_BYTES + lane * 16;
       const unsigned char* p_w = lds + CMM16_WBUF_OFF + buf * CMM16_WBUF_BYTES + rs * 8;
       const int keys = lane < CMM_STAGE_TILES ? __float_as_int(hcur[3]) : -1;
-#pragma unroll 1
-      for (int q = 0; q < CMM_STAGE_TILES; ++q) {
+      const int n_live = cellmm16_live_tiles(keys);
+      for (int q = 0; q < n_live;) {  // one trip per cell run
         const int ks = __builtin_amdgcn_readlane(keys, q);
-        if (ks < 0) break;  // pad tiles (key -1) only trail the last source tile (wave-uniform)
-        if (ks != key_s) {  // wave-uniform, once per ~30 tiles
+        if (ks != key_s) {  // wave-uniform, once per ~30 tiles; a run that continues the last stage's cell does not fold
           f32x4 cs;
 #pragma unroll
           for (int c = 0; c < 3; ++c) cs[c] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hcur[c]), q));
           cs[3] = 0.f;
           new_cell(cs, ks);
         }
-        const f16x8 ya = *reinterpret_cast<const f16x8*>(p_ya);
-        const f32x2 w = *reinterpret_cast<const f32x2*>(p_w);
-        p_ya += 64 * 16;
-        p_w += CELL_TILE * 8;
-        cellmm16_weight_sum(w[0], w[1], S0, S0c);
+        const int q_end = cellmm16_run_end(keys, ks, q, n_live);
+        // the tile loop: ONE site of accumulating MFMAs per body, no test but the back edge
+#pragma unroll 1
+        do {
+          const f16x8 ya = *reinterpret_cast<const f16x8*>(p_ya);
+          const f32x2 w = *reinterpret_cast<const f32x2*>(p_w);
+          p_ya += 64 * 16;
+          p_w += CELL_TILE * 8;
+          cellmm16_weight_sum(w[0], w[1], S0, S0c);
 #pragma unroll
-        for (int u = 0; u < HT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ya, xb[u], acc[u], 0, 0, 0);
+          for (int u = 0; u < HT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ya, xb[u], acc[u], 0, 0, 0);
+        } while (++q < q_end);
       }
       hcur = hnext;
       hnext = hfar;
@@ -684,34 +709,37 @@ __device__ __forceinline__ void cellmm16_body(const CellmmArgs& a, int bid, unsi
       // the stage's cell keys, lane q holding tile q's: a tile's key is then one v_readlane, and the reads of its e and b
       // no longer queue behind a header read and its wait
       const int keys = lane < CMM_STAGE_TILES ? __float_as_int(hdr[hl][3]) : -1;
-#pragma unroll 1
-      for (int q = 0; q < CMM_STAGE_TILES; ++q) {
+      const int n_live = cellmm16_live_tiles(keys);
+      for (int q = 0; q < n_live;) {  // one trip per cell run
         const int ks = __builtin_amdgcn_readlane(keys, q);
-        if (ks < 0) break;                         // pad tiles (key -1) only trail the last source tile (wave-uniform)
-        if (ks != key_s) new_cell(hdr[q], ks);     // wave-uniform, once per ~30 tiles
-        // ---- A = psi_k(e_j) W_j(T) b_j for source row rs, slot half h (cellmm16_operand)
-        const f32x4 ef = *reinterpret_cast<const f32x4*>(p_ef);
-        const float bq = *reinterpret_cast<const float*>(p_b);
-        p_ef += CELL_TILE * 16;
-        p_b += CELL_TILE * 4;
+        if (ks != key_s) new_cell(hdr[q], ks);  // wave-uniform, once per ~30 tiles; a continued cell does not fold
+        const int q_end = cellmm16_run_end(keys, ks, q, n_live);
+        // the tile loop: ONE site of accumulating MFMAs per body, no test but the back edge (the timing-only probe aside)
+#pragma unroll 1
+        do {
+          // ---- A = psi_k(e_j) W_j(T) b_j for source row rs, slot half h (cellmm16_operand)
+          const f32x4 ef = *reinterpret_cast<const f32x4*>(p_ef);
+          const float bq = *reinterpret_cast<const float*>(p_b);
+          p_ef += CELL_TILE * 16;
+          p_b += CELL_TILE * 4;
 #if CMM16_BUILD_PROBE
-        if ((q & 3) == wave_u) {
-          cellmm16_operand(ef, bq, D1[0], D1[1], D1[2], h, ya_probe, wexp_probe);
-        } else {
-          asm volatile("" ::"v"(ef[0]), "v"(ef[1]), "v"(ef[2]), "v"(ef[3]));
-        }
-        asm volatile("" ::"v"(bq), "v"(S0));
-        const f16x8 ya = ya_probe;
-        const float wexp = wexp_probe;
+          if ((q & 3) == wave_u) {
+            cellmm16_operand(ef, bq, D1[0], D1[1], D1[2], h, ya_probe, wexp_probe);
+          } else {
+            asm volatile("" ::"v"(ef[0]), "v"(ef[1]), "v"(ef[2]), "v"(ef[3]));
+          }
+          asm volatile("" ::"v"(bq), "v"(S0));
+          const f16x8 ya = ya_probe;
+          const float wexp = wexp_probe;
 #else
-        f16x8 ya;
-        float wexp;
-        cellmm16_operand(ef, bq, D1[0], D1[1], D1[2], h, ya, wexp);
+          f16x8 ya;
+          float wexp;
+          cellmm16_operand(ef, bq, D1[0], D1[1], D1[2], h, ya, wexp);
 #endif
-        cellmm16_weight_sum(bq, wexp, S0, S0c);
-        // ONE site of accumulating MFMAs per body and no branch around it (cellmm_kernel)
+          cellmm16_weight_sum(bq, wexp, S0, S0c);
 #pragma unroll
-        for (int u = 0; u < HT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ya, xb[u], acc[u], 0, 0, 0);
+          for (int u = 0; u < HT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ya, xb[u], acc[u], 0, 0, 0);
+        } while (++q < q_end);
       }
       if (s + 1 < s_end) commit(buf ^ 1);
     }
