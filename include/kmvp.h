@@ -405,9 +405,10 @@ int kmvp_set_batches(kmvp_ctx* ctx, int B, const int64_t* y_offsets, const int64
  * N > 0, exclude_self when the targets are not the sources.  KMVP_E_UNSUPPORTED with a message that names the cutoff and
  * the cause: D > 3, E > 4 signal columns, a bfloat16 context, an attached communicator, a source slice (M < M_total), and
  * while batches are set (kmvp_set_batches).  float16 data: a float32 context of float16-rounded points, as everywhere.
- * Not built: K nearest within a radius, gradients / log-sum-exp with a cutoff, solvers with a cutoff for the four
- * truncated kernels (a truncated Gaussian or Matern matrix is in general not positive definite), D > 3, source shards,
- * batches combined with a cutoff, a device-side plan build, caller-supplied block-sparse ranges. */
+ * Not built: K nearest within a radius, log-sum-exp with a cutoff, the length-scale derivative with a cutoff (the gradient
+ * with respect to the targets is kmvp_<kernel>_cutoff_grad below), solvers with a cutoff for the four truncated kernels (a
+ * truncated Gaussian or Matern matrix is in general not positive definite), D > 3, source shards, batches combined with a
+ * cutoff, a device-side plan build, caller-supplied block-sparse ranges. */
 int kmvp_gaussian_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_absexp_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_matern32_cutoff(kmvp_ctx* ctx, double radius, int normalise);
@@ -441,14 +442,58 @@ int kmvp_cutoff_info(kmvp_ctx* ctx, int64_t out[8]);
  *     KMVP_E_INVALID: a bad radius, targets that are not the sources, the solver's own argument checks.
  *     KMVP_E_UNSUPPORTED, naming the cause: E > 4, whatever kmvp_<kernel>_cutoff refuses (D > 3, bfloat16, a communicator,
  *     a source slice, batches), and a preconditioner of rank > 0 (its column kernel knows no Wendland function).
- * Not built: MINRES, the Lanczos quadrature, eigsh, the preconditioner, gradients, source shards and batches with these
- * kernels. */
+ * Not built: MINRES, the Lanczos quadrature, eigsh, the preconditioner, the length-scale derivative, source shards and
+ * batches with these kernels.  Their gradient with respect to the targets is kmvp_wendland_<c>_cutoff_grad below. */
 int kmvp_wendland_c2_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_wendland_c4_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_wendland_c2_cg_solve(kmvp_ctx* ctx, double radius, const void* a, int E, double rtol, int maxit, double* out_b,
                               int* iters, double* resid);
 int kmvp_wendland_c4_cg_solve(kmvp_ctx* ctx, double radius, const void* a, int E, double rtol, int maxit, double* out_b,
                               int* iters, double* resid);
+
+/* Gradient of the cutoff-radius product with respect to the target points (an extension: SPH's sum of m_j grad W, the
+ * force of a short-range potential sum, the slope of a kriging mean with a tapered covariance), O(N * neighbours):
+ *     G[i, e, :] = c * sum_{j : s_ij <= r2} W(s_ij) (x_i - y_j) b[j, e]
+ * kmvp_<kernel>_grad's output on kmvp_<kernel>_cutoff's cell list: read with kmvp_get_result as (N, E * D) float64, column
+ * e D + d, in the caller's order; in density mode (kmvp_set_signal(NULL)) b = 1 and E = 1.  r2 and the plan are the
+ * cutoff's; kmvp_cutoff_info is valid afterwards.  s_ij is formed from the D differences x_i - y_j, computed once and kept:
+ * one square and D - 1 fmas, the cutoff's expression bit for bit, so a row's inside set is exactly the set
+ * kmvp_radius_count counts (a pair at exactly r2 is inside, a NaN s is outside).
+ *   Gaussian, exp(-r), Matern 3/2 and 5/2: W and c are kmvp_<kernel>_grad's (c = -2, -1, -3, -5/3).  G is the sum of the
+ *     plain gradient's terms over the inside set; it equals the derivative of the truncated sum wherever no pair sits on
+ *     the boundary (the truncated sum jumps there).  exp(-r): a pair with s = 0 or a denormal s contributes 0, the own pair
+ *     of targets == sources included (the plain gradient's subgradient rule).
+ *   Wendland, t = sqrt(s iR2) and u = max(1 - t, 0) exactly as kmvp_wendland_<c>_cutoff forms them:
+ *     wendland_c2   grad k = -(20 / R^2) u^3 (x - y)                 W = (u u) u                      c = -20 / R^2
+ *     wendland_c4   grad k = -(56 / (3 R^2)) u^5 (5 t + 1) (x - y)   W = ((u2 u2) u) fma(5, t, 1)     c = -56 / (3 R^2)
+ *     continuous and 0 at the boundary: the exact gradients of the exact products.
+ * c is formed in double and applied once per row in float64, never per pair.
+ *  - an outside pair that the walk meets adds exactly +0 to every component: W and the D differences are set to 0 on the
+ *    inside condition (a pad record's difference is -inf, so W = 0 alone would give NaN);
+ *  - a target with nothing inside gets a row of +0; a target with an infinite coordinate has nothing inside;
+ *  - a target with a NaN coordinate gets a NaN row in every component and disturbs no other row;
+ *  - a source with a NaN or infinite coordinate is in no record and touches no row.  kmvp_<kernel>_grad does NOT screen its
+ *    sources: there such a source makes components of every row NaN;
+ *  - signals must be finite, as for kmvp_<kernel>_cutoff: 0 * b is added for a walked outside pair;
+ *  - float32 keeps E D sums per lane, folded into float64 every "chunk" walked records and at the end of every range;
+ *    float64 keeps one chain.  Every row is written once by its own lane: no partial sums, no atomics; bitwise
+ *    reproducible run to run for the same points, radius and options;
+ *  - it reads the records and the target image that kmvp_<kernel>_cutoff packs: a product and a gradient on one context
+ *    plan and pack once.  Every other entry returns the same bits before and after.
+ *  - kmvp_last_kernel_name is "lowd_cutoff_grad_kernel" (csrc/kmvp_lowd_cutoff_grad.hpp); kmvp_last_kernel_ms is the pair
+ *    loop.
+ * KMVP_E_INVALID: a radius that is not finite or not > 0, no points set, no signal set.  KMVP_E_UNSUPPORTED with a message
+ * that names the cutoff gradient and the cause: everything kmvp_<kernel>_cutoff refuses -- D > 3, E > 4 signal columns, a
+ * bfloat16 context, an attached communicator, a source slice, batches.  There is no `normalise` argument (the gradient of
+ * a ratio is not built) and no inverse-distance entry.
+ * Not built: log-sum-exp and K nearest with a cutoff, the length-scale derivative with a cutoff, D > 3, source shards,
+ * batches, a device-side plan build. */
+int kmvp_gaussian_cutoff_grad(kmvp_ctx* ctx, double radius);
+int kmvp_absexp_cutoff_grad(kmvp_ctx* ctx, double radius);
+int kmvp_matern32_cutoff_grad(kmvp_ctx* ctx, double radius);
+int kmvp_matern52_cutoff_grad(kmvp_ctx* ctx, double radius);
+int kmvp_wendland_c2_cutoff_grad(kmvp_ctx* ctx, double radius);
+int kmvp_wendland_c4_cutoff_grad(kmvp_ctx* ctx, double radius);
 
 /* Lloyd's k-means, resident on the device (an extension: the solver on top of the arg-K-min at K = 1, as the Krylov
  * solvers are on top of the product and Sinkhorn on top of the log-sum-exp).  Kernel-independent, like kmvp_nearest.  The

@@ -62,6 +62,12 @@ SYMBOLS = [
     ("kmvp_matern52_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
     ("kmvp_wendland_c2_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
     ("kmvp_wendland_c4_cutoff", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int]),
+    ("kmvp_gaussian_cutoff_grad", _c.c_int, [_c.c_void_p, _c.c_double]),
+    ("kmvp_absexp_cutoff_grad", _c.c_int, [_c.c_void_p, _c.c_double]),
+    ("kmvp_matern32_cutoff_grad", _c.c_int, [_c.c_void_p, _c.c_double]),
+    ("kmvp_matern52_cutoff_grad", _c.c_int, [_c.c_void_p, _c.c_double]),
+    ("kmvp_wendland_c2_cutoff_grad", _c.c_int, [_c.c_void_p, _c.c_double]),
+    ("kmvp_wendland_c4_cutoff_grad", _c.c_int, [_c.c_void_p, _c.c_double]),
     ("kmvp_radius_count", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p]),
     ("kmvp_cutoff_info", _c.c_int, [_c.c_void_p, _c.c_void_p]),
     ("kmvp_kmeans", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
@@ -377,6 +383,21 @@ class Context:
         if entry is None:
             raise NotImplementedError(f"no cutoff-radius product for kernel {kernel}")
         self._check(entry(self._ctx, float(radius), 1 if normalize_rows else 0))
+
+    def run_cutoff_grad(self, kernel, radius):
+        """Gradient of the cutoff-radius product with respect to the targets (include/kmvp.h kmvp_<kernel>_cutoff_grad): the
+        plain gradient's terms over the pairs inside ``radius``; read it with get_result(N, E * D)."""
+        entry = {
+            "gaussian": self._lib.kmvp_gaussian_cutoff_grad,
+            "absolute-exponential": self._lib.kmvp_absexp_cutoff_grad,
+            "matern-3/2": self._lib.kmvp_matern32_cutoff_grad,
+            "matern-5/2": self._lib.kmvp_matern52_cutoff_grad,
+            "wendland-c2": self._lib.kmvp_wendland_c2_cutoff_grad,
+            "wendland-c4": self._lib.kmvp_wendland_c4_cutoff_grad,
+        }.get(kernel)
+        if entry is None:
+            raise NotImplementedError(f"no cutoff-radius gradient for kernel {kernel}")
+        self._check(entry(self._ctx, float(radius)))
 
     def radius_count(self, radius, exclude_self=False):
         """The number of sources within ``radius`` of every target (include/kmvp.h kmvp_radius_count): (N,) int64, -1 for a

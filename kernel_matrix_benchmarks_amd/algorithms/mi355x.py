@@ -510,6 +510,27 @@ class MI355XProduct(BaseProduct):
         self._cutoff_info = self._ctx.cutoff_info()
         self.res = None
 
+    def query_cutoff_gradient(self, radius):
+        """G[i, e, :] = the gradient with respect to x_i of the sum over the sources within ``radius`` (include/kmvp.h
+        kmvp_<kernel>_cutoff_grad): query_gradient()'s terms over query_cutoff()'s inside set, on the same cell list and the
+        same packed records.  For kernel="wendland-c2" / "wendland-c4" it is the exact gradient of the exact product.  A
+        target with nothing inside gets zeros.  Honours density estimation; read the result with get_gradient().  The
+        timed part, like query().  Synchronous."""
+        self._check_cutoff_supported("query_cutoff_gradient")
+        what = None
+        if self.kernel not in CUTOFF_KERNELS + WENDLAND_KERNELS:
+            what = (f"kernel={self.kernel!r} (gaussian, absolute-exponential, matern-3/2, matern-5/2, wendland-c2 and "
+                    "wendland-c4 only)")
+        elif self.normalize_rows:
+            what = "normalize_rows=True (the gradient of a ratio of sums is not built)"
+        elif self.E > GRADIENT_MAX_E:
+            what = f"E = {self.E} > {GRADIENT_MAX_E} signal columns (pass them in blocks of {GRADIENT_MAX_E})"
+        if what is not None:
+            raise NotImplementedError(f"MI355XProduct.query_cutoff_gradient doesn't support {what}.")
+        self._ctx.run_cutoff_grad(self.kernel, radius)
+        self._cutoff_info = self._ctx.cutoff_info()
+        self.res = None
+
     def query_radius_count(self, radius, exclude_self=False):
         """The number of sources within ``radius`` of every target (include/kmvp.h kmvp_radius_count): DBSCAN's core-point
         test, ball_query's lengths.  exclude_self (same_points only) leaves a point's own pair out.  Needs prepare_data()

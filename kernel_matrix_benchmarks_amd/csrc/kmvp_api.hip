@@ -222,6 +222,12 @@ int kmvp_matern32_cutoff(kmvp_ctx* c, double radius, int normalise) { return run
 int kmvp_matern52_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_MATERN52, radius, normalise != 0); }
 int kmvp_wendland_c2_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_WENDLAND_C2, radius, normalise != 0); }
 int kmvp_wendland_c4_cutoff(kmvp_ctx* c, double radius, int normalise) { return run_cutoff(c, K_WENDLAND_C4, radius, normalise != 0); }
+int kmvp_gaussian_cutoff_grad(kmvp_ctx* c, double radius) { return run_cutoff_grad(c, K_GAUSSIAN, radius); }
+int kmvp_absexp_cutoff_grad(kmvp_ctx* c, double radius) { return run_cutoff_grad(c, K_ABSEXP, radius); }
+int kmvp_matern32_cutoff_grad(kmvp_ctx* c, double radius) { return run_cutoff_grad(c, K_MATERN32, radius); }
+int kmvp_matern52_cutoff_grad(kmvp_ctx* c, double radius) { return run_cutoff_grad(c, K_MATERN52, radius); }
+int kmvp_wendland_c2_cutoff_grad(kmvp_ctx* c, double radius) { return run_cutoff_grad(c, K_WENDLAND_C2, radius); }
+int kmvp_wendland_c4_cutoff_grad(kmvp_ctx* c, double radius) { return run_cutoff_grad(c, K_WENDLAND_C4, radius); }
 int kmvp_radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts) { return radius_count(c, radius, exclude_self, counts); }
 int kmvp_cutoff_info(kmvp_ctx* c, int64_t* out) { return cutoff_info(c, out); }
 int kmvp_kmeans(kmvp_ctx* c, int C, const double* weights, double tol, int maxit, double* centroids, int64_t* labels,

@@ -392,6 +392,8 @@ int sinkhorn_batched_solve(kmvp_ctx* c, int kernel, const double* log_a, const d
 // kmvp_cutoff.hip: kmvp_<kernel>_cutoff, kmvp_radius_count and kmvp_cutoff_info -- the cell-list plan
 // (kmvp_cutoff_plan.hpp), the gather-packed layouts, lowd_cutoff_kernel / lowd_cutoff_count_kernel
 int run_cutoff(kmvp_ctx* c, int kernel, double radius, bool normalise);
+// kmvp_<kernel>_cutoff_grad: the gradient with respect to the targets on the same plan and packs, lowd_cutoff_grad_kernel
+int run_cutoff_grad(kmvp_ctx* c, int kernel, double radius);
 int radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts);
 int cutoff_info(kmvp_ctx* c, int64_t* out);
 // kmvp_wendland_<c>_cg_solve: the checks, the plan and the packed layouts, then cg_solve with cutoff_apply as its operator

@@ -3,6 +3,7 @@
 //                    (kmvp_cutoff_plan.hpp) and uploads its two tables and two maps -- once per (points, radius, factor)
 //   pack_cutoff      the gather-packs of the batched clouds (kmvp_lowd_batch.hpp) through the plan's maps
 //   run_cutoff       the truncated product on lowd_cutoff_kernel
+//   run_cutoff_grad  its gradient with respect to the targets on lowd_cutoff_grad_kernel: the same plan, the same packs
 //   radius_count     the neighbour counts on lowd_cutoff_count_kernel
 //   wendland_cg_solve / cutoff_apply   conjugate gradients (kmvp_solvers.hip cg_solve) with the Wendland cutoff product as
 //                    its operator: plan and packs once, then two launches per application
@@ -15,6 +16,7 @@
 #include "kmvp_ctx.hpp"
 #include "kmvp_lowd_batch.hpp"
 #include "kmvp_lowd_cutoff.hpp"
+#include "kmvp_lowd_cutoff_grad.hpp"
 
 namespace kmvp {
 
@@ -137,6 +139,7 @@ LowdCutoffArgs<real> cutoff_args(const kmvp_ctx* c, double radius) {
   a.self_norm = 0;
   a.exclude_self = 0;
   a.iR2 = (real)(1.0 / (radius * radius));
+  a.gconst = 0.0;
   return a;
 }
 
@@ -184,6 +187,62 @@ int run_cutoff_t(kmvp_ctx* c, int kernel, double radius, bool normalise) {
   HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
   c->out_n = c->N;
   c->out_e = E;
+  return KMVP_OK;
+}
+
+inline hipError_t launch_cutoff_grad(int kernel, int D, int E, int sig, const LowdCutoffArgs<float>& a, dim3 grid, hipStream_t s,
+                                     const char** name) {
+  return is_wendland(kernel) ? launch_lowd_wendland_grad_f32(kernel, D, E, sig, a, grid, s, name)
+                             : launch_lowd_cutoff_grad_f32(kernel, D, E, sig, a, grid, s, name);
+}
+inline hipError_t launch_cutoff_grad(int kernel, int D, int E, int sig, const LowdCutoffArgs<double>& a, dim3 grid, hipStream_t s,
+                                     const char** name) {
+  return is_wendland(kernel) ? launch_lowd_wendland_grad_f64(kernel, D, E, sig, a, grid, s, name)
+                             : launch_lowd_cutoff_grad_f64(kernel, D, E, sig, a, grid, s, name);
+}
+
+// The gradient's constant c (kmvp_lowd_cutoff_grad.hpp), in double: grad_constant<KERNEL>()'s values for the four truncated
+// kernels, Wendland's from the radius.
+double cutoff_grad_constant(int kernel, double radius) {
+  switch (kernel) {
+    case K_GAUSSIAN: return -2.0;
+    case K_MATERN32: return -3.0;
+    case K_MATERN52: return -5.0 / 3.0;
+    case K_WENDLAND_C2: return -20.0 / (radius * radius);
+    case K_WENDLAND_C4: return -56.0 / (3.0 * (radius * radius));
+    default: return -1.0;  // exp(-r)
+  }
+}
+
+// run_cutoff_t with the product's record length, so that the two share plan and packs, and (N, E D) in c->out.
+template <typename real>
+int run_cutoff_grad_t(kmvp_ctx* c, int kernel, double radius) {
+  const int D = c->D;
+  const int sig = c->density ? SIG_DENSITY : SIG_PRODUCT;
+  const int E = c->density ? 1 : c->E;
+  const int EB = c->density ? 0 : E;
+  const int R = (D + EB + 3) / 4 * 4;
+  int rc;
+  HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
+  if ((rc = cutoff_prepare<real>(c, radius))) return rc;
+  if ((rc = pack_cutoff<real>(c, R, EB))) return rc;
+  if ((rc = ensure(c, c->out, (size_t)c->N * E * D * sizeof(double)))) return rc;
+  LowdCutoffArgs<real> a = cutoff_args<real>(c, radius);
+  a.out = (double*)c->out.p;
+  a.gconst = cutoff_grad_constant(kernel, radius);
+  HIP_TRY(c, hipEventRecord(c->ev[3], c->stream));
+  hipError_t le = launch_cutoff_grad(kernel, D, E, sig, a, dim3((unsigned)(c->ct_n_pad / (CUTOFF_TILE * CUTOFF_WAVES))), c->stream,
+                                     &c->last_kernel_name);
+  if (le == hipErrorInvalidValue)
+    return fail(c, KMVP_E_UNSUPPORTED, "cutoff gradient: no kernel instantiated for this (kernel, D, E)");
+  HIP_TRY(c, le);
+  HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_kernel_ms, c->ev[3], c->ev[1]));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
+  c->out_n = c->N;
+  c->out_e = E * D;
   return KMVP_OK;
 }
 
@@ -296,6 +355,31 @@ int run_cutoff(kmvp_ctx* c, int kernel, double radius, bool normalise) {
     return KMVP_OK;
   }
   return c->dtype == KMVP_F64 ? run_cutoff_t<double>(c, kernel, radius, normalise) : run_cutoff_t<float>(c, kernel, radius, normalise);
+}
+
+int run_cutoff_grad(kmvp_ctx* c, int kernel, double radius) {
+  if (!c) return KMVP_E_INVALID;
+  c->note.clear();
+  int rc;
+  if ((rc = radius_checked(c, radius))) return rc;
+  if (!c->have_points) return fail(c, KMVP_E_INVALID, "cutoff gradient: kmvp_set_points has not been called");
+  if (!c->have_signal) return fail(c, KMVP_E_INVALID, "cutoff gradient: kmvp_set_signal has not been called");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = cutoff_unsupported(c, "cutoff gradient"))) return rc;
+  const int E = c->density ? 1 : c->E;
+  if (E > LOWD_MAX_E)
+    return fail(c, KMVP_E_UNSUPPORTED, "cutoff gradient: E = " + std::to_string(E) + " signal columns are beyond the cutoff's kernels' E <= " +
+                                           std::to_string(LOWD_MAX_E) + " (cutoff radius: run it per block of columns)");
+  c->last_kernel_ms = c->last_total_ms = c->last_allreduce_ms = 0.f;
+  if (c->N == 0) {
+    if ((rc = c->dtype == KMVP_F64 ? cutoff_prepare<double>(c, radius) : cutoff_prepare<float>(c, radius))) return rc;
+    if ((rc = ensure(c, c->out, 16))) return rc;
+    c->out_n = 0;
+    c->out_e = E * c->D;
+    c->last_kernel_name = "none";
+    return KMVP_OK;
+  }
+  return c->dtype == KMVP_F64 ? run_cutoff_grad_t<double>(c, kernel, radius) : run_cutoff_grad_t<float>(c, kernel, radius);
 }
 
 int cutoff_apply(kmvp_ctx* c, int kernel, const double* v, int E) {

@@ -43,6 +43,7 @@ struct LowdCutoffArgs {
   int self_norm;            // density estimation with normalised rows: v / v
   int exclude_self;         // count: a finite target has its own pair subtracted
   real iR2;                 // Wendland kernels: (real)(1 / (R R)), the quotient formed in double; no other kernel reads it
+  double gconst;            // lowd_cutoff_grad_kernel (kmvp_lowd_cutoff_grad.hpp): the gradient's constant c, applied once per row
 };
 
 __device__ __forceinline__ CutoffTile cutoff_tile_of_wave(const CutoffTile* __restrict__ tiles, int64_t& slot0) {
