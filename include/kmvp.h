@@ -405,8 +405,8 @@ int kmvp_set_batches(kmvp_ctx* ctx, int B, const int64_t* y_offsets, const int64
  * N > 0, exclude_self when the targets are not the sources.  KMVP_E_UNSUPPORTED with a message that names the cutoff and
  * the cause: D > 3, E > 4 signal columns, a bfloat16 context, an attached communicator, a source slice (M < M_total), and
  * while batches are set (kmvp_set_batches).  float16 data: a float32 context of float16-rounded points, as everywhere.
- * Not built: K nearest within a radius, log-sum-exp with a cutoff, the length-scale derivative with a cutoff (the gradient
- * with respect to the targets is kmvp_<kernel>_cutoff_grad below), solvers with a cutoff for the four truncated kernels (a
+ * Not built: log-sum-exp with a cutoff, the length-scale derivative with a cutoff (the gradient with respect to the
+ * targets is kmvp_<kernel>_cutoff_grad below, the K nearest inside the radius kmvp_radius_nearest), solvers with a cutoff for the four truncated kernels (a
  * truncated Gaussian or Matern matrix is in general not positive definite), D > 3, source shards, batches combined with a
  * cutoff, a device-side plan build, caller-supplied block-sparse ranges. */
 int kmvp_gaussian_cutoff(kmvp_ctx* ctx, double radius, int normalise);
@@ -415,6 +415,40 @@ int kmvp_matern32_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_matern52_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_radius_count(kmvp_ctx* ctx, double radius, int exclude_self, int64_t* counts);
 int kmvp_cutoff_info(kmvp_ctx* ctx, int64_t out[8]);
+
+/* K nearest sources within a radius on the cell list (an extension: PyTorch3D's ball_query with indices, fixed-radius
+ * nearest neighbours, SPH and molecular-dynamics neighbour lists, DBSCAN's region query, Vecchia neighbour sets and a k-NN
+ * graph on a cloud too large for the brute-force kmvp_nearest).  For every target the K sources with the smallest s_ij
+ * among those INSIDE the radius -- kmvp_radius_count's rule exactly: r2 = (real)(R * R) with R * R formed in double, s_ij
+ * the family's difference-form squared distance in the working precision, a pair at exactly r2 inside, a NaN s outside.
+ * Outputs and conventions are kmvp_nearest's: out_idx / out_sqdist (N, K) row-major, caller-owned, written during the call;
+ * nearest first, equal distances in ascending caller's source index; out_sqdist is the very value that was compared,
+ * widened to float64; a row with fewer than K sources inside ends in (-1, +inf); N == 0 writes nothing and returns KMVP_OK.
+ * exclude_self != 0 (targets == sources only) is kmvp_nearest's rule: K + 1 candidates are collected, the one with j == i
+ * is dropped if it is there, else the last.  Hence K <= 16, and K <= 15 with exclude_self.
+ * THE CONTRACT: row i equals, bit for bit, row i of kmvp_nearest(ctx, K, exclude_self, ...) with every entry whose
+ * sqdist > r2 replaced by (-1, +inf).  That holds whatever "cutoff_cell_factor" is: the result does NOT depend on the grid
+ * (unlike the float32 products), and it is bitwise reproducible.
+ * Non-finite coordinates
+ *  - a target with a NaN coordinate gets (-1, NaN) in all K entries (where there is a source at all: M == 0 gives
+ *    (-1, +inf) everywhere, as kmvp_nearest does) and disturbs no other row;
+ *  - a target with an infinite coordinate has nothing inside: (-1, +inf);
+ *  - a source with a NaN or infinite coordinate is in no record and never appears.
+ * How: lowd_cutoff_count_kernel's walk with a sorted list of 1, 4 or 16 candidates per lane in registers, the smallest
+ * capacity that holds K [+ 1] (lowd_cutoff_knn_kernel, csrc/kmvp_lowd_cutoff_knn.hpp).  The walk does not meet the sources
+ * in ascending index, so the list is ordered by the pair (s, caller's index) (csrc/kmvp_radius_knn_list.hpp); the indices
+ * come from an int32 copy of the plan's source map, read through the scalar cache beside the records.
+ *  - kmvp_set_signal is neither needed nor consulted, kmvp_get_result is not involved, kmvp_cutoff_info is valid afterwards;
+ *  - the plan cache on (points, R, factor) and the density-layout pack are kmvp_radius_count's: a count and a radius search
+ *    on one context plan and pack once; every other entry returns the same bits before and after the call;
+ *  - kmvp_last_kernel_name is "lowd_cutoff_knn_kernel", kmvp_last_dispatch_note is "", kmvp_last_kernel_ms is the pair
+ *    loop, kmvp_last_total_ms includes the plan build's uploads and the packs, as for the count.
+ * KMVP_E_INVALID: a radius that is not finite or not > 0, K < 1, a NULL output with N > 0, no points set, exclude_self when
+ * the targets are not the sources.  KMVP_E_UNSUPPORTED with a message that names the radius search and the cause: K > 16
+ * (15 with exclude_self) and everything kmvp_radius_count refuses -- D > 3, a bfloat16 context, an attached communicator,
+ * a source slice, batches.
+ * Not built: all neighbours inside the radius without a bound K (a ragged result), D > 3, source shards, batches. */
+int kmvp_radius_nearest(kmvp_ctx* ctx, double radius, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);
 
 /* Wendland's compactly supported kernels (an extension: the reference has none) -- the cutoff WITHOUT a truncation error,
  * and the library's first sparse operator for conjugate gradients.  With the support radius R, t = |x - y| / R and
@@ -486,7 +520,7 @@ int kmvp_wendland_c4_cg_solve(kmvp_ctx* ctx, double radius, const void* a, int E
  * that names the cutoff gradient and the cause: everything kmvp_<kernel>_cutoff refuses -- D > 3, E > 4 signal columns, a
  * bfloat16 context, an attached communicator, a source slice, batches.  There is no `normalise` argument (the gradient of
  * a ratio is not built) and no inverse-distance entry.
- * Not built: log-sum-exp and K nearest with a cutoff, the length-scale derivative with a cutoff, D > 3, source shards,
+ * Not built: log-sum-exp with a cutoff, the length-scale derivative with a cutoff, D > 3, source shards,
  * batches, a device-side plan build. */
 int kmvp_gaussian_cutoff_grad(kmvp_ctx* ctx, double radius);
 int kmvp_absexp_cutoff_grad(kmvp_ctx* ctx, double radius);

@@ -69,6 +69,7 @@ SYMBOLS = [
     ("kmvp_wendland_c2_cutoff_grad", _c.c_int, [_c.c_void_p, _c.c_double]),
     ("kmvp_wendland_c4_cutoff_grad", _c.c_int, [_c.c_void_p, _c.c_double]),
     ("kmvp_radius_count", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p]),
+    ("kmvp_radius_nearest", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     ("kmvp_cutoff_info", _c.c_int, [_c.c_void_p, _c.c_void_p]),
     ("kmvp_kmeans", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
                                _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
@@ -406,6 +407,19 @@ class Context:
         counts = np.zeros(int(getattr(self, "N", 0)), dtype=np.int64)
         self._check(self._lib.kmvp_radius_count(self._ctx, float(radius), 1 if exclude_self else 0, counts.ctypes.data))
         return counts
+
+    def radius_nearest(self, radius, K, exclude_self=False):
+        """The K nearest sources of every target among those within ``radius`` (include/kmvp.h kmvp_radius_nearest):
+        (idx int64 (N, K), sqdist float64 (N, K)), nearest first, ties in ascending index; (-1, +inf) where fewer than K
+        sources are inside -- run_nearest()'s rows with every entry beyond radius^2 (in the working precision) emptied."""
+        K = int(K)
+        N = int(getattr(self, "N", 0))
+        # the library writes N * K elements through each pointer: the arrays are sized here, from the points it was given
+        idx = np.empty((N, max(K, 0)), dtype=np.int64)
+        sqdist = np.empty((N, max(K, 0)), dtype=np.float64)
+        self._check(self._lib.kmvp_radius_nearest(self._ctx, float(radius), K, 1 if exclude_self else 0, idx.ctypes.data,
+                                                  sqdist.ctypes.data))
+        return idx, sqdist
 
     def cutoff_info(self):
         """The plan of the last cutoff call (include/kmvp.h kmvp_cutoff_info): a dict of cells (3 per-axis counts),

@@ -478,7 +478,8 @@ class MI355XProduct(BaseProduct):
         self._nearest = self._ctx.run_nearest(k, exclude_self)
 
     def get_nearest(self):
-        """(idx (N, k) int64, sqdist (N, k) float64), C-contiguous: the result of the last query_nearest()."""
+        """(idx (N, k) int64, sqdist (N, k) float64), C-contiguous: the result of the last query_nearest() or
+        query_radius_nearest()."""
         return self._nearest
 
     def _check_cutoff_supported(self, method):
@@ -539,6 +540,22 @@ class MI355XProduct(BaseProduct):
         if exclude_self and not self.same_points:
             raise ValueError("exclude_self needs same_points=True")
         self._radius_count = self._ctx.radius_count(radius, exclude_self)
+        self._cutoff_info = self._ctx.cutoff_info()
+
+    def query_radius_nearest(self, k, radius, exclude_self=False):
+        """The k nearest sources of every target among those within ``radius`` (include/kmvp.h kmvp_radius_nearest), on the
+        cell list: ball_query with indices, a fixed-radius neighbour list, a k-NN graph on a cloud too large for
+        query_nearest().  Row for row it is query_nearest(k, exclude_self) with every entry beyond radius^2 (in the working
+        precision) replaced by (-1, +inf): nearest first, ties in ascending index, indices into source_points.  Needs
+        prepare_data() only.  Read it with get_nearest().  Synchronous."""
+        k = int(k)
+        self._check_cutoff_supported("query_radius_nearest")
+        if exclude_self and not self.same_points:
+            raise ValueError("exclude_self needs same_points=True")
+        if k + bool(exclude_self) > NEAREST_MAX_K:
+            raise NotImplementedError(f"MI355XProduct.query_radius_nearest doesn't support k = {k} > {NEAREST_MAX_K - bool(exclude_self)}"
+                                      + (" with exclude_self" if exclude_self else "") + ".")
+        self._nearest = self._ctx.radius_nearest(radius, k, exclude_self)
         self._cutoff_info = self._ctx.cutoff_info()
 
     def get_radius_count(self):

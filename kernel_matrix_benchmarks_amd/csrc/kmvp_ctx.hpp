@@ -189,6 +189,8 @@ struct kmvp_ctx {
   uint64_t ct_sig_ver = 0;      // signal version the records' signal slots hold (0: none), of
   int ct_sig_EB = -1;           // ct_sig_EB columns
   int64_t ct_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kmvp_cutoff_info
+  DevBuf ct_smap32;             // kmvp_radius_nearest: ct_smap narrowed to int32, what its kernel reads through the scalar cache,
+  uint64_t ct_smap32_ver = 0;   // made from the plan of this version (0: none)
   double ct_solve_radius = 0.0;  // kmvp_wendland_<c>_cg_solve: the support radius cg_apply's operator runs at (0: no such solve is running)
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
@@ -395,6 +397,8 @@ int run_cutoff(kmvp_ctx* c, int kernel, double radius, bool normalise);
 // kmvp_<kernel>_cutoff_grad: the gradient with respect to the targets on the same plan and packs, lowd_cutoff_grad_kernel
 int run_cutoff_grad(kmvp_ctx* c, int kernel, double radius);
 int radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts);
+// kmvp_radius_nearest: the K nearest sources inside the radius on the same plan and the count's packs, lowd_cutoff_knn_kernel
+int radius_nearest(kmvp_ctx* c, double radius, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);
 int cutoff_info(kmvp_ctx* c, int64_t* out);
 // kmvp_wendland_<c>_cg_solve: the checks, the plan and the packed layouts, then cg_solve with cutoff_apply as its operator
 int wendland_cg_solve(kmvp_ctx* c, int kernel, double radius, const void* a_host, int E, double rtol, int maxit, double* out_b,

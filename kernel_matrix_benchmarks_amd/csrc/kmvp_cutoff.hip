@@ -5,6 +5,8 @@
 //   run_cutoff       the truncated product on lowd_cutoff_kernel
 //   run_cutoff_grad  its gradient with respect to the targets on lowd_cutoff_grad_kernel: the same plan, the same packs
 //   radius_count     the neighbour counts on lowd_cutoff_count_kernel
+//   radius_nearest   the K nearest sources inside the radius on lowd_cutoff_knn_kernel: the count's plan and packs, and an
+//                    int32 copy of the plan's source map, narrowed on the device once per plan
 //   wendland_cg_solve / cutoff_apply   conjugate gradients (kmvp_solvers.hip cg_solve) with the Wendland cutoff product as
 //                    its operator: plan and packs once, then two launches per application
 // Target image, records, tables and maps live in buffers of their own (ct_*): the product's pack bookkeeping
@@ -17,6 +19,7 @@
 #include "kmvp_lowd_batch.hpp"
 #include "kmvp_lowd_cutoff.hpp"
 #include "kmvp_lowd_cutoff_grad.hpp"
+#include "kmvp_lowd_cutoff_knn.hpp"
 
 namespace kmvp {
 
@@ -140,6 +143,11 @@ LowdCutoffArgs<real> cutoff_args(const kmvp_ctx* c, double radius) {
   a.exclude_self = 0;
   a.iR2 = (real)(1.0 / (radius * radius));
   a.gconst = 0.0;
+  a.smap32 = nullptr;
+  a.knn_idx = nullptr;
+  a.knn_sqdist = nullptr;
+  a.knn_k = 0;
+  a.knn_nan_rows = 0;
   return a;
 }
 
@@ -265,6 +273,60 @@ int radius_count_t(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts
   HIP_TRY(c, le);
   HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
   HIP_TRY(c, hipMemcpyAsync(counts, c->knn.p, (size_t)c->N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_kernel_ms, c->ev[3], c->ev[1]));
+  HIP_TRY(c, hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]));
+  return KMVP_OK;
+}
+
+// The plan's smap narrowed to int32 (every index is below 2^31: cutoff_plan_build refuses more sources), once per plan.
+__global__ void cutoff_narrow_smap_kernel(const int64_t* __restrict__ smap, int32_t* __restrict__ smap32, int64_t m_alloc) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < m_alloc) smap32[s] = (int32_t)smap[s];
+}
+
+inline hipError_t launch_cutoff_knn(int D, int KT, const LowdCutoffArgs<float>& a, dim3 grid, hipStream_t s, const char** name) {
+  return launch_lowd_cutoff_knn_f32(D, KT, a, grid, s, name);
+}
+inline hipError_t launch_cutoff_knn(int D, int KT, const LowdCutoffArgs<double>& a, dim3 grid, hipStream_t s, const char** name) {
+  return launch_lowd_cutoff_knn_f64(D, KT, a, grid, s, name);
+}
+
+// radius_count_t with the lists: the count's plan, target image and density-layout records, and the index copy.
+template <typename real>
+int radius_nearest_t(kmvp_ctx* c, double radius, int K, int exclude_self, int64_t* out_idx, double* out_sqdist) {
+  const int D = c->D;
+  const int R = (D + 3) / 4 * 4;  // density layout: no signal columns
+  int rc;
+  HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
+  if ((rc = cutoff_prepare<real>(c, radius))) return rc;
+  if ((rc = pack_cutoff<real>(c, R, 0))) return rc;
+  if (c->ct_smap32_ver != c->ct_ver) {
+    if ((rc = ensure(c, c->ct_smap32, (size_t)c->ct_m_alloc * sizeof(int32_t)))) return rc;
+    hipLaunchKernelGGL(cutoff_narrow_smap_kernel, dim3(blocks_for(c->ct_m_alloc)), dim3(256), 0, c->stream,
+                       (const int64_t*)c->ct_smap.p, (int32_t*)c->ct_smap32.p, c->ct_m_alloc);
+    HIP_TRY(c, hipGetLastError());
+    c->ct_smap32_ver = c->ct_ver;
+  }
+  // the rows in c->knn, as kmvp_nearest: (N, K) int64 indices, then (N, K) float64 squared distances
+  const size_t nk = (size_t)c->N * K;
+  if ((rc = ensure(c, c->knn, nk * (sizeof(int64_t) + sizeof(double))))) return rc;
+  LowdCutoffArgs<real> a = cutoff_args<real>(c, radius);
+  a.exclude_self = exclude_self != 0;
+  a.smap32 = (const int32_t*)c->ct_smap32.p;
+  a.knn_idx = (int64_t*)c->knn.p;
+  a.knn_sqdist = (double*)(a.knn_idx + nk);
+  a.knn_k = K;
+  a.knn_nan_rows = c->M > 0;
+  HIP_TRY(c, hipEventRecord(c->ev[3], c->stream));
+  hipError_t le = launch_cutoff_knn(D, knn_capacity(K + (exclude_self ? 1 : 0)), a, dim3((unsigned)(c->ct_n_pad / (CUTOFF_TILE * CUTOFF_WAVES))),
+                                    c->stream, &c->last_kernel_name);
+  if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "radius search: no kernel instantiated for this (D, K)");
+  HIP_TRY(c, le);
+  HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out_idx, a.knn_idx, nk * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out_sqdist, a.knn_sqdist, nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipEventElapsedTime(&c->last_kernel_ms, c->ev[3], c->ev[1]));
@@ -439,6 +501,31 @@ int radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts) 
   }
   return c->dtype == KMVP_F64 ? radius_count_t<double>(c, radius, exclude_self, counts)
                               : radius_count_t<float>(c, radius, exclude_self, counts);
+}
+
+int radius_nearest(kmvp_ctx* c, double radius, int K, int exclude_self, int64_t* out_idx, double* out_sqdist) {
+  if (!c) return KMVP_E_INVALID;
+  c->note.clear();
+  int rc;
+  if ((rc = radius_checked(c, radius))) return rc;
+  if (!c->have_points) return fail(c, KMVP_E_INVALID, "radius search: kmvp_set_points has not been called");
+  if (K < 1) return fail(c, KMVP_E_INVALID, "radius search: K must be >= 1");
+  if (exclude_self && !c->same_points)
+    return fail(c, KMVP_E_INVALID, "radius search: exclude_self needs the targets to be the sources (x == NULL at kmvp_set_points)");
+  if (c->N > 0 && (!out_idx || !out_sqdist)) return fail(c, KMVP_E_INVALID, "radius search: a NULL output");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = cutoff_unsupported(c, "radius search"))) return rc;
+  if (K + (exclude_self ? 1 : 0) > KNN_MAX_K)
+    return fail(c, KMVP_E_UNSUPPORTED, "radius search: K = " + std::to_string(K) + (exclude_self ? " with exclude_self" : "") +
+                                           " is beyond the lists' K <= 16 (15 with exclude_self)");
+  c->last_kernel_ms = c->last_total_ms = c->last_allreduce_ms = 0.f;
+  if (c->N == 0) {
+    if ((rc = c->dtype == KMVP_F64 ? cutoff_prepare<double>(c, radius) : cutoff_prepare<float>(c, radius))) return rc;
+    c->last_kernel_name = "none";
+    return KMVP_OK;
+  }
+  return c->dtype == KMVP_F64 ? radius_nearest_t<double>(c, radius, K, exclude_self, out_idx, out_sqdist)
+                              : radius_nearest_t<float>(c, radius, K, exclude_self, out_idx, out_sqdist);
 }
 
 int cutoff_info(kmvp_ctx* c, int64_t* out) {

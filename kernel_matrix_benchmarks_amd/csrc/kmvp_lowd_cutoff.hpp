@@ -44,6 +44,12 @@ struct LowdCutoffArgs {
   int exclude_self;         // count: a finite target has its own pair subtracted
   real iR2;                 // Wendland kernels: (real)(1 / (R R)), the quotient formed in double; no other kernel reads it
   double gconst;            // lowd_cutoff_grad_kernel (kmvp_lowd_cutoff_grad.hpp): the gradient's constant c, applied once per row
+  // lowd_cutoff_knn_kernel (kmvp_lowd_cutoff_knn.hpp) alone reads what follows; it takes exclude_self from above
+  const int32_t* smap32;    // [m_alloc] record -> caller's source index, -1 for a pad
+  int64_t* knn_idx;         // (N, knn_k) row-major in the caller's order
+  double* knn_sqdist;       // (N, knn_k)
+  int knn_k;                // entries per row
+  int knn_nan_rows;         // a NaN target gets (-1, NaN): set unless there is no source at all
 };
 
 __device__ __forceinline__ CutoffTile cutoff_tile_of_wave(const CutoffTile* __restrict__ tiles, int64_t& slot0) {
