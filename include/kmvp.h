@@ -380,8 +380,17 @@ int kmvp_set_batches(kmvp_ctx* ctx, int B, const int64_t* y_offsets, const int64
  *     coordinates are all finite counts itself once and has 1 subtracted; duplicates of it still count.
  *   kmvp_cutoff_info(ctx, out[8])   the plan the last of these calls ran on: [0], [1], [2] cells per axis (1 for unused
  *     axes); [3] wave tiles of 64 target slots that own a target; [4] source runs of all tiles; [5] records walked, the sum
- *     over the tiles of live lanes x the records of its runs; [6] padded source records; [7] host milliseconds the last
- *     plan build took, rounded (the plan is cached: 0 builds since do not reset it).  KMVP_E_INVALID before any such call.
+ *     over the tiles of live lanes x the records of its runs; [6] padded source records; [7] wall milliseconds the last
+ *     plan build took on whichever side ran it ("cutoff_plan": the host's build without its copies, the device's with its
+ *     two read-backs), rounded (the plan is cached: 0 builds since do not reset it).  KMVP_E_INVALID before any such call.
+ *   kmvp_cutoff_plan_read(ctx, sizes[13], grid[4], tiles, runs, tmap, smap)   that plan itself, copied from the device
+ *     buffers the kernels read (so it checks the host build's upload as well as the device build): sizes[0 .. 3) cells per
+ *     axis, [3] n_pad target slots, [4] m_pad and [5] m_alloc source records, [6] tiles with a live lane, [7] records walked,
+ *     [8] tiles and [9] runs of the tables, [10] entries of tmap (= n_pad), [11] entries of smap (= m_alloc), [12] the side
+ *     that built it: 0 the host, 1 the device; grid = the origin lo[3] and the cell side h; tiles as sizes[8] rows of three
+ *     int64 (first run, runs, live lanes), runs as sizes[9] rows of two (first record, records), tmap and smap the padded
+ *     slot -> caller index maps, -1 for a pad (csrc/kmvp_cutoff_plan.hpp).  Every pointer may be NULL: read the sizes
+ *     first, then the arrays, as with kmvp_cell_layout.  KMVP_E_INVALID before any cutoff call has built a plan.
  * Non-finite coordinates
  *  - a source with a NaN or infinite coordinate is never inside;
  *  - a target with an infinite coordinate has nothing inside: a row of 0 (NaN when normalised), count 0;
@@ -389,12 +398,13 @@ int kmvp_set_batches(kmvp_ctx* ctx, int B, const int64_t* y_offsets, const int64
  * Signals must be finite.  An outside pair that the walk meets is removed by setting k to 0 -- one select per pair -- and
  * 0 * b is added: a non-finite b[j, e] therefore reaches column e of every row whose walk meets source j (its cell or a
  * neighbouring one), inside the radius or not.
- * How: both clouds are counting-sorted on the host into cells of side h = "cutoff_cell_factor" * R * (1 + 2^-16) -- larger
+ * How: both clouds are counting-sorted -- on the host, or with "cutoff_plan" = 1 by a radix sort on the device, which gives
+ * the same plan entry for entry and hence the same bits from every entry here -- into cells of side h = "cutoff_cell_factor" * R * (1 + 2^-16) -- larger
  * where that would give more than 2^20 cells along an axis or more than 2 (N + M) cells -- and every wave tile of up to 64
  * targets of one row of cells walks the records of the 3^(D-1) neighbouring rows between its first cell - 1 and its last
  * cell + 1 (csrc/kmvp_cutoff_plan.hpp; kernels lowd_cutoff_kernel / lowd_cutoff_count_kernel, csrc/kmvp_lowd_cutoff.hpp:
  * lowd_batch_kernel's scalar-cache feed with several source ranges per wavefront).  The plan is cached on (points, R,
- * factor); target image, records, tables and maps live in buffers of the feature's own, so every other entry returns the
+ * factor, "cutoff_plan"); target image, records, tables and maps live in buffers of the feature's own, so every other entry returns the
  * same bits before and after these calls.  float32 sums fold into float64 every "chunk" walked records and at the end of
  * every range; float64 keeps one chain.
  *  - bitwise reproducible run to run for the same points, radius and options.  The products depend on the grid (hence on
@@ -408,13 +418,14 @@ int kmvp_set_batches(kmvp_ctx* ctx, int B, const int64_t* y_offsets, const int64
  * Not built: log-sum-exp with a cutoff, the length-scale derivative with a cutoff (the gradient with respect to the
  * targets is kmvp_<kernel>_cutoff_grad below, the K nearest inside the radius kmvp_radius_nearest), solvers with a cutoff for the four truncated kernels (a
  * truncated Gaussian or Matern matrix is in general not positive definite), D > 3, source shards, batches combined with a
- * cutoff, a device-side plan build, caller-supplied block-sparse ranges. */
+ * cutoff, caller-supplied block-sparse ranges. */
 int kmvp_gaussian_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_absexp_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_matern32_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_matern52_cutoff(kmvp_ctx* ctx, double radius, int normalise);
 int kmvp_radius_count(kmvp_ctx* ctx, double radius, int exclude_self, int64_t* counts);
 int kmvp_cutoff_info(kmvp_ctx* ctx, int64_t out[8]);
+int kmvp_cutoff_plan_read(kmvp_ctx* ctx, int64_t sizes[13], double grid[4], int64_t* tiles, int64_t* runs, int64_t* tmap, int64_t* smap);
 
 /* K nearest sources within a radius on the cell list (an extension: PyTorch3D's ball_query with indices, fixed-radius
  * nearest neighbours, SPH and molecular-dynamics neighbour lists, DBSCAN's region query, Vecchia neighbour sets and a k-NN
@@ -521,7 +532,7 @@ int kmvp_wendland_c4_cg_solve(kmvp_ctx* ctx, double radius, const void* a, int E
  * bfloat16 context, an attached communicator, a source slice, batches.  There is no `normalise` argument (the gradient of
  * a ratio is not built) and no inverse-distance entry.
  * Not built: log-sum-exp with a cutoff, the length-scale derivative with a cutoff, D > 3, source shards,
- * batches, a device-side plan build. */
+ * batches. */
 int kmvp_gaussian_cutoff_grad(kmvp_ctx* ctx, double radius);
 int kmvp_absexp_cutoff_grad(kmvp_ctx* ctx, double radius);
 int kmvp_matern32_cutoff_grad(kmvp_ctx* ctx, double radius);
@@ -1012,6 +1023,13 @@ int kmvp_comm_init_host(kmvp_ctx* ctx, kmvp_host_allreduce_fn fn, void* user, in
  *                      range set to empty), so the pair loop covers the batches still running; 0 = never, stopped batches ride
  *                      along and are ignored.  The results are the same bit for bit either way: it exists to measure what
  *                      retirement saves
+ *   "cutoff_plan"      where the cell-list plan of the cutoff entries (kmvp_<kernel>_cutoff, kmvp_<kernel>_cutoff_grad,
+ *                      kmvp_radius_count, kmvp_radius_nearest, kmvp_wendland_<c>_cg_solve) is built: 0 (default) = on the host,
+ *                      from a copy of the points; 1 = on the device (csrc/kmvp_cutoff_plan_device.hip: radix sort, scans and
+ *                      one thread per table entry; two small read-backs, no transfer that grows with the clouds), for a
+ *                      cloud that moves every call.  The plan is the same entry for entry (kmvp_cutoff_plan_read) and every
+ *                      result the same bit for bit; the value is part of the plan's cache key.  Clouds beyond the device
+ *                      build's 32-bit keys (2^31 - 1 points or cells) are planned on the host whatever the option says
  *   "mfma_variant"     bf16 path, software-pipelined kernel: -1 = by kernel (default: exp(-r) 4, others 0), 0 = plain,
  *                      1 = denominators on the matrix pipe (one more accumulator tile per target tile), 4 = loop rotated by one
  *                      transcendental stage, 5 = both (csrc/kmvp_mfma.hpp, mfma_pipe_kernel VAR) */

@@ -71,6 +71,7 @@ SYMBOLS = [
     ("kmvp_radius_count", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p]),
     ("kmvp_radius_nearest", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     ("kmvp_cutoff_info", _c.c_int, [_c.c_void_p, _c.c_void_p]),
+    ("kmvp_cutoff_plan_read", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     ("kmvp_kmeans", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
                                _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
     ("kmvp_gaussian_meanshift", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -140,6 +141,8 @@ WENDLAND = ("wendland-c2", "wendland-c4")
 
 # options whose value is a real number (include/kmvp.h kmvp_set_option_double)
 REAL_OPTIONS = ("cutoff_cell_factor",)
+# sizes[12] of kmvp_cutoff_plan_read: the side that built the cutoff plan ("cutoff_plan" of kmvp_set_option: 0 / 1)
+CUTOFF_PLAN_SIDES = ("host", "device")
 
 # enum kmvp_eig_operator (include/kmvp.h)
 EIG_OPERATORS = {"kernel": 0, "centered": 1, "normalized": 2}
@@ -423,11 +426,29 @@ class Context:
 
     def cutoff_info(self):
         """The plan of the last cutoff call (include/kmvp.h kmvp_cutoff_info): a dict of cells (3 per-axis counts),
-        tiles, runs, walked (records walked, summed over the tiles as live lanes x records), records (padded) and plan_ms."""
+        tiles, runs, walked (records walked, summed over the tiles as live lanes x records), records (padded), plan_ms and
+        built_on ("host" or "device": the side that built it, kmvp_cutoff_plan_read)."""
         info = np.zeros(8, dtype=np.int64)
         self._check(self._lib.kmvp_cutoff_info(self._ctx, info.ctypes.data))
+        sizes = np.zeros(13, dtype=np.int64)
+        self._check(self._lib.kmvp_cutoff_plan_read(self._ctx, sizes.ctypes.data, None, None, None, None, None))
         return {"cells": tuple(int(v) for v in info[:3]), "tiles": int(info[3]), "runs": int(info[4]), "walked": int(info[5]),
-                "records": int(info[6]), "plan_ms": int(info[7])}
+                "records": int(info[6]), "plan_ms": int(info[7]), "built_on": CUTOFF_PLAN_SIDES[int(sizes[12])]}
+
+    def cutoff_plan(self):
+        """The plan of the last cutoff call as the kernels read it (include/kmvp.h kmvp_cutoff_plan_read): the dict of
+        tests/cutoff_reference.py plan() -- g (3,), lo (3,), h, n_pad, m_pad, m_alloc, live_tiles, walked, tiles (T, 3)
+        [run0, nruns, live], runs (Q, 2) [rec0, len], tmap (n_pad,), smap (m_alloc,) -- and built_on, "host" or "device"."""
+        sizes, grid = np.zeros(13, dtype=np.int64), np.zeros(4)
+        self._check(self._lib.kmvp_cutoff_plan_read(self._ctx, sizes.ctypes.data, grid.ctypes.data, None, None, None, None))
+        # the library writes sizes[8 .. 12) entries through the four pointers: the arrays are sized from its own answer
+        tiles, runs = np.zeros((int(sizes[8]), 3), dtype=np.int64), np.zeros((int(sizes[9]), 2), dtype=np.int64)
+        tmap, smap = np.zeros(int(sizes[10]), dtype=np.int64), np.zeros(int(sizes[11]), dtype=np.int64)
+        self._check(self._lib.kmvp_cutoff_plan_read(self._ctx, None, None, tiles.ctypes.data, runs.ctypes.data, tmap.ctypes.data,
+                                                    smap.ctypes.data))
+        return dict(g=sizes[:3].copy(), lo=grid[:3].copy(), h=float(grid[3]), n_pad=int(sizes[3]), m_pad=int(sizes[4]),
+                    m_alloc=int(sizes[5]), live_tiles=int(sizes[6]), walked=int(sizes[7]), tiles=tiles, runs=runs, tmap=tmap,
+                    smap=smap, built_on=CUTOFF_PLAN_SIDES[int(sizes[12])])
 
     def get_result(self, N, E):
         out = np.empty((N, E), dtype=np.float64)

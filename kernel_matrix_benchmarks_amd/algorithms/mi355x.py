@@ -71,6 +71,13 @@ LOGSUMEXP_MAX_D, LOGSUMEXP_MAX_E = 8, 4
 NEAREST_MAX_D, NEAREST_MAX_K = 8, 16
 CUTOFF_KERNELS = BATCHED_KERNELS  # kmvp_<kernel>_cutoff
 CUTOFF_MAX_D = 3                  # the cutoff entries' cell list
+
+
+def _cutoff_plan_code(cutoff_plan):
+    """cutoff_plan="host" | "device" -> the value of the library's "cutoff_plan" option (include/kmvp.h)."""
+    if cutoff_plan not in _lib.CUTOFF_PLAN_SIDES:
+        raise ValueError(f"cutoff_plan must be 'host' or 'device', not {cutoff_plan!r}")
+    return _lib.CUTOFF_PLAN_SIDES.index(cutoff_plan)
 EXPDOT_NATIVE_MAX_D = 64
 EXPDOT_NATIVE_MAX_D_BF16 = 141  # 16 * 9 k-steps - 3 operand columns (kmvp_mfma.hpp MFMA_DOT_AUG)
 # largest spread max_j |y_j|^2/2 - min_j |y_j|^2/2 the identity route accepts: the smallest weight is exp(-spread);
@@ -103,7 +110,7 @@ class MI355XProduct(BaseProduct):
 
     def __init__(self, *, kernel, dimension, normalize_rows=False, precision=np.float32,
                  fast_sqdists=None, device=0, comm=None, targets_per_lane=0, feed=None, segments=0,
-                 chunk=0, fast_tiles=0):
+                 chunk=0, fast_tiles=0, cutoff_plan="host"):
         super().__init__(kernel=kernel, dimension=dimension, normalize_rows=normalize_rows,
                          precision=precision)
         if kernel not in SUPPORTED_KERNELS + WENDLAND_KERNELS:
@@ -144,7 +151,10 @@ class MI355XProduct(BaseProduct):
                                           "the Matern kernels run in the difference form only (None or False).")
         self.fast_sqdists = fast_sqdists
         self._options = dict(targets_per_lane=targets_per_lane, feed=feed, segments=segments,
-                             chunk=chunk, fast_tiles=fast_tiles)
+                             chunk=chunk, fast_tiles=fast_tiles,
+                             # the query_cutoff* / query_radius_* calls: their cell-list plan built on the host (default)
+                             # or on the device -- same plan, same bits; for points that move every call
+                             cutoff_plan=_cutoff_plan_code(cutoff_plan))
         self._ctx = None
         self.res = None
         self.name = f"MI355XProduct({_precision_name(precision)})" if fast_sqdists is None else (
@@ -692,11 +702,13 @@ class MI355XSolver(BaseSolver):
 
     def __init__(self, *, kernel, dimension, normalize_rows=False, precision=np.float64,
                  device=0, rtol=1e-6, maxit=10000, comm=None, refine=None, inner_rtol=1e-3, ridge=0.0,
-                 preconditioner_rank=0, support_radius=None):
+                 preconditioner_rank=0, support_radius=None, cutoff_plan="host"):
         super().__init__(kernel=kernel, dimension=dimension, normalize_rows=normalize_rows,
                          precision=precision)
         if kernel not in SUPPORTED_KERNELS + WENDLAND_KERNELS:
             raise NotImplementedError(f"MI355XSolver doesn't support kernel {kernel}.")
+        # the Wendland solve's cell-list plan: built on the host (default) or on the device, same plan and same bits
+        self._cutoff_plan = _cutoff_plan_code(cutoff_plan)
         # kernel="wendland-c2" / "wendland-c4" (an extension): the sparse operator of kmvp_wendland_<c>_cg_solve, O(M x
         # neighbours) per iteration; support_radius is the R of t = |x - y| / R
         self._wendland = kernel in WENDLAND_KERNELS
@@ -846,6 +858,8 @@ class MI355XSolver(BaseSolver):
         self._precond_in_ctx = 0                            # and its preconditioner
         if self._ctx is None:
             self._ctx = _lib.Context(self.device)
+            if self._cutoff_plan:
+                self._ctx.set_option("cutoff_plan", self._cutoff_plan)
         world = 1 if self.comm is None else self.comm.world
         if world > 1:
             # every rank iterates on the full (replicated) Krylov vectors; the operator
@@ -1118,6 +1132,8 @@ class MI355XSolver(BaseSolver):
         if self._ctx is not None:
             extra["device_kernel"] = self._ctx.last_kernel_name  # the operator's pair-loop kernel
             extra["rccl_ranks"] = self._ctx.rccl_ranks
+            if self._wendland and self._ctx.last_kernel_name.startswith("lowd_cutoff"):
+                extra["cutoff_built_on"] = self._ctx.cutoff_info()["built_on"]  # the side that built the solve's plan
         if self._dot and hasattr(self, "scaled_residual"):
             extra["cg_scaled_system_residual"] = self.scaled_residual  # of G (D b) = D^-1 a, what the iteration saw
         if self.refine and self._ctx32 is not None:

@@ -91,7 +91,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
                     &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state, &c->ct_tiles, &c->ct_runs, &c->ct_tmap, &c->ct_smap, &c->ct_xs, &c->ct_rec, &c->ct_smap32,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state, &c->ct_tiles, &c->ct_runs, &c->ct_tmap, &c->ct_smap, &c->ct_xs, &c->ct_rec, &c->ct_smap32, &c->ct_work,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     release(*b);
   for (int i = 0; i < 5; ++i)
@@ -233,6 +233,9 @@ int kmvp_radius_nearest(kmvp_ctx* c, double radius, int K, int exclude_self, int
   return radius_nearest(c, radius, K, exclude_self, out_idx, out_sqdist);
 }
 int kmvp_cutoff_info(kmvp_ctx* c, int64_t* out) { return cutoff_info(c, out); }
+int kmvp_cutoff_plan_read(kmvp_ctx* c, int64_t* sizes, double* grid, int64_t* tiles, int64_t* runs, int64_t* tmap, int64_t* smap) {
+  return cutoff_plan_read(c, sizes, grid, tiles, runs, tmap, smap);
+}
 int kmvp_kmeans(kmvp_ctx* c, int C, const double* weights, double tol, int maxit, double* centroids, int64_t* labels,
                 double* cluster_weight, int* iters, double* inertia, double* shift) {
   KMVP_NOT_BATCHED(c, "k-means");
@@ -525,6 +528,9 @@ int kmvp_set_option(kmvp_ctx* c, const char* key, int64_t value) {
   } else if (k == "sinkhorn_retire") {
     if (value < -1 || value > 1) return fail(c, KMVP_E_INVALID, "sinkhorn_retire must be -1 (default), 0 or 1");
     c->opt_sinkhorn_retire = (int)value;
+  } else if (k == "cutoff_plan") {
+    if (value != 0 && value != 1) return fail(c, KMVP_E_INVALID, "cutoff_plan must be 0 (the plan is built on the host) or 1 (on the device)");
+    c->opt_cutoff_plan = (int)value;
   } else if (k == "chunk") {
     if (value < 8 || value > (1 << 24)) return fail(c, KMVP_E_INVALID, "chunk out of range");
     c->opt_chunk = (int)value;
@@ -551,7 +557,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
                           &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state, &c->ct_tiles, &c->ct_runs, &c->ct_tmap, &c->ct_smap, &c->ct_xs, &c->ct_rec, &c->ct_smap32,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state, &c->ct_tiles, &c->ct_runs, &c->ct_tmap, &c->ct_smap, &c->ct_xs, &c->ct_rec, &c->ct_smap32, &c->ct_work,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     t += b->cap;
   return (int64_t)t;

@@ -191,6 +191,12 @@ struct kmvp_ctx {
   int64_t ct_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kmvp_cutoff_info
   DevBuf ct_smap32;             // kmvp_radius_nearest: ct_smap narrowed to int32, what its kernel reads through the scalar cache,
   uint64_t ct_smap32_ver = 0;   // made from the plan of this version (0: none)
+  int opt_cutoff_plan = 0;      // "cutoff_plan": 0 the plan is built on the host, 1 on the device (kmvp_cutoff_plan_device.hip)
+  int ct_plan_opt = 0;          // ... the value the plan in ct_* was built under: part of its cache key
+  int ct_built_on = 0;          // the side that built it (0 host, 1 device), and what kmvp_cutoff_plan_read reports beyond
+  double ct_grid[4] = {0.0, 0.0, 0.0, 0.0};  // ct_info: lo[3] and h,
+  int64_t ct_tiles_n = 0;                    // the tiles of the table (fillers included)
+  DevBuf ct_work;               // the device build's keys, sorted clouds, scans and hipcub's scratch: nothing survives a build
   double ct_solve_radius = 0.0;  // kmvp_wendland_<c>_cg_solve: the support radius cg_apply's operator runs at (0: no such solve is running)
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
@@ -400,6 +406,17 @@ int radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts);
 // kmvp_radius_nearest: the K nearest sources inside the radius on the same plan and the count's packs, lowd_cutoff_knn_kernel
 int radius_nearest(kmvp_ctx* c, double radius, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);
 int cutoff_info(kmvp_ctx* c, int64_t* out);
+// kmvp_cutoff_plan_read: the plan of the last cutoff call from the device buffers the kernels read
+int cutoff_plan_read(kmvp_ctx* c, int64_t* sizes, double* grid, int64_t* tiles, int64_t* runs, int64_t* tmap, int64_t* smap);
+// kmvp_cutoff_plan_device.hip: the plan for (points, radius, "cutoff_cell_factor") built on c->stream into ct_tiles, ct_runs,
+// ct_tmap and ct_smap, and what cutoff_prepare keeps of it.  *fits false: nothing was built, the cloud is beyond the build's
+// 32-bit keys and indices (kmvp_cutoff_plan_device.hpp cutoff_device_fits).
+struct CutoffBuilt {
+  int64_t g[3];
+  double lo[3], h;
+  int64_t n_pad, m_pad, m_alloc, live_tiles, walked, tiles, runs;
+};
+int cutoff_plan_device(kmvp_ctx* c, double radius, CutoffBuilt* out, bool* fits);
 // kmvp_wendland_<c>_cg_solve: the checks, the plan and the packed layouts, then cg_solve with cutoff_apply as its operator
 int wendland_cg_solve(kmvp_ctx* c, int kernel, double radius, const void* a_host, int E, double rtol, int maxit, double* out_b,
                       int* iters, double* resid);

@@ -1,6 +1,9 @@
 // Cutoff-radius products and neighbour counts (include/kmvp.h kmvp_<kernel>_cutoff, kmvp_radius_count, kmvp_cutoff_info).
-//   cutoff_prepare   copies the points back, widens them exactly to double, builds the cell-list plan
-//                    (kmvp_cutoff_plan.hpp) and uploads its two tables and two maps -- once per (points, radius, factor)
+//   cutoff_prepare   the cell-list plan, once per (points, radius, factor, "cutoff_plan"): on the host (cutoff_plan_host
+//                    copies the points back, widens them exactly to double, runs kmvp_cutoff_plan.hpp's build and uploads
+//                    its two tables and two maps) or, "cutoff_plan" = 1, on the device (kmvp_cutoff_plan_device.hip: the
+//                    same entries with no transfer that grows with the clouds)
+//   cutoff_plan_read the plan back from the buffers the kernels read (kmvp_cutoff_plan_read)
 //   pack_cutoff      the gather-packs of the batched clouds (kmvp_lowd_batch.hpp) through the plan's maps
 //   run_cutoff       the truncated product on lowd_cutoff_kernel
 //   run_cutoff_grad  its gradient with respect to the targets on lowd_cutoff_grad_kernel: the same plan, the same packs
@@ -46,12 +49,10 @@ void widen(const std::vector<real>& in, std::vector<double>& out) {
   for (size_t i = 0; i < in.size(); ++i) out[i] = (double)in[i];
 }
 
-// The plan for (points, radius, factor), built and uploaded unless the context holds it.
+// The host build: the points copied back and widened exactly to double, cutoff_plan_build, its two tables and two maps
+// uploaded.
 template <typename real>
-int cutoff_prepare(kmvp_ctx* c, double radius) {
-  uint64_t bits;
-  memcpy(&bits, &radius, sizeof(bits));
-  if (c->ct_plan_points_ver == c->points_ver && c->ct_radius_bits == bits && c->ct_factor == c->opt_cutoff_factor) return KMVP_OK;
+int cutoff_plan_host(kmvp_ctx* c, double radius, CutoffBuilt* out, double* ms) {
   const int D = c->D;
   std::vector<real> yh((size_t)c->M * D), xh(c->same_points ? 0 : (size_t)c->N * D);
   if (!yh.empty()) HIP_TRY(c, hipMemcpyAsync(yh.data(), c->y_raw.p, yh.size() * sizeof(real), hipMemcpyDeviceToHost, c->stream));
@@ -64,7 +65,7 @@ int cutoff_prepare(kmvp_ctx* c, double radius) {
   CutoffPlan p;
   if (!cutoff_plan_build(yd.data(), c->M, c->same_points ? yd.data() : xd.data(), c->N, D, radius, c->opt_cutoff_factor, p))
     return fail(c, KMVP_E_UNSUPPORTED, "cutoff radius: 2^31 sources or more (the pair loop counts positions within a run in 32 bits)");
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (p.n_pad / (CUTOFF_TILE * CUTOFF_WAVES) > MAX_GRID) return fail(c, KMVP_E_UNSUPPORTED, "cutoff radius: launch grid too large");
   c->ct_plan_points_ver = 0;  // (a device failure from here on leaves no plan behind)
   int rc;
@@ -80,14 +81,58 @@ int cutoff_prepare(kmvp_ctx* c, double radius) {
     HIP_TRY(c, hipMemcpyAsync(c->ct_tmap.p, p.tmap.data(), p.tmap.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->ct_smap.p, p.smap.data(), p.smap.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the plan's vectors are only read during the call
-  c->ct_n_pad = p.n_pad;
-  c->ct_m_alloc = p.m_alloc;
-  const int64_t info[8] = {p.g[0], p.g[1], p.g[2], p.live_tiles, (int64_t)p.runs.size(), p.walked, p.m_pad, (int64_t)std::llround(ms)};
+  for (int d = 0; d < 3; ++d) {
+    out->g[d] = p.g[d];
+    out->lo[d] = p.lo[d];
+  }
+  out->h = p.h;
+  out->n_pad = p.n_pad;
+  out->m_pad = p.m_pad;
+  out->m_alloc = p.m_alloc;
+  out->live_tiles = p.live_tiles;
+  out->walked = p.walked;
+  out->tiles = (int64_t)p.tiles.size();
+  out->runs = (int64_t)p.runs.size();
+  return KMVP_OK;
+}
+
+// The plan for (points, radius, factor, "cutoff_plan"), built unless the context holds it: on the host and uploaded, or on
+// the device where the option asks for it and the cloud fits the device build's 32-bit keys.
+template <typename real>
+int cutoff_prepare(kmvp_ctx* c, double radius) {
+  uint64_t bits;
+  memcpy(&bits, &radius, sizeof(bits));
+  if (c->ct_plan_points_ver == c->points_ver && c->ct_radius_bits == bits && c->ct_factor == c->opt_cutoff_factor &&
+      c->ct_plan_opt == c->opt_cutoff_plan)
+    return KMVP_OK;
+  CutoffBuilt b;
+  double ms = 0.0;
+  int rc, built_on = 0;
+  if (c->opt_cutoff_plan == 1) {
+    bool fits = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    c->ct_plan_points_ver = 0;  // (a device failure from here on leaves no plan behind)
+    if ((rc = cutoff_plan_device(c, radius, &b, &fits))) return rc;
+    ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (fits) {
+      built_on = 1;
+      if (b.n_pad / (CUTOFF_TILE * CUTOFF_WAVES) > MAX_GRID) return fail(c, KMVP_E_UNSUPPORTED, "cutoff radius: launch grid too large");
+    }
+  }
+  if (!built_on && (rc = cutoff_plan_host<real>(c, radius, &b, &ms))) return rc;
+  c->ct_n_pad = b.n_pad;
+  c->ct_m_alloc = b.m_alloc;
+  const int64_t info[8] = {b.g[0], b.g[1], b.g[2], b.live_tiles, b.runs, b.walked, b.m_pad, (int64_t)std::llround(ms)};
   memcpy(c->ct_info, info, sizeof(info));
+  const double grid[4] = {b.lo[0], b.lo[1], b.lo[2], b.h};
+  memcpy(c->ct_grid, grid, sizeof(grid));
+  c->ct_tiles_n = b.tiles;
+  c->ct_built_on = built_on;
   ++c->ct_ver;
   c->ct_plan_points_ver = c->points_ver;
   c->ct_radius_bits = bits;
   c->ct_factor = c->opt_cutoff_factor;
+  c->ct_plan_opt = c->opt_cutoff_plan;
   return KMVP_OK;
 }
 
@@ -533,6 +578,41 @@ int cutoff_info(kmvp_ctx* c, int64_t* out) {
   if (!out) return fail(c, KMVP_E_INVALID, "cutoff radius: a NULL output");
   if (c->ct_ver == 0) return fail(c, KMVP_E_INVALID, "cutoff radius: no cutoff call has built a plan on this context");
   memcpy(out, c->ct_info, sizeof(c->ct_info));
+  return KMVP_OK;
+}
+
+// Tiles and runs widened to rows of int64 on the host: the tables come back as the kernels read them, 16 bytes an entry.
+int cutoff_plan_read(kmvp_ctx* c, int64_t* sizes, double* grid, int64_t* tiles, int64_t* runs, int64_t* tmap, int64_t* smap) {
+  if (!c) return KMVP_E_INVALID;
+  if (c->ct_ver == 0 || c->ct_plan_points_ver == 0)
+    return fail(c, KMVP_E_INVALID, "cutoff radius: no cutoff call has built a plan on this context");
+  const int64_t ntiles = c->ct_tiles_n, nruns = c->ct_info[4];
+  if (sizes) {
+    const int64_t v[13] = {c->ct_info[0], c->ct_info[1], c->ct_info[2], c->ct_n_pad, c->ct_info[6], c->ct_m_alloc, c->ct_info[3],
+                           c->ct_info[5],  ntiles,        nruns,         c->ct_n_pad, c->ct_m_alloc, c->ct_built_on};
+    memcpy(sizes, v, sizeof(v));
+  }
+  if (grid) memcpy(grid, c->ct_grid, sizeof(c->ct_grid));
+  if (!tiles && !runs && !tmap && !smap) return KMVP_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<CutoffTile> th(tiles ? (size_t)ntiles : 0);
+  std::vector<CutoffRun> rh(runs ? (size_t)nruns : 0);
+  if (!th.empty()) HIP_TRY(c, hipMemcpyAsync(th.data(), c->ct_tiles.p, th.size() * sizeof(CutoffTile), hipMemcpyDeviceToHost, c->stream));
+  if (!rh.empty()) HIP_TRY(c, hipMemcpyAsync(rh.data(), c->ct_runs.p, rh.size() * sizeof(CutoffRun), hipMemcpyDeviceToHost, c->stream));
+  if (tmap && c->ct_n_pad > 0)
+    HIP_TRY(c, hipMemcpyAsync(tmap, c->ct_tmap.p, (size_t)c->ct_n_pad * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  if (smap && c->ct_m_alloc > 0)
+    HIP_TRY(c, hipMemcpyAsync(smap, c->ct_smap.p, (size_t)c->ct_m_alloc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t t = 0; t < th.size(); ++t) {
+    tiles[3 * t + 0] = th[t].run0;
+    tiles[3 * t + 1] = th[t].nruns;
+    tiles[3 * t + 2] = th[t].live;
+  }
+  for (size_t r = 0; r < rh.size(); ++r) {
+    runs[2 * r + 0] = rh[r].rec0;
+    runs[2 * r + 1] = rh[r].len;
+  }
   return KMVP_OK;
 }
 

@@ -28,12 +28,16 @@
 // the padded -> caller index maps (-1: a pad) of the gather-pack kernels and of the kernels' epilogue.
 //
 // Plain C++ with nothing of HIP in it: the same text compiles into kmvp_cutoff.hip and, with a host compiler alone, into
-// tests/test_host_cutoff_plan.py.
+// tests/test_host_cutoff_plan.py.  cutoff_plan_build is the host build and the definition of the plan; the device build
+// ("cutoff_plan" = 1, kmvp_cutoff_plan_device.hpp) shares cutoff_grid and the per-element rules marked KMVP_HD, and has to
+// produce the same plan entry for entry.
 #pragma once
 #include <stdint.h>
 
 #include <cmath>
 #include <vector>
+
+#include "kmvp_radius_knn_list.hpp"  // KMVP_HD: the per-element rules below also run in the device build's kernels
 
 namespace kmvp {
 
@@ -70,9 +74,9 @@ struct CutoffPlan {
   std::vector<int64_t> smap;  // [m_alloc] record      -> caller's source index, -1 for a pad
 };
 
-inline int64_t cutoff_round_up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
+KMVP_HD inline int64_t cutoff_round_up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
 
-inline bool cutoff_point_finite(const double* p, int D) {
+KMVP_HD inline bool cutoff_point_finite(const double* p, int D) {
   for (int d = 0; d < D; ++d)
     if (!std::isfinite(p[d])) return false;
   return true;
@@ -84,11 +88,36 @@ inline int64_t cutoff_axis_cells(double ext, double h) {
   return (int64_t)q + 1;
 }
 
-inline int64_t cutoff_cell_of(double v, double lo, double h, int64_t g) {
+KMVP_HD inline int64_t cutoff_cell_of(double v, double lo, double h, int64_t g) {
   const double q = std::floor((v - lo) / h);
   if (!(q > 0.0)) return 0;
   if (!(q < (double)g)) return g - 1;
   return (int64_t)q;
+}
+
+// The grid rule, stated once for the host build below and the device build (kmvp_cutoff_plan_device.hpp): the cell side h
+// and the cells per axis g for the extent [lo, hi] of the finite points (both 0 where there is none), D <= 3.
+inline void cutoff_grid(const double* lo, const double* hi, int64_t M, int64_t N, int D, double R, double factor, double& h_out,
+                        int64_t* g) {
+  double ext[3] = {0.0, 0.0, 0.0};
+  for (int d = 0; d < D; ++d) ext[d] = hi[d] - lo[d];  // (may overflow to inf: the caps below take care of it)
+  double h = factor * R * (1.0 + 1.0 / 65536.0);
+  for (int d = 0; d < D; ++d) {
+    if (!(ext[d] / h < (double)(CUTOFF_MAX_AXIS - 1))) {
+      const double need = ext[d] / (double)(CUTOFF_MAX_AXIS - 1);
+      if (need > h) h = need;
+    }
+  }
+  if (!std::isfinite(h)) h = INFINITY;
+  const int64_t cap = 2 * (N + M) > 1 ? 2 * (N + M) : 1;
+  for (;;) {
+    for (int d = 0; d < 3; ++d) g[d] = d < D ? cutoff_axis_cells(ext[d], h) : 1;
+    if (g[0] * g[1] * g[2] <= cap || !std::isfinite(h)) break;
+    h *= 1.25;
+  }
+  if (!std::isfinite(h))
+    for (int d = 0; d < 3; ++d) g[d] = 1;
+  h_out = h;
 }
 
 // The plan for sources y (M, D) and targets x (N, D), row-major doubles (x may be y), D <= 3, a finite radius R > 0 and a
@@ -112,25 +141,8 @@ inline bool cutoff_plan_build(const double* y, int64_t M, const double* x, int64
       any = true;
     }
   }
-  double ext[3] = {0.0, 0.0, 0.0};
-  for (int d = 0; d < D; ++d) ext[d] = hi[d] - p.lo[d];  // (may overflow to inf: the caps below take care of it)
-  double h = factor * R * (1.0 + 1.0 / 65536.0);
-  for (int d = 0; d < D; ++d) {
-    if (!(ext[d] / h < (double)(CUTOFF_MAX_AXIS - 1))) {
-      const double need = ext[d] / (double)(CUTOFF_MAX_AXIS - 1);
-      if (need > h) h = need;
-    }
-  }
-  if (!std::isfinite(h)) h = INFINITY;
-  const int64_t cap = 2 * (N + M) > 1 ? 2 * (N + M) : 1;
-  for (;;) {
-    for (int d = 0; d < 3; ++d) p.g[d] = d < D ? cutoff_axis_cells(ext[d], h) : 1;
-    if (p.g[0] * p.g[1] * p.g[2] <= cap || !std::isfinite(h)) break;
-    h *= 1.25;
-  }
-  if (!std::isfinite(h))
-    for (int d = 0; d < 3; ++d) p.g[d] = 1;
-  p.h = h;
+  cutoff_grid(p.lo, hi, M, N, D, R, factor, p.h, p.g);
+  const double h = p.h;
   const int64_t g0 = p.g[0], g1 = p.g[1], g2 = p.g[2];
   const int64_t ncells = g0 * g1 * g2, nrows = g1 * g2;
   auto cell_of = [&](const double* q) {
