@@ -461,6 +461,51 @@ int kmvp_cutoff_plan_read(kmvp_ctx* ctx, int64_t sizes[13], double grid[4], int6
  * Not built: all neighbours inside the radius without a bound K (a ragged result), D > 3, source shards, batches. */
 int kmvp_radius_nearest(kmvp_ctx* ctx, double radius, int K, int exclude_self, int64_t* out_idx, double* out_sqdist);
 
+/* DBSCAN on the cell list, resident on the device (an extension: the third clusterer beside kmvp_kmeans and
+ * kmvp_gaussian_meanshift; sklearn.cluster.DBSCAN, density clustering without a cluster count).  The points are clustered
+ * among themselves: the context's targets must be its sources (x == NULL at kmvp_set_points).
+ * THE DEFINITION is canonical -- it does not depend on the order of the points, on the grid or on scheduling:
+ *  - inside   pair (i, j) is inside iff s_ij <= r2: kmvp_radius_count's rule exactly -- s the family's difference-form
+ *             squared distance in the working precision, r2 = (real)(R * R) with R * R formed in double, a pair at exactly
+ *             r2 inside, a NaN s outside.  The difference form is symmetric bit for bit: the graph is undirected.
+ *  - counts   counts[i] is what kmvp_radius_count(ctx, R, 0, .) returns, bit for bit: the point itself is included
+ *             (sklearn's convention); a point with a NaN coordinate gets -1.
+ *  - core     i is a core point iff counts[i] >= min_samples.
+ *  - cluster  a connected component of the graph on the core points with the inside pairs as edges.  Its root is the
+ *             smallest caller's index among its core points; clusters are numbered 0 .. C - 1 in ascending order of their
+ *             roots.  That is the numbering sklearn's DBSCAN produces: core labels and the noise set agree with it exactly.
+ *  - border   a point that is no core point and has a core point inside joins the cluster of its NEAREST inside core point,
+ *             the minimum of the pair (s, caller's index) -- the order of kmvp_radius_nearest.  sklearn gives such a point
+ *             to whichever cluster its traversal reaches first, which depends on the order of the points; this rule does not.
+ *  - noise    every other point: label -1.  That covers the points with a NaN or infinite coordinate, which are inside of
+ *             nothing (count -1, resp. 0) and join nothing.
+ * Outputs, caller-owned, written during the call: labels (N int64); core_of_or_null (N int64: the point itself for a core
+ * point, the core point it was attached to for a border point, -1 for noise); counts_or_null (N int64);
+ * info = [n_clusters, n_core, n_border, n_noise, rounds, walks].  N == 0 writes zeros to info (if given) and returns KMVP_OK.
+ * How (csrc/kmvp_dbscan.hip): the count's walk once; then rounds of one walk each (lowd_cutoff_label_kernel,
+ * csrc/kmvp_lowd_cutoff_label.hpp: the count's pair loop with one select and one integer minimum per pair, the labels read
+ * beside the records through the scalar cache) in which every core point takes the smallest label among its inside core
+ * points, followed by an integer hook-and-chase step over O(N) words (csrc/kmvp_dbscan_step.hpp) that lets whole trees
+ * fall at once; a round that changes nothing ends them -- labels only fall, so there is no maxit; the host reads one word
+ * per round.  Then one walk attaches the border points, and a scan numbers the clusters.  `rounds` counts the rounds, the
+ * last one included (0: there is no core point); `walks` the passes over the cell list: the count, the rounds, the border
+ * walk (left out when there is no core point or nothing else).  O(N) integers of state never leave the device.
+ *  - bitwise reproducible run to run, rounds included; independent of "cutoff_cell_factor" and of "cutoff_plan";
+ *  - the plan cache on (points, R, factor, "cutoff_plan"), the target image, the density-layout records and the int32
+ *    source map are kmvp_radius_count's and kmvp_radius_nearest's; the label buffers are its own: every other entry returns
+ *    the same bits before and after the call.  kmvp_set_signal is neither needed nor consulted; kmvp_cutoff_info is valid
+ *    afterwards;
+ *  - kmvp_last_kernel_name is "lowd_cutoff_label_kernel", kmvp_last_kernel_ms is the sum of the walks, kmvp_last_total_ms
+ *    the whole call.
+ * KMVP_E_INVALID: a radius that is not finite or not > 0, min_samples < 1, a NULL labels or info with N > 0, no points set,
+ * targets that are not the sources.  KMVP_E_UNSUPPORTED with a message that names DBSCAN and the cause: everything
+ * kmvp_radius_count refuses -- a bfloat16 context, D > 3, an attached communicator, a source slice, batches.
+ * KMVP_E_DEVICE should the labels not settle within N rounds (they cannot: every round but the last removes a root).
+ * Not built: sample weights, targets != sources (predicting the cluster of new points), D > 3, shards, batches,
+ * HDBSCAN / OPTICS, the unbounded neighbour list. */
+int kmvp_dbscan(kmvp_ctx* ctx, double radius, int64_t min_samples, int64_t* labels, int64_t* core_of_or_null, int64_t* counts_or_null,
+                int64_t info[6]);
+
 /* Wendland's compactly supported kernels (an extension: the reference has none) -- the cutoff WITHOUT a truncation error,
  * and the library's first sparse operator for conjugate gradients.  With the support radius R, t = |x - y| / R and
  * u = max(1 - t, 0):

@@ -70,6 +70,7 @@ SYMBOLS = [
     ("kmvp_wendland_c4_cutoff_grad", _c.c_int, [_c.c_void_p, _c.c_double]),
     ("kmvp_radius_count", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p]),
     ("kmvp_radius_nearest", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    ("kmvp_dbscan", _c.c_int, [_c.c_void_p, _c.c_double, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     ("kmvp_cutoff_info", _c.c_int, [_c.c_void_p, _c.c_void_p]),
     ("kmvp_cutoff_plan_read", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     ("kmvp_kmeans", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
@@ -423,6 +424,20 @@ class Context:
         self._check(self._lib.kmvp_radius_nearest(self._ctx, float(radius), K, 1 if exclude_self else 0, idx.ctypes.data,
                                                   sqdist.ctypes.data))
         return idx, sqdist
+
+    def dbscan(self, radius, min_samples):
+        """DBSCAN of the points among themselves (include/kmvp.h kmvp_dbscan): (labels, core_of, counts, info), three (N,)
+        int64 arrays -- the cluster of every point (-1: noise), the core point it belongs to a cluster through (itself for
+        a core point, -1 for noise), radius_count()'s counts -- and a dict of n_clusters, n_core, n_border, n_noise, rounds
+        and walks."""
+        # the library writes N values through each pointer: the arrays are sized here, from the points it was given
+        N = int(getattr(self, "N", 0))
+        labels, core_of, counts = (np.full(N, -1, dtype=np.int64) for _ in range(3))
+        info = np.zeros(6, dtype=np.int64)
+        self._check(self._lib.kmvp_dbscan(self._ctx, float(radius), int(min_samples), labels.ctypes.data, core_of.ctypes.data,
+                                          counts.ctypes.data, info.ctypes.data))
+        names = ("n_clusters", "n_core", "n_border", "n_noise", "rounds", "walks")
+        return labels, core_of, counts, {k: int(v) for k, v in zip(names, info)}
 
     def cutoff_info(self):
         """The plan of the last cutoff call (include/kmvp.h kmvp_cutoff_info): a dict of cells (3 per-axis counts),

@@ -1920,3 +1920,125 @@ class MI355XMeanShift:
             self.done()
         except Exception:
             pass
+
+
+class MI355XDBSCAN:
+    """DBSCAN on one MI355X, resident on the device (include/kmvp.h kmvp_dbscan; the pair loops are
+    lowd_cutoff_count_kernel and lowd_cutoff_label_kernel on the cutoff's cell list).  The third clusterer beside
+    MI355XKMeans and MI355XMeanShift: density clustering without a cluster count.  An extension: the reference's plugin API
+    has no such role, so the class is not registered in algos.yaml.
+
+        core point    at least min_samples points within eps, itself included (sklearn's convention)
+        cluster       a connected component of the core points under "within eps", numbered in ascending order of its
+                      smallest core index -- the numbering sklearn.cluster.DBSCAN gives
+        border point  a point that is no core point with a core point within eps: it joins the cluster of the NEAREST one
+                      (ties: the smaller index).  sklearn's choice depends on its traversal order, this one does not
+        noise         everything else, label -1
+
+    Call order: prepare_data, set_query_arguments, query, then get_labels / get_core_sample_indices / get_core_of /
+    get_counts / get_additional, done.  D <= 3; float16 / float32 / float64.  ``options``: device, cutoff_plan ("host" or
+    "device": the side that builds the cell-list plan; the same result), cutoff_cell_factor (the cells' side in units of
+    eps, >= 1; the same result)."""
+
+    def __init__(self, *, eps, min_samples, dimension, precision=np.float32, device=0, cutoff_plan="host", cutoff_cell_factor=None):
+        self.dimension = int(dimension)
+        self.precision = precision
+        self._dtype_code, self._host_dtype = _lib.dtype_code(precision)
+        if self._dtype_code == _lib.KMVP_BF16:
+            raise NotImplementedError("MI355XDBSCAN: float32, float64 and float16 only")
+        if self.dimension > 3:
+            raise NotImplementedError(f"MI355XDBSCAN: dimension = {self.dimension} is beyond the cell list's D <= 3")
+        self._round = _lib.input_rounding(precision)  # float16: rounded points, float32 arithmetic
+        self.device = device
+        self._cutoff_plan = _cutoff_plan_code(cutoff_plan)
+        self._cell_factor = None if cutoff_cell_factor is None else float(cutoff_cell_factor)
+        self._ctx = None
+        self.labels = self.core_of = self.counts = self.info = None
+        self.set_query_arguments(eps=eps, min_samples=min_samples)
+        self.name = f"MI355XDBSCAN({_precision_name(precision)}, eps={self.eps}, min_samples={self.min_samples})"
+
+    # -- untimed -------------------------------------------------------------------
+    def prepare_data(self, *, points):
+        p = np.asarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != self.dimension:
+            raise ValueError(f"points has shape {p.shape}, expected (N, {self.dimension})")
+        if self._round is not None:
+            p = p.astype(self._round)
+        x = np.ascontiguousarray(p, dtype=self._host_dtype)
+        self.N, self.D = x.shape
+        self._x = x  # the points as the device holds them
+        if self._ctx is None:
+            self._ctx = _lib.Context(self.device)
+            if self._cutoff_plan:
+                self._ctx.set_option("cutoff_plan", self._cutoff_plan)
+            if self._cell_factor is not None:
+                self._ctx.set_option("cutoff_cell_factor", self._cell_factor)
+        self._ctx.set_points(x, None, self._dtype_code)  # the cloud is its own target set: the points of kmvp_dbscan
+        self.labels = self.core_of = self.counts = self.info = None
+
+    def set_query_arguments(self, eps=None, min_samples=None):
+        if eps is not None:
+            if not (np.isfinite(float(eps)) and float(eps) > 0):
+                raise ValueError(f"eps must be finite and > 0, not {eps!r}")
+            self.eps = float(eps)
+        if min_samples is not None:
+            if int(min_samples) != min_samples or int(min_samples) < 1:
+                raise ValueError(f"min_samples must be an integer >= 1, not {min_samples!r}")
+            self.min_samples = int(min_samples)
+
+    # -- timed ---------------------------------------------------------------------
+    def fit(self):
+        """Nothing to build ahead of the first query: it plans and packs itself, once per (points, eps)."""
+
+    def query(self):
+        """Clusters the points.  Synchronous; every failure raises."""
+        if self._ctx is None:
+            raise RuntimeError("MI355XDBSCAN.query() needs prepare_data() first")
+        self.labels, self.core_of, self.counts, self.info = self._ctx.dbscan(self.eps, self.min_samples)
+
+    # -- results -------------------------------------------------------------------
+    def _need_solution(self, method):
+        if self.labels is None:
+            raise RuntimeError(f"MI355XDBSCAN.{method}: no solution yet -- call query() after prepare_data() first")
+
+    def get_labels(self):
+        """(N,) int64: the cluster of every point, -1 for noise (sklearn's labels_ on the core points and the noise)."""
+        self._need_solution("get_labels")
+        return self.labels
+
+    def get_core_sample_indices(self):
+        """The indices of the core points in ascending order (sklearn's core_sample_indices_)."""
+        self._need_solution("get_core_sample_indices")
+        return np.flatnonzero(self.core_of == np.arange(self.N))
+
+    def get_core_of(self):
+        """(N,) int64: the point itself for a core point, the core point a border point was attached to, -1 for noise."""
+        self._need_solution("get_core_of")
+        return self.core_of
+
+    def get_counts(self):
+        """(N,) int64: the points within eps of every point, itself included; -1 for a point with a NaN coordinate."""
+        self._need_solution("get_counts")
+        return self.counts
+
+    def get_memory_usage(self):
+        """Device kB held by the context."""
+        return (self._ctx.device_bytes if self._ctx is not None else 0) / 1024
+
+    def get_additional(self):
+        extra = dict(self.info or {})
+        if self._ctx is not None:
+            extra.update(device_kernel_ms=self._ctx.last_kernel_ms, device_total_ms=self._ctx.last_total_ms,
+                         device_kernel=self._ctx.last_kernel_name, device_bytes=self._ctx.device_bytes)
+        return extra
+
+    def done(self):
+        if self._ctx is not None:
+            self._ctx.close()
+        self._ctx = None
+
+    def __del__(self):
+        try:
+            self.done()
+        except Exception:
+            pass

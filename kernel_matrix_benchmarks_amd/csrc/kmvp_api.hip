@@ -91,7 +91,7 @@ void kmvp_destroy(kmvp_ctx* c) {
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   for (DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled, &c->y_scaled,
                     &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state, &c->ct_tiles, &c->ct_runs, &c->ct_tmap, &c->ct_smap, &c->ct_xs, &c->ct_rec, &c->ct_smap32, &c->ct_work,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state, &c->ct_tiles, &c->ct_runs, &c->ct_tmap, &c->ct_smap, &c->ct_xs, &c->ct_rec, &c->ct_smap32, &c->ct_work, &c->db_state, &c->db_rec, &c->db_tmp,
                     &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     release(*b);
   for (int i = 0; i < 5; ++i)
@@ -231,6 +231,10 @@ int kmvp_wendland_c4_cutoff_grad(kmvp_ctx* c, double radius) { return run_cutoff
 int kmvp_radius_count(kmvp_ctx* c, double radius, int exclude_self, int64_t* counts) { return radius_count(c, radius, exclude_self, counts); }
 int kmvp_radius_nearest(kmvp_ctx* c, double radius, int K, int exclude_self, int64_t* out_idx, double* out_sqdist) {
   return radius_nearest(c, radius, K, exclude_self, out_idx, out_sqdist);
+}
+int kmvp_dbscan(kmvp_ctx* c, double radius, int64_t min_samples, int64_t* labels, int64_t* core_of_or_null, int64_t* counts_or_null,
+                int64_t* info) {
+  return dbscan_solve(c, radius, min_samples, labels, core_of_or_null, counts_or_null, info);
 }
 int kmvp_cutoff_info(kmvp_ctx* c, int64_t* out) { return cutoff_info(c, out); }
 int kmvp_cutoff_plan_read(kmvp_ctx* c, int64_t* sizes, double* grid, int64_t* tiles, int64_t* runs, int64_t* tmap, int64_t* smap) {
@@ -557,7 +561,7 @@ int64_t kmvp_device_bytes(const kmvp_ctx* c) {
   size_t t = 0;
   for (const DevBuf* b : {&c->y_raw, &c->x_raw, &c->b_raw, &c->xs, &c->rec, &c->x_scaled,
                           &c->y_scaled, &c->part, &c->partd, &c->aux, &c->sortbuf, &c->perm, &c->sums, &c->out, &c->scratch, &c->sdiag, &c->precond, &c->knn, &c->xchg, &c->kexp, &c->kshift, &c->xchgk, &c->kflag,
-                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state, &c->ct_tiles, &c->ct_runs, &c->ct_tmap, &c->ct_smap, &c->ct_xs, &c->ct_rec, &c->ct_smap32, &c->ct_work,
+                    &c->sk_xs_x, &c->sk_rec_y, &c->sk_xs_y, &c->sk_rec_x, &c->sk_state, &c->km_xs, &c->km_rec, &c->km_part, &c->km_state, &c->ms_xs, &c->ms_state, &c->ms_tmp, &c->bt_tiles, &c->bt_tmap, &c->bt_smap, &c->bt_xs, &c->bt_rec, &c->skb_plan, &c->skb_xs, &c->skb_rec, &c->skb_state, &c->ct_tiles, &c->ct_runs, &c->ct_tmap, &c->ct_smap, &c->ct_xs, &c->ct_rec, &c->ct_smap32, &c->ct_work, &c->db_state, &c->db_rec, &c->db_tmp,
                           &c->cell_tperm, &c->cell_sperm, &c->cell_tgrp, &c->cell_sgrp, &c->cell_slot, &c->cell_tmeta, &c->cell_sums, &c->cell_skey, &c->cell_scentre, &c->cell_scale, &c->cell_tcentre, &c->cell_scentre32})
     t += b->cap;
   return (int64_t)t;

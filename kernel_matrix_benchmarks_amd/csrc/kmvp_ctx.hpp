@@ -10,6 +10,7 @@
 //   kmvp_batch.hip    batched clouds: block-diagonal products and nearest neighbours on layouts of their own
 //   kmvp_precond.hip  the pivoted-Cholesky preconditioner of conjugate gradients: build, apply, read-back
 //   kmvp_cutoff.hip   cutoff-radius products and neighbour counts on a cell list, on layouts of their own
+//   kmvp_dbscan.hip   DBSCAN on that cell list: core counts, label sweeps, border attachment
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -197,6 +198,9 @@ struct kmvp_ctx {
   double ct_grid[4] = {0.0, 0.0, 0.0, 0.0};  // ct_info: lo[3] and h,
   int64_t ct_tiles_n = 0;                    // the tiles of the table (fillers included)
   DevBuf ct_work;               // the device build's keys, sorted clouds, scans and hipcub's scratch: nothing survives a build
+  // DBSCAN (kmvp_dbscan.hip): the per-point state (counts, labels, the round's arrays, the outputs, the state words), the
+  // labels in record order that the pair loop reads beside the records, and hipcub's scratch of the renumbering scan
+  DevBuf db_state, db_rec, db_tmp;
   double ct_solve_radius = 0.0;  // kmvp_wendland_<c>_cg_solve: the support radius cg_apply's operator runs at (0: no such solve is running)
   uint64_t points_ver = 0, signal_ver = 0;
   // what xs / rec / scaled copies currently hold
@@ -423,6 +427,15 @@ int wendland_cg_solve(kmvp_ctx* c, int kernel, double radius, const void* a_host
 // cg_apply's operator for the Wendland kernels: the E signal slots of the records straight from the float64 (M, E) vector v,
 // then the pair loop into c->out -- two launches.  While c->async_product is set: no event, no synchronisation, no host check.
 int cutoff_apply(kmvp_ctx* c, int kernel, const double* v, int E);
+
+// kmvp_cutoff.hip, for kmvp_dbscan.hip: kmvp_radius_count's refusals under the name `what`; and its setup and walk -- the
+// cached plan, the target image, the density-layout records, ct_smap32, then lowd_cutoff_count_kernel into the device
+// array `counts` (N values) between ev[3] and ev[1], left on the stream.  N == 0: the plan alone.
+int cutoff_refuse(kmvp_ctx* c, const std::string& what);
+int cutoff_count_device(kmvp_ctx* c, double radius, int64_t* counts);
+// kmvp_dbscan.hip: kmvp_dbscan, density clustering on the cell list -- the count, then sweeps of lowd_cutoff_label_kernel
+// with an integer hook-and-chase step between them, one border walk and the renumbering, all resident on the device
+int dbscan_solve(kmvp_ctx* c, double radius, int64_t min_samples, int64_t* labels, int64_t* core_of, int64_t* counts, int64_t* info);
 
 // kmvp_meanshift.hip: kmvp_gaussian_meanshift, the device-resident mean-shift iteration on lowd_lse_grad_kernel
 int meanshift_solve(kmvp_ctx* c, double tol, int maxit, double* modes, int* iters, double* step2, int* sweeps,

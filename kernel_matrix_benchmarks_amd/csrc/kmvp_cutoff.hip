@@ -10,6 +10,7 @@
 //   radius_count     the neighbour counts on lowd_cutoff_count_kernel
 //   radius_nearest   the K nearest sources inside the radius on lowd_cutoff_knn_kernel: the count's plan and packs, and an
 //                    int32 copy of the plan's source map, narrowed on the device once per plan
+//   cutoff_count_device  the count's setup and walk with the counts left on the device: the first step of kmvp_dbscan.hip
 //   wendland_cg_solve / cutoff_apply   conjugate gradients (kmvp_solvers.hip cg_solve) with the Wendland cutoff product as
 //                    its operator: plan and packs once, then two launches per application
 // Target image, records, tables and maps live in buffers of their own (ct_*): the product's pack bookkeeping
@@ -331,6 +332,17 @@ __global__ void cutoff_narrow_smap_kernel(const int64_t* __restrict__ smap, int3
   if (s < m_alloc) smap32[s] = (int32_t)smap[s];
 }
 
+int cutoff_smap32(kmvp_ctx* c) {
+  if (c->ct_smap32_ver == c->ct_ver) return KMVP_OK;
+  int rc;
+  if ((rc = ensure(c, c->ct_smap32, (size_t)c->ct_m_alloc * sizeof(int32_t)))) return rc;
+  hipLaunchKernelGGL(cutoff_narrow_smap_kernel, dim3(blocks_for(c->ct_m_alloc)), dim3(256), 0, c->stream,
+                     (const int64_t*)c->ct_smap.p, (int32_t*)c->ct_smap32.p, c->ct_m_alloc);
+  HIP_TRY(c, hipGetLastError());
+  c->ct_smap32_ver = c->ct_ver;
+  return KMVP_OK;
+}
+
 inline hipError_t launch_cutoff_knn(int D, int KT, const LowdCutoffArgs<float>& a, dim3 grid, hipStream_t s, const char** name) {
   return launch_lowd_cutoff_knn_f32(D, KT, a, grid, s, name);
 }
@@ -347,13 +359,7 @@ int radius_nearest_t(kmvp_ctx* c, double radius, int K, int exclude_self, int64_
   HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
   if ((rc = cutoff_prepare<real>(c, radius))) return rc;
   if ((rc = pack_cutoff<real>(c, R, 0))) return rc;
-  if (c->ct_smap32_ver != c->ct_ver) {
-    if ((rc = ensure(c, c->ct_smap32, (size_t)c->ct_m_alloc * sizeof(int32_t)))) return rc;
-    hipLaunchKernelGGL(cutoff_narrow_smap_kernel, dim3(blocks_for(c->ct_m_alloc)), dim3(256), 0, c->stream,
-                       (const int64_t*)c->ct_smap.p, (int32_t*)c->ct_smap32.p, c->ct_m_alloc);
-    HIP_TRY(c, hipGetLastError());
-    c->ct_smap32_ver = c->ct_ver;
-  }
+  if ((rc = cutoff_smap32(c))) return rc;
   // the rows in c->knn, as kmvp_nearest: (N, K) int64 indices, then (N, K) float64 squared distances
   const size_t nk = (size_t)c->N * K;
   if ((rc = ensure(c, c->knn, nk * (sizeof(int64_t) + sizeof(double))))) return rc;
@@ -437,7 +443,33 @@ int cutoff_solve_prepare(kmvp_ctx* c, double radius, int E) {
   return KMVP_OK;
 }
 
+// cutoff_count_device for one precision: radius_count_t's setup and launch, the index copy, nothing read back.
+template <typename real>
+int cutoff_count_device_t(kmvp_ctx* c, double radius, int64_t* counts) {
+  const int D = c->D;
+  const int R = (D + 3) / 4 * 4;  // density layout: no signal columns
+  int rc;
+  if ((rc = cutoff_prepare<real>(c, radius))) return rc;
+  if (c->N == 0) return KMVP_OK;
+  if ((rc = pack_cutoff<real>(c, R, 0))) return rc;
+  if ((rc = cutoff_smap32(c))) return rc;
+  LowdCutoffArgs<real> a = cutoff_args<real>(c, radius);
+  a.counts = counts;
+  HIP_TRY(c, hipEventRecord(c->ev[3], c->stream));
+  hipError_t le = launch_cutoff_count(D, a, dim3((unsigned)(c->ct_n_pad / (CUTOFF_TILE * CUTOFF_WAVES))), c->stream, &c->last_kernel_name);
+  if (le == hipErrorInvalidValue) return fail(c, KMVP_E_UNSUPPORTED, "cutoff radius: no count kernel instantiated for this D");
+  HIP_TRY(c, le);
+  HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
+  return KMVP_OK;
+}
+
 }  // namespace
+
+int cutoff_refuse(kmvp_ctx* c, const std::string& what) { return cutoff_unsupported(c, what); }
+
+int cutoff_count_device(kmvp_ctx* c, double radius, int64_t* counts) {
+  return c->dtype == KMVP_F64 ? cutoff_count_device_t<double>(c, radius, counts) : cutoff_count_device_t<float>(c, radius, counts);
+}
 
 int run_cutoff(kmvp_ctx* c, int kernel, double radius, bool normalise) {
   if (!c) return KMVP_E_INVALID;
