@@ -60,10 +60,15 @@ __device__ __forceinline__ double lse_neg_logit(double s) {
   }
 }
 
-// 2^-a for a >= 0 (a = m - u; +inf and anything beyond the format's range give exactly 0; NaN stays NaN)
+// 2^-a for a >= 0 (a = m - u; +inf and anything beyond the format's range give exactly 0; NaN stays NaN).  a is NaN for a
+// log-weight of NaN, and for one of +inf (m = +inf, inf - inf): v_exp_f32 passes it on, so the column's sum is NaN and
+// the column not finite, as include/kmvp.h says.  kexp_neg_f64 clamps its argument with a min, which returns its OTHER
+// argument for a NaN: the weight came out exactly 0 and the column finite (c = +inf: finite wherever another segment had
+// a live term) -- hence the select, which changes no result of a finite a.
 __device__ __forceinline__ float lse_exp2_neg(float a, const double*) { return kexp2(-a); }
 __device__ __forceinline__ double lse_exp2_neg(double a, const double* __restrict__ tab) {
-  return kexp_neg_f64(a * 0.6931471805599453, tab);
+  const double w = kexp_neg_f64(a * 0.6931471805599453, tab);
+  return (a == a) ? w : a;
 }
 
 // x 2^d for an integer-valued d <= 0 held in floating point (-inf allowed): exact

@@ -22,13 +22,15 @@
 // Terms that must contribute exactly 0 to Z and to V: c = -inf, pairs whose squared distance overflowed, pad records.
 // All have u = -inf and so the weight 2^-inf = 0 (m starts from lowd_lse_kernel's finite sentinel).  For the first two
 // x - y is finite and 0 (x - y) = 0.  A pad record has x - y = -inf and 0 * -inf is NaN: pad records only exist among the
-// last 2 U records of the array, and only the batches that reach into them zero x - y where s is not below inf (GUARD,
-// as lowd_grad_kernel's).
+// last 2 U records of the array, and only the batches that reach into them zero x - y of the records from a.m on (GUARD,
+// as lowd_grad_kernel's: by the record's INDEX, not by s < inf -- that select also took a real source with an infinite
+// coordinate for a pad record, so the components include/kmvp.h calls NaN came out finite when, and only when, the
+// source stood among the last 8 records).
 // exp(-r) at s = 0 (not differentiable: 0 is the symmetric subgradient, and the own pair of same_points must drop out):
 // 1 / r comes from rsq(s) kept for the positive NORMAL s only (lowd_grad_kernel's select), so a coincident pair adds 0
 // to V and keeps its weight in Z.  The logit itself is lse_neg_logit's: L and G see the same weights.
 // A NaN target coordinate: the lane is marked once and all its sums are NaN at the store, as lowd_lse_kernel.
-// c = NaN or +inf: the weight of that pair is NaN (float64: by a select on m - u, see the batch step), so Z and with it all
+// c = NaN or +inf: the weight of that pair is NaN (float64: by lse_exp2_neg's select on m - u), so Z and with it all
 // D components of that column are NaN; the other columns are untouched.
 //
 // Each (segment, column, target) leaves the D + 1 fp64 sums and ONE exponent -m in the `kexp` convention (+inf: no live
@@ -47,9 +49,10 @@ __device__ __forceinline__ real lse_grad_rinv(real s, const double* __restrict__
   return positive_normal(s) ? q : (real)0;
 }
 
-// One batch of U sources against the lane's target: logits, the shift's move, the D + 1 sums per column.
+// One batch of U sources against the lane's target: logits, the shift's move, the D + 1 sums per column.  GUARD: the
+// batch's records from n_real on are pad records.
 template <int KERNEL, int D, int E, int SIG, int U, bool GUARD, typename real>
-__device__ __forceinline__ void lse_grad_batch_step(const real (&x)[D], const real* __restrict__ rec,
+__device__ __forceinline__ void lse_grad_batch_step(const real (&x)[D], const real* __restrict__ rec, int n_real,
                                                     real (&m)[LseLayout<E, SIG>::NC],
                                                     real (&acc)[LseLayout<E, SIG>::NC][D + 1],
                                                     double (&accd)[LseLayout<E, SIG>::NC][D + 1],
@@ -71,7 +74,7 @@ __device__ __forceinline__ void lse_grad_batch_step(const real (&x)[D], const re
     }
     if constexpr (GUARD) {
       // a pad record: its weight is 0 by itself (u = -inf), but 0 * (x - y) = 0 * -inf is NaN -- the differences go to 0
-      const bool live = s < (real)INFINITY;
+      const bool live = k < n_real;
 #pragma unroll
       for (int d = 0; d < D; ++d) df[k][d] = live ? df[k][d] : (real)0;
     }
@@ -114,10 +117,8 @@ __device__ __forceinline__ void lse_grad_batch_step(const real (&x)[D], const re
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const real a = m[c] - u[k][c];
-      real w = lse_exp2_neg(a, tab);
-      // c = NaN, or c = +inf (m = +inf, a = inf - inf): the column must not come out finite.  v_exp_f32 passes the NaN on;
-      // the float64 exp clamps its argument with a min, which would turn it into a weight of exactly 0
-      if constexpr (sizeof(real) == 8) w = (a == a) ? w : a;
+      // c = NaN, or c = +inf (m = +inf, a = inf - inf): the column must not come out finite -- lse_exp2_neg passes the NaN on
+      const real w = lse_exp2_neg(a, tab);
       acc[c][0] += w;
       real wq = w;
       if constexpr (KERNEL == K_ABSEXP) wq = w * q[k];
@@ -227,9 +228,12 @@ __global__ void __launch_bounds__(BLOCK_THREADS) lowd_lse_grad_kernel(const Lowd
     if (jt + cnt > pad_from) cnt_plain = jt < pad_from ? (int)(pad_from - jt) : 0;
     int jj = 0;
     for (; jj < cnt_plain; jj += U)
-      lse_grad_batch_step<KERNEL, D, E, SIG, U, false, real>(x, lrec + jj * R, m, acc, accd, exp_tab);
-    for (; jj < cnt; jj += U)
-      lse_grad_batch_step<KERNEL, D, E, SIG, U, true, real>(x, lrec + jj * R, m, acc, accd, exp_tab);
+      lse_grad_batch_step<KERNEL, D, E, SIG, U, false, real>(x, lrec + jj * R, U, m, acc, accd, exp_tab);
+    for (; jj < cnt; jj += U) {
+      const int64_t left = a.m - (jt + jj);  // real records from this batch's first on
+      const int n_real = left < 0 ? 0 : left < U ? (int)left : U;
+      lse_grad_batch_step<KERNEL, D, E, SIG, U, true, real>(x, lrec + jj * R, n_real, m, acc, accd, exp_tab);
+    }
     since_fold += LDS_TILE;
     if (since_fold >= a.chunk) {
       fold();
